@@ -12,6 +12,11 @@ segments, match_branch(+link), resolve, scan, emit.  The timed region starts wit
 ends with dense uint32 ids + offsets in HBM.  `value` = raw UTF-8 bytes of all ranks x K / max-over-ranks wall time.
 (--hot-path-only times the tokenize kernels alone on host-normalized input, as rounds before the GPU normalizer did.)
 
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds everything beside the headline: the
+checks against the oracle and the reference runtime, per-kernel times and rooflines (with their rocprofv3 counter passes),
+the CPU baselines, the host-to-host pipeline and the tables laid out by use.  --dump-outputs DIR writes what the last timed
+step computed as DIR/<name>.npy (see dump_outputs).
+
 Prints ONE JSON line on rank 0 (see README / DESIGN.md for the roofline and cpu_baseline objects).
 """
 import argparse
@@ -70,7 +75,66 @@ def parse():
                     help="do not measure roofline.traffic / roofline_valu in this run (default: three rocprofv3 --pmc passes - instruction counts, FETCH_SIZE, "
                          "WRITE_SIZE - over tools/k1_time.py in a child process, about a minute; without them the figures of profiles/traffic_latest.json are "
                          "reported and labelled as static)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything beside the headline figure (verification, per-kernel times and rooflines, counter passes, CPU "
+                         "baselines, host-to-host pipeline, tables laid out by use); off: set up, warm up, time the steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (rank 0's shard, device 0's with --in-process) as DIR/<name>.npy, "
+                         "float32 / float64, at most 64 MB")
     return ap.parse_args()
+
+
+def config_image(synth, name):
+    """the .vocab image of a named shape: from the cache beside the package, or made again (it is deterministic in its seed) where the
+    checkout is read-only and the cache cannot be written"""
+    try:
+        return synth.config_vocab(name)
+    except OSError:
+        return synth.config_vocab(name, cache=False)
+
+
+DUMP_LIMIT = 64 << 20
+DUMP_SEED = 0x44554D50
+DUMP_SAMPLE_DOCS = 8192
+
+
+def dump_outputs(dirname, arrays, log):
+    """--dump-outputs: every array as DIR/<name>.npy; the inputs are seeded, so two builds compare output for output"""
+    arrays = {k: np.ascontiguousarray(v) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit("bench.py: --dump-outputs would write %d bytes, more than %d" % (total, DUMP_LIMIT))
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    log("outputs of the last timed step: %s in %s (%.1f MB)" % (", ".join(sorted(arrays)), dirname, total / 1e6))
+
+
+def score_outputs(res):
+    """a scoring pass's histogram (scores u32[n_ids], tokens_in_text, missing_set u8[32]) as --dump-outputs writes it"""
+    scores, tokens, missing = res
+    return {"scores": np.asarray(scores).astype(np.float64), "tokens_in_text": np.array([tokens], dtype=np.float64),
+            "missing_set": np.asarray(missing).astype(np.float64)}
+
+
+def stream_outputs(prefix, data, offs, per_doc=None):
+    """a batch's packed output (token ids, or decoded bytes, with the offsets of its documents) as --dump-outputs writes it: every
+    document's offset (and `per_doc` value), the sums of the values over 65536 equal slices of the whole stream, and the values
+    themselves of a fixed, seeded sample of documents.  Past 1M documents the per-document arrays hold the sample's documents only."""
+    nd = offs.size - 1
+    offs = offs[: nd + 1].astype(np.int64)
+    pick = np.sort(np.random.default_rng(DUMP_SEED).choice(nd, size=min(nd, DUMP_SAMPLE_DOCS), replace=False))
+    n = int(offs[-1])
+    cut = np.unique(np.linspace(0, n, 65537).astype(np.int64))[:-1]
+    out = {prefix + "_sample_docs": pick.astype(np.float64),
+           prefix + "_sample": np.concatenate([data[offs[d]:offs[d + 1]] for d in pick] + [data[:0]])[: 6 << 20].astype(np.float32),
+           prefix + "_slice_sums": (np.add.reduceat(data[:n], cut, dtype=np.uint64) if n else np.zeros(0)).astype(np.float64)}
+    docs = slice(None) if nd <= (1 << 20) else pick
+    out[prefix + "_offsets"] = np.stack([offs[:-1][docs], offs[1:][docs]]).astype(np.float64)
+    if per_doc is not None:
+        out[prefix + "_" + per_doc[0]] = np.asarray(per_doc[1][:nd])[docs].astype(np.float64)
+    return out
 
 
 def cpu_baseline(img, text, offs, sample_mb, log, raw_mode=False, check=None):
@@ -320,6 +384,8 @@ def bench_score(args, rank, local_rank, world, vocab, img, kind, capcode, norm_f
         dist.all_reduce(tot, op=dist.ReduceOp.SUM)
     all_raw, all_norm = float(tot[0].item()), float(tot[1].item())
     scores, tokens, missing = tmdist.decode_histogram(hist.cpu().numpy(), n_ids)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, score_outputs((scores, tokens, missing)), log)
     verified = None
     if rank == 0 and world == 1 and args.verify != 0:
         # bit-exact check against the oracle's scoring mode (outside the timed region): the whole buffer where the host has the cores for it
@@ -424,28 +490,44 @@ def bench_decode(args, rank, local_rank, world, vocab, img, kind, capcode, norm_
         elapsed = float(t.item())
         dist.all_reduce(tot, op=dist.ReduceOp.SUM)
     all_out = float(tot[0].item())
-    # the stages of one pass by HIP events on the launch stream
-    ms = (C.c_float * 3)()
-    acc = np.zeros(3)
-    for _ in range(3):
-        N.check(N.lib.tm_batch_decode_timed(batch, 0, C.c_void_p(stream), C.byref(nbytes), C.byref(host_docs), ms))
-        acc += np.array(list(ms))
-    acc /= 3
-    stage_ms = {"tile_lengths_scan": round(float(acc[0]), 4), "k_dec_gather": round(float(acc[1]), 4), "k_dec_capcode": round(float(acc[2]), 4)}
-    # algorithmic bytes of each stage: the byte counts of the tiles read the ids once (4T; the key lengths come out of a table of n_ids + 1 words that
-    # stays in the caches, and what is written is one word per 2048 ids); the gather reads them once more and writes the encoded text once (the keys
-    # come out of a 0.3 MB table); the capcode decoder reads the encoded text once and writes the decoded text once
-    T, n_enc = float(ntok.value), float(enc_bytes)
-    alg = {"tile_lengths_scan": 4 * T, "k_dec_gather": 4 * T + n_enc, "k_dec_capcode": n_enc + out_bytes}
-    dom = max(stage_ms, key=lambda k: stage_ms[k])
-    achieved = alg[dom] / (stage_ms[dom] * 1e-3) / 1e9 if stage_ms[dom] > 0 else 0.0
-    verified, verified_ref = None, None
-    cpu = None
-    if rank == 0:
-        # every document of the timed pass: the decoded text must be the NFD form of the raw text (no capcode, nothing missing) ...
+
+    def decoded():
         ooff = np.zeros(ndocs + 1, dtype=np.uint64)
         out = np.empty(int(raw.size) + int(raw.size) // 2 + 64, dtype=np.uint8)
         N.check(N.lib.tm_batch_decoded_download(batch, N.ptr(out), out.size, N.ptr(ooff)))
+        return out, ooff
+    if args.dump_outputs and rank == 0:
+        out, ooff = decoded()
+        dump_outputs(args.dump_outputs, stream_outputs("text", out, ooff), log)
+        del out, ooff
+    T, n_enc = float(ntok.value), float(enc_bytes)
+    stage_ms, roofline = None, None
+    if args.full:
+        # the stages of one pass by HIP events on the launch stream
+        ms = (C.c_float * 3)()
+        acc = np.zeros(3)
+        for _ in range(3):
+            N.check(N.lib.tm_batch_decode_timed(batch, 0, C.c_void_p(stream), C.byref(nbytes), C.byref(host_docs), ms))
+            acc += np.array(list(ms))
+        acc /= 3
+        stage_ms = {"tile_lengths_scan": round(float(acc[0]), 4), "k_dec_gather": round(float(acc[1]), 4), "k_dec_capcode": round(float(acc[2]), 4)}
+        # algorithmic bytes of each stage: the byte counts of the tiles read the ids once (4T; the key lengths come out of a table of n_ids + 1 words that
+        # stays in the caches, and what is written is one word per 2048 ids); the gather reads them once more and writes the encoded text once (the keys
+        # come out of a 0.3 MB table); the capcode decoder reads the encoded text once and writes the decoded text once
+        alg = {"tile_lengths_scan": 4 * T, "k_dec_gather": 4 * T + n_enc, "k_dec_capcode": n_enc + out_bytes}
+        dom = max(stage_ms, key=lambda k: stage_ms[k])
+        achieved = alg[dom] / (stage_ms[dom] * 1e-3) / 1e9 if stage_ms[dom] > 0 else 0.0
+        e2e_alg = 4 * T + 2 * out_bytes
+        roofline = {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 6),
+                    "traffic": None, "algorithmic_bytes_per_launch": alg[dom],
+                    "algorithmic_bytes_note": "tile_lengths_scan: 4T ids read; k_dec_gather: 4T ids read, encoded text written once; k_dec_capcode: encoded text read, decoded text written",
+                    "whole_pass": {"algorithmic_bytes": e2e_alg, "achieved": round(e2e_alg / (elapsed / args.steps) / 1e9, 3),
+                                   "frac": round(e2e_alg / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS, 6), "note": "4T + 2 N_out over the whole step"}}
+    verified, verified_ref = None, None
+    cpu = None
+    if rank == 0 and args.full:
+        # every document of the timed pass: the decoded text must be the NFD form of the raw text (no capcode, nothing missing) ...
+        out, ooff = decoded()
         if int(nmiss.value) == 0 and args.verify != 0:
             plain, poff = synth.normalize_batch(raw, roffs, 0, norm_flag)
             if int(ooff[-1]) != plain.size or not (ooff == poff).all() or not (out[: plain.size] == plain).all():
@@ -476,7 +558,6 @@ def bench_decode(args, rank, local_rank, world, vocab, img, kind, capcode, norm_
                                  "1 thread, %.1f s incl. the Python loop around it; every document compared with the device's text" % (done, nb / 1e6, dt)}
     if rank == 0:
         value = all_out * args.steps / elapsed / 1e9
-        e2e_alg = 4 * T + 2 * out_bytes
         line = {
             "metric": "GB/s of decoded UTF-8 text, Decode of englishcode-32000 id streams, device-resident", "value": round(value, 4), "unit": "GB/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
@@ -487,11 +568,7 @@ def bench_decode(args, rank, local_rank, world, vocab, img, kind, capcode, norm_
                        "parallelism": "documents sharded by rank, no collective", "rccl_ranks": dist.get_world_size() if world > 1 else 0,
                        "verified_docs_round_trip": verified, "verified_docs_vs_reference": verified_ref},
             "stage_ms": stage_ms,
-            "roofline": {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 6),
-                         "traffic": None, "algorithmic_bytes_per_launch": alg[dom],
-                         "algorithmic_bytes_note": "tile_lengths_scan: 4T ids read; k_dec_gather: 4T ids read, encoded text written once; k_dec_capcode: encoded text read, decoded text written",
-                         "whole_pass": {"algorithmic_bytes": e2e_alg, "achieved": round(e2e_alg / (elapsed / args.steps) / 1e9, 3),
-                                        "frac": round(e2e_alg / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS, 6), "note": "4T + 2 N_out over the whole step"}},
+            "roofline": roofline,
             "cpu_baseline": cpu,
         }
         print(json.dumps(line), flush=True)
@@ -567,6 +644,8 @@ def bench_in_process(args, img, kind, capcode, norm_flag, log):
         for _ in range(args.steps):
             res = ds.score(vs)
         elapsed = time.perf_counter() - t0
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, score_outputs(res), log)
         verified = None
         if args.verify != 0:
             one = tm.Vocab(img)
@@ -629,6 +708,15 @@ def bench_in_process(args, img, kind, capcode, norm_flag, log):
         raise errs[0]
     elapsed = max(done) - t0
     all_raw = float(sum(int(r.size) for r, _, _ in shards))
+    if args.dump_outputs:
+        # (device 0's batch)
+        b, nd = shards[0][2], shards[0][1].size - 1
+        nt = C.c_uint64()
+        N.check(N.lib.tm_batch_totals(b, C.byref(nt), None))
+        ids, toff, miss = np.empty(max(int(nt.value), 1), dtype=np.uint32), np.empty(nd + 1, dtype=np.uint64), np.empty(max(nd, 1), dtype=np.uint32)
+        N.check(N.lib.tm_batch_download(b, N.ptr(ids), int(nt.value), N.ptr(toff), N.ptr(miss)))
+        dump_outputs(args.dump_outputs, stream_outputs("ids", ids, toff, ("missing", miss)), log)
+        del ids, toff, miss
     # every document of every device against the reference runtime (RAW text through its Tokenize)
     verified = 0
     ntok_all = 0
@@ -682,6 +770,9 @@ TRAFFIC_NOTE = ("FETCH_SIZE / WRITE_SIZE count the requests on the memory side o
 
 def main():
     args = parse()
+    if not args.full:
+        # a plain run: set up, warm up, time the steps, print the line (every other leg belongs to --full)
+        args.verify, args.no_cpu_baseline, args.no_host_to_host, args.no_tuned_leg, args.measure_traffic = 0, True, True, True, False
     if args.also_flags:
         os.environ.setdefault("TM_TEST_HOOKS", "1")      # (the kernel-variant switches are inert unless the process is started this way)
     if args.gpus < 1:
@@ -698,7 +789,7 @@ def main():
         if args.config is None:
             args.config = "englishcode-32000-consistent" if args.workload == "tokenize" else "candidates-65536"
         kind0, _, capcode0, norm0, _, _ = synth0.CONFIGS[args.config]
-        return bench_in_process(args, synth0.config_vocab(args.config), kind0, capcode0, norm0, log0)
+        return bench_in_process(args, config_image(synth0, args.config), kind0, capcode0, norm0, log0)
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         spawn_ranks(args)
     rank = int(os.environ.get("RANK", "0"))
@@ -735,10 +826,10 @@ def main():
     kind, vsize, capcode, norm_flag, level, vseed = synth.CONFIGS[args.config]
     t0 = time.time()
     if rank == 0:
-        img = synth.config_vocab(args.config)
+        img = config_image(synth, args.config)
     if world > 1:
         dist.barrier()
-    img = synth.config_vocab(args.config)
+    img = config_image(synth, args.config)
     vocab = tm.Vocab(img)
     if args.tune_mib > 0:
         sraw, sroffs = synth.synth_corpus(kind, int(args.tune_mib * (1 << 20)), seed=0x434F5250 + 77)        # (not the corpus that is timed: another seed)
@@ -804,16 +895,22 @@ def main():
     ntok = C.c_uint64()
     nmiss = C.c_uint64()
     N.check(N.lib.tm_batch_totals(batch, C.byref(ntok), C.byref(nmiss)))
+    if args.dump_outputs and rank == 0:
+        ids = np.empty(max(int(ntok.value), 1), dtype=np.uint32)
+        toff = np.empty(ndocs + 1, dtype=np.uint64)
+        miss = np.empty(max(ndocs, 1), dtype=np.uint32)
+        N.check(N.lib.tm_batch_download(batch, N.ptr(ids), int(ntok.value), N.ptr(toff), N.ptr(miss)))
+        dump_outputs(args.dump_outputs, stream_outputs("ids", ids, toff, ("missing", miss)), log)
+        del ids, toff, miss
 
     normalize_ms = None
-    fallback_docs = 0
-    if not args.hot_path_only:
+    fallback_docs = 0 if args.hot_path_only else int(N.lib.tm_batch_host_fallback_docs(batch))
+    if args.full and not args.hot_path_only:
         tn = time.perf_counter()
         for _ in range(3):
             N.check(N.lib.tm_batch_normalize(batch, C.c_void_p(stream)))
         torch.cuda.synchronize()
         normalize_ms = (time.perf_counter() - tn) / 3 * 1e3
-        fallback_docs = int(N.lib.tm_batch_host_fallback_docs(batch))
         # the device-normalized bytes must equal the host normalizer's
         nb = int(N.lib.tm_batch_normalized_bytes(batch))
         if rank == 0:
@@ -823,79 +920,79 @@ def main():
             if nb != text.size or not (doffs == offs).all() or not (dtext[:nb] == text).all():
                 raise SystemExit("bench.py: device-normalized text differs from the host normalizer - number is INVALID")
 
-    # ---- per-kernel time, HIP events on the launch stream (after the timed loop, a few extra passes) --------
     ms = (C.c_float * N.TM_NUM_KERNELS)()
-    acc = np.zeros(N.TM_NUM_KERNELS)
-    reps = 3
-    for _ in range(reps):
-        N.check(N.lib.tm_batch_run_timed(batch, C.c_void_p(stream), ms))
-        acc += np.array(list(ms))
-    acc /= reps
     names = [N.lib.tm_kernel_name(k).decode() for k in range(N.TM_NUM_KERNELS)]
-    kernel_ms = {n: round(float(v), 4) for n, v in zip(names, acc)}
-    dom = int(np.argmax(acc))
-    alg_bytes = float(text.size) + 4.0 * float(ntok.value)     # B_alg = N + 4T per pass
-    achieved = alg_bytes / (acc[dom] * 1e-3) / 1e9
-    # HBM traffic of the dominant kernel: PMC counters cannot be read from inside this process, so the figure is the one
-    # tools/pmc_profile.py measured under rocprofv3 for the same configuration and size (FETCH_SIZE x2 + WRITE_SIZE, separate passes,
-    # as /opt/skills/guides/MI355X_MICROARCH.md prescribes) and wrote to profiles/traffic_latest.json; null when that file is for
-    # another configuration.  `traffic_source` says so in the line itself.
-    traffic, traffic_source = None, None
-    valu_per_wave, salu_per_wave, waves_per_launch, insts_source = None, None, None, None
-    l2_reqs = None            # requests of the vector L1s to the L2 per launch of the match kernel (reads + writes)
-    tpath = os.path.join(ROOT, "profiles", "traffic_latest.json")
-    if os.path.exists(tpath):
-        try:
-            tj = json.load(open(tpath))
-            if tj.get("config") == args.config and tj.get("mbytes") == args.mbytes:
-                traffic = tj.get("hbm_bytes_per_launch")
-                traffic_source = "static: profiles/traffic_latest.json (%s), not measured in this run" % tj.get("measured", "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE")
-                if tj.get("valu_per_wave"):
-                    valu_per_wave, salu_per_wave, waves_per_launch = tj["valu_per_wave"], tj.get("salu_per_wave"), tj.get("waves_per_launch")
-                    insts_source = "static: profiles/traffic_latest.json, not measured in this run"
-                l2_reqs = tj.get("l2_requests_per_launch")
-        except Exception:
-            traffic = None
     under_profiler = any(k.startswith("ROCPROF") for k in os.environ) or "rocprof" in os.environ.get("LD_PRELOAD", "")     # (no profiler inside a profiler)
-    if args.measure_traffic and rank == 0 and world == 1 and not args.hot_path_only and not under_profiler:
-        # separate --pmc passes as /opt/skills/guides/MI355X_MICROARCH.md prescribes, the kernels driven without torch (tools/k1_time.py);
-        # FETCH_SIZE / WRITE_SIZE are in KB, gfx950 tallies 128-byte fetches at 64 bytes (x2)
-        import subprocess
-        try:
-            r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "pmc_profile.py"), "--fast", "--mbytes", str(args.mbytes), "--groups", "0,3,4,5",
-                                "--kernel", "k_match_branch", "--out", os.path.join("/tmp", "tm_bench_traffic")] + (["--extra=--config " + args.config] if args.config else []),
-                               stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900, start_new_session=True)
-            k = list(json.loads(r.stdout.decode()).values())[0]
-            if "FETCH_SIZE" in k and "WRITE_SIZE" in k:
-                traffic = int(k["FETCH_SIZE"] * 1024 * 2 + k["WRITE_SIZE"] * 1024)
-                traffic_source = "measured in this run: rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes; FETCH_SIZE x 2 on gfx950) over the same kernel, configuration and size"
-            if k.get("SQ_WAVES"):
-                valu_per_wave, salu_per_wave, waves_per_launch = k["SQ_INSTS_VALU"] / k["SQ_WAVES"], k["SQ_INSTS_SALU"] / k["SQ_WAVES"], k["SQ_WAVES"]
-                insts_source = "measured in this run: rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVES over the same kernel, configuration and size"
-            if k.get("TCP_TCC_READ_REQ_sum"):
-                l2_reqs = k["TCP_TCC_READ_REQ_sum"] + k.get("TCP_TCC_WRITE_REQ_sum", 0.0)
-        except Exception as ex:     # noqa: BLE001
-            log("counter passes failed (%s): the static figures stay" % ex)
-    roofline = {"bound": "hbm", "kernel": names[dom], "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": round(achieved / HBM_PEAK_GBS, 6), "traffic": traffic, "traffic_source": traffic_source, "traffic_note": TRAFFIC_NOTE,
-                "algorithmic_bytes_per_launch": alg_bytes, "kernel_ms": kernel_ms}
-    # the same kernel against the port it actually occupies: vector instructions issued per second (one wavefront = one 256-byte segment)
-    roofline_valu = None
-    if valu_per_wave:
-        gi = valu_per_wave * waves_per_launch / (acc[dom] * 1e-3) / 1e9
-        roofline_valu = {"bound": "valu_issue", "kernel": names[dom], "achieved": round(gi, 2), "peak": round(VALU_PEAK_GINSTS, 1), "unit": "G wave64 instructions/s",
-                         "frac": round(gi / VALU_PEAK_GINSTS, 4), "vector_instructions_per_segment": round(valu_per_wave, 1),
-                         "scalar_instructions_per_segment": None if salu_per_wave is None else round(salu_per_wave, 1),
-                         "vector_instructions_per_input_byte": round(valu_per_wave * waves_per_launch / float(text.size), 3), "source": insts_source}
+    roofline = roofline_valu = roofline_l2 = None
+    # ---- per-kernel time, HIP events on the launch stream (after the timed loop, a few extra passes) --------
+    if args.full:
+        acc = np.zeros(N.TM_NUM_KERNELS)
+        reps = 3
+        for _ in range(reps):
+            N.check(N.lib.tm_batch_run_timed(batch, C.c_void_p(stream), ms))
+            acc += np.array(list(ms))
+        acc /= reps
+        kernel_ms = {n: round(float(v), 4) for n, v in zip(names, acc)}
+        dom = int(np.argmax(acc))
+        alg_bytes = float(text.size) + 4.0 * float(ntok.value)     # B_alg = N + 4T per pass
+        achieved = alg_bytes / (acc[dom] * 1e-3) / 1e9
+        # HBM traffic of the dominant kernel: PMC counters cannot be read from inside this process, so the figure is the one
+        # tools/pmc_profile.py measured under rocprofv3 for the same configuration and size (FETCH_SIZE x2 + WRITE_SIZE, separate passes,
+        # as the MI355X microarchitecture guide prescribes) and wrote to profiles/traffic_latest.json; null when that file is for
+        # another configuration.  `traffic_source` says so in the line itself.
+        traffic, traffic_source = None, None
+        valu_per_wave, salu_per_wave, waves_per_launch, insts_source = None, None, None, None
+        l2_reqs = None            # requests of the vector L1s to the L2 per launch of the match kernel (reads + writes)
+        tpath = os.path.join(ROOT, "profiles", "traffic_latest.json")
+        if os.path.exists(tpath):
+            try:
+                tj = json.load(open(tpath))
+                if tj.get("config") == args.config and tj.get("mbytes") == args.mbytes:
+                    traffic = tj.get("hbm_bytes_per_launch")
+                    traffic_source = "static: profiles/traffic_latest.json (%s), not measured in this run" % tj.get("measured", "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE")
+                    if tj.get("valu_per_wave"):
+                        valu_per_wave, salu_per_wave, waves_per_launch = tj["valu_per_wave"], tj.get("salu_per_wave"), tj.get("waves_per_launch")
+                        insts_source = "static: profiles/traffic_latest.json, not measured in this run"
+                    l2_reqs = tj.get("l2_requests_per_launch")
+            except Exception:
+                traffic = None
+        if args.measure_traffic and rank == 0 and world == 1 and not args.hot_path_only and not under_profiler:
+            # separate --pmc passes as the MI355X microarchitecture guide prescribes, the kernels driven without torch (tools/k1_time.py);
+            # FETCH_SIZE / WRITE_SIZE are in KB, gfx950 tallies 128-byte fetches at 64 bytes (x2)
+            import subprocess
+            try:
+                r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "pmc_profile.py"), "--fast", "--mbytes", str(args.mbytes), "--groups", "0,3,4,5",
+                                    "--kernel", "k_match_branch", "--out", os.path.join("/tmp", "tm_bench_traffic")] + (["--extra=--config " + args.config] if args.config else []),
+                                   stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900, start_new_session=True)
+                k = list(json.loads(r.stdout.decode()).values())[0]
+                if "FETCH_SIZE" in k and "WRITE_SIZE" in k:
+                    traffic = int(k["FETCH_SIZE"] * 1024 * 2 + k["WRITE_SIZE"] * 1024)
+                    traffic_source = "measured in this run: rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes; FETCH_SIZE x 2 on gfx950) over the same kernel, configuration and size"
+                if k.get("SQ_WAVES"):
+                    valu_per_wave, salu_per_wave, waves_per_launch = k["SQ_INSTS_VALU"] / k["SQ_WAVES"], k["SQ_INSTS_SALU"] / k["SQ_WAVES"], k["SQ_WAVES"]
+                    insts_source = "measured in this run: rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVES over the same kernel, configuration and size"
+                if k.get("TCP_TCC_READ_REQ_sum"):
+                    l2_reqs = k["TCP_TCC_READ_REQ_sum"] + k.get("TCP_TCC_WRITE_REQ_sum", 0.0)
+            except Exception as ex:     # noqa: BLE001
+                log("counter passes failed (%s): the static figures stay" % ex)
+        roofline = {"bound": "hbm", "kernel": names[dom], "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": round(achieved / HBM_PEAK_GBS, 6), "traffic": traffic, "traffic_source": traffic_source, "traffic_note": TRAFFIC_NOTE,
+                    "algorithmic_bytes_per_launch": alg_bytes, "kernel_ms": kernel_ms}
+        # the same kernel against the port it actually occupies: vector instructions issued per second (one wavefront = one 256-byte segment)
+        if valu_per_wave:
+            gi = valu_per_wave * waves_per_launch / (acc[dom] * 1e-3) / 1e9
+            roofline_valu = {"bound": "valu_issue", "kernel": names[dom], "achieved": round(gi, 2), "peak": round(VALU_PEAK_GINSTS, 1), "unit": "G wave64 instructions/s",
+                             "frac": round(gi / VALU_PEAK_GINSTS, 4), "vector_instructions_per_segment": round(valu_per_wave, 1),
+                             "scalar_instructions_per_segment": None if salu_per_wave is None else round(salu_per_wave, 1),
+                             "vector_instructions_per_input_byte": round(valu_per_wave * waves_per_launch / float(text.size), 3), "source": insts_source}
 
-    # ... and against what its divergent gathers load most: the request rate of the L2 (16 channels per XCD x 8 XCDs, one request per channel
-    # and clock of the 2.1 GHz the guide's 34.5 TB/s of L2 bandwidth are 128-byte lines at)
-    roofline_l2 = None
-    if l2_reqs:
-        gr = l2_reqs / (acc[dom] * 1e-3) / 1e9
-        roofline_l2 = {"bound": "l2_requests", "kernel": names[dom], "achieved": round(gr, 1), "peak": L2_PEAK_GREQS, "unit": "G requests/s",
-                       "frac": round(gr / L2_PEAK_GREQS, 4), "requests_per_segment": round(l2_reqs / waves_per_launch, 1) if waves_per_launch else None,
-                       "source": "rocprofv3 --pmc TCP_TCC_READ_REQ_sum TCP_TCC_WRITE_REQ_sum over the same kernel, configuration and size"}
+        # ... and against what its divergent gathers load most: the request rate of the L2 (16 channels per XCD x 8 XCDs, one request per channel
+        # and clock of the 2.1 GHz the guide's 34.5 TB/s of L2 bandwidth are 128-byte lines at)
+        if l2_reqs:
+            gr = l2_reqs / (acc[dom] * 1e-3) / 1e9
+            roofline_l2 = {"bound": "l2_requests", "kernel": names[dom], "achieved": round(gr, 1), "peak": L2_PEAK_GREQS, "unit": "G requests/s",
+                           "frac": round(gr / L2_PEAK_GREQS, 4), "requests_per_segment": round(l2_reqs / waves_per_launch, 1) if waves_per_launch else None,
+                           "source": "rocprofv3 --pmc TCP_TCC_READ_REQ_sum TCP_TCC_WRITE_REQ_sum over the same kernel, configuration and size"}
 
     # ---- verification of a sample against the oracle (rank 0; outside the timed region) -------------------
     verified = None

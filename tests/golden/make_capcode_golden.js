@@ -1,6 +1,9 @@
 // make_capcode_golden.js — pins capcode level 2 to the reference's OWN statement of it.
 //
-//   node tests/golden/make_capcode_golden.js > /tmp/capcode_js.json && gzip -9n -c /tmp/capcode_js.json > tests/golden/capcode_js.json.gz
+//   node tests/golden/make_capcode_golden.js > capcode_js.json
+//
+// and the JSON split in two, tests/golden/capcode_js.0.json.gz and capcode_js.1.json.gz (gzip -9n): each holds every key but
+// `cases`, half of `cases` in order and "part": k, "parts": 2 - no committed file may be larger than 1 MiB.
 //
 // Evaluates /root/reference/javascript/tokenmonster.js from its "// ---- capcode.js ----" marker on, WHERE IT LIES
 // (nothing is copied into this repository), and runs the reference's capcode_encode (:900-1005) and CapcodeDecoder

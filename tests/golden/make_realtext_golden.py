@@ -1,20 +1,17 @@
 #!/usr/bin/env python3
-"""Generates tests/golden/realtext.json.gz (committed) and tests/golden/_realtext_docs.bin.gz (git-ignored; travels to the GPU box with the
-snapshot like oracle/_ref): REAL prose and code — every *.md / *.go / *.js / *.cpp / *.hpp / *.py / *.yaml under /root/reference (about
-0.8 MB: the reference's READMEs, its Go / JS / C++ / Python sources), one document per file and one per 4 KiB slice of it (cut on UTF-8
-character boundaries) — tokenized by the REFERENCE's own C++ runtime (oracle/_ref/libtmref.so) with two vocabularies built from the only
-real token list in the tree, yaml_guide/gpt2.json:
+"""Generates tests/golden/realtext.json.gz and tests/golden/realtext_docs.bin.gz (both committed): REAL prose and code - this project's
+own READMEs, design notes and Python / Go / C / HIP sources as they stood when the fixture was made (DOC_FILES), one document per file
+and one per 4 KiB slice of it (cut on UTF-8 character boundaries) - tokenized by the REFERENCE's own C++ runtime (oracle/_ref/libtmref.so)
+with two vocabularies built from the only real token list in the reference tree, yaml_guide/gpt2.json:
   (a) "gpt2"        capcode 0, charset UTF-8, no normalization: the image of tests/golden/gpt2_vocab.json.gz
   (b) "gpt2-capcode2-nfd"  the same token list as the reference's normalizer (capcode 2 + NFD) writes each token - lower case, capital
                     markers - built with capcode 2, norm_flag 1 (the builder adds the "D " duplicates itself)
-The committed fixture holds, per document, the sha1 of its raw bytes and the ids / missing / count the reference returns for it under
-both vocabularies, plus image (b); the documents' TEXT is the reference's own files and stays out of the repository's history: it is
-written beside the fixture into a git-ignored file (the -m gpu test skips its text-dependent half where that file is missing and the
-reference tree is not there to make it again).
+The fixture holds, per document, the sha1 of its raw bytes and the ids / missing / count the reference returns for it under both
+vocabularies, plus image (b); realtext_docs.bin.gz holds the documents' text, so that the tests need nothing outside the repository.
 
     python tests/golden/make_realtext_golden.py
 
-Runs in the build container only (needs /root/reference and oracle/_ref)."""
+Runs where the reference tree and oracle/_ref are present (REF below)."""
 import base64
 import gzip
 import hashlib
@@ -32,21 +29,16 @@ from oracle_bind import Reference  # noqa: E402
 from tokenmonster_amd import synth  # noqa: E402
 
 REF = "/root/reference"
-EXTS = (".md", ".go", ".js", ".cpp", ".hpp", ".py", ".yaml")
+DOC_FILES = ["README.md", "INTEGRATION.md", "DESIGN.md", "tokenmonster_amd/vocab.py", "tokenmonster_amd/dist.py", "go/tokenmonster_hip.go",
+             "oracle/tm_oracle.c", "examples/server_jobs.c"]
+DOCS = os.path.join(HERE, "realtext_docs.bin.gz")
 SLICE = 4096
 
 
 def collect():
-    files = []
-    for d, _, names in os.walk(REF):
-        for n in names:
-            if n.endswith(EXTS):
-                files.append(os.path.join(d, n))
-    files.sort()
     docs, names = [], []
-    for p in files:
-        b = open(p, "rb").read()
-        rel = os.path.relpath(p, REF)
+    for rel in DOC_FILES:
+        b = open(os.path.join(ROOT, rel), "rb").read()
         docs.append(b); names.append(rel)
         if len(b) > SLICE:
             at, k = 0, 0
@@ -101,7 +93,7 @@ def main():
         if 0 < len(t) <= 40:
             gpt2_tokens.append(t)
     img_b, n_b = capcode_vocab(gpt2_tokens)
-    out = {"note": "real text: %d documents (%d files of /root/reference + their 4 KiB slices), %d bytes; ids / missing / count from the reference C++ "
+    out = {"note": "real text: %d documents (%d files of this project + their 4 KiB slices), %d bytes; ids / missing / count from the reference C++ "
                    "runtime on the RAW bytes (Vocab::tokenize = normalize + walk)" % (len(docs), sum(1 for n in names if "[" not in n), sum(map(len, docs))),
            "generator": "tests/golden/make_realtext_golden.py via oracle/_ref/libtmref.so",
            "names": names, "sha1": [hashlib.sha1(d).hexdigest() for d in docs], "bytes": [len(d) for d in docs],
@@ -120,9 +112,9 @@ def main():
         print("%-20s %d documents, %d tokens, %d missing, %d normalized bytes" % (key, len(docs), sum(len(base64.b64decode(x)) // 2 for x in ids), sum(missing), sum(nbytes)))
     with gzip.GzipFile(os.path.join(HERE, "realtext.json.gz"), "wb", compresslevel=9, mtime=0) as f:
         f.write(json.dumps(out).encode())
-    write_docs(docs, os.path.join(HERE, "_realtext_docs.bin.gz"))
-    print("vocabulary (b): %d tokens, image %d bytes; fixture %d bytes, text %d bytes (git-ignored)" % (
-        n_b, len(img_b), os.path.getsize(os.path.join(HERE, "realtext.json.gz")), os.path.getsize(os.path.join(HERE, "_realtext_docs.bin.gz"))))
+    write_docs(docs, DOCS)
+    print("vocabulary (b): %d tokens, image %d bytes; fixture %d bytes, text %d bytes" % (
+        n_b, len(img_b), os.path.getsize(os.path.join(HERE, "realtext.json.gz")), os.path.getsize(DOCS)))
 
 
 if __name__ == "__main__":

@@ -1,6 +1,6 @@
 """Capcode level 2 and the NFD pre-step, pinned to the reference's OWN statement of capcode.
 
-tests/golden/capcode_js.json.gz was produced by tests/golden/make_capcode_golden.js, which evaluates
+tests/golden/capcode_js.{0,1}.json.gz were produced by tests/golden/make_capcode_golden.js, which evaluates
 /root/reference/javascript/tokenmonster.js:872-1065 (capcode_encode, CapcodeDecoder) where it lies, under node 12, on
 5 261 strings (caps / digits / apostrophes / U+2019 / combining marks / accents / CJK / Cyrillic / Greek / emoji, plus every
 hand-written string of the device-normalizer test).  Replayed here against
@@ -19,11 +19,13 @@ import pytest
 from oracle_bind import Reference, have_ref
 from tokenmonster_amd import synth
 
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "capcode_js.json.gz")
+GOLDEN = [os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "capcode_js.%d.json.gz" % k) for k in range(2)]
 
 
 def cases():
-    g = json.load(gzip.open(GOLDEN))
+    parts = [json.load(gzip.open(p)) for p in GOLDEN]
+    assert [p["part"] for p in parts] == list(range(parts[0]["parts"]))
+    g = dict(parts[0], cases=[c for p in parts for c in p["cases"]])
     assert g["n"] >= 5000 and len(g["cases"]) == g["n"]
     return [tuple(base64.b64decode(c[k]) for k in ("in", "nfd", "enc", "dec")) for c in g["cases"]]
 

@@ -15,8 +15,8 @@ from tokenmonster_amd import synth
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHIM = os.path.join(ROOT, "examples", "cpp_port_shim")
-UNIT = os.path.join(SHIM, "_build", "unit")
-BENCH = os.path.join(SHIM, "_build", "bench")
+UNIT = os.path.join(ROOT, "oracle", "_ref", "cpp_port_shim", "unit")
+BENCH = os.path.join(ROOT, "oracle", "_ref", "cpp_port_shim", "bench")
 REF_BENCH = os.path.join(ROOT, "oracle", "_ref", "bench")
 
 
@@ -24,7 +24,7 @@ def _build():
     r = subprocess.run(["make", "-C", SHIM], stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
     assert r.returncode == 0, r.stdout.decode(errors="replace")[-3000:]
     if not os.path.exists(UNIT):
-        pytest.skip("examples/cpp_port_shim/_build is not there (built where /root/reference is present)")
+        pytest.skip("oracle/_ref/cpp_port_shim is not there (built where the reference sources are present)")
 
 
 def test_the_ports_unit_test_passes_on_the_hip_library(tmp_path):

@@ -1,7 +1,7 @@
 #!/bin/bash
 # development aid: K1 time (256 MiB, hot path, ids verified against the oracle) + its dynamic instruction / cache counters per wavefront
 cd "$(dirname "$0")/.."
-python bench.py --mbytes 256 --steps 8 --warmup 2 --hot-path-only --no-cpu-baseline 2>&1 | python -c "
+python bench.py --full --mbytes 256 --steps 8 --warmup 2 --hot-path-only --no-cpu-baseline 2>&1 | python -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):

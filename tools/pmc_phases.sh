@@ -4,7 +4,7 @@
 cd "$(dirname "$0")/.."
 for d in "$@"; do
   TM_DBG=$d python tools/pmc_profile.py --kernel k_match_branch --groups 0,3 --out gpurun_out/pmc_d$d > gpurun_out/pmc_d$d.json 2> gpurun_out/pmc_d$d.err
-  t=$(TM_DBG=$d python bench.py --mbytes 256 --steps 5 --warmup 2 --hot-path-only --no-cpu-baseline --verify 0 2>/dev/null | python -c "import json,sys; print(json.loads(sys.stdin.read())['roofline']['kernel_ms']['match_branch'])")
+  t=$(TM_DBG=$d python bench.py --full --mbytes 256 --steps 5 --warmup 2 --hot-path-only --no-cpu-baseline --verify 0 2>/dev/null | python -c "import json,sys; print(json.loads(sys.stdin.read())['roofline']['kernel_ms']['match_branch'])")
   python - "$d" "$t" <<'PY'
 import json, sys
 d, t = sys.argv[1], sys.argv[2]

@@ -46,7 +46,7 @@ def main():
             work = [sys.executable, os.path.join(ROOT, "tools", "k1_time.py"), "--one", os.path.abspath(args.lib) if args.lib else "", "--mbytes", str(args.mbytes),
                     "--reps", "2"] + (["--e2e"] if args.e2e else []) + args.extra.split()
         else:
-            work = [sys.executable, os.path.join(ROOT, "bench.py"), "--mbytes", str(args.mbytes), "--steps", "2", "--warmup", "1",
+            work = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--mbytes", str(args.mbytes), "--steps", "2", "--warmup", "1",
                     "--verify", "0", "--no-cpu-baseline", "--no-host-to-host"] + ([] if args.e2e else ["--hot-path-only"]) + args.extra.split()
         cmd = ["rocprofv3", "--pmc"] + grp + ["--kernel-trace", "-d", d, "-o", "pmc", "--output-format", "csv", "--"] + work
         r = subprocess.run(cmd, cwd="/tmp", env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)

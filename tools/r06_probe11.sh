@@ -8,7 +8,7 @@ import subprocess, sys, os
 # hook 15: the word-staging walk (k_score_tiles) on the same rows, for the time of record beside it
 env = dict(os.environ, TM_K1_HOOKS="32768")
 PY
-timeout 900 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --verify 0 > $OUT/bench_default.json 2> $OUT/bench_default.err
+timeout 900 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --verify 0 > $OUT/bench_default.json 2> $OUT/bench_default.err
 python - <<'PY'
 import json
 d = json.load(open("gpurun_out/r06_probe11/bench_default.json"))

@@ -4,7 +4,7 @@ cd "$(dirname "$0")/.."
 OUT=gpurun_out/r06_probe21; mkdir -p $OUT
 timeout 600 python -m pytest tests/test_gpu_host_api.py -x -q -p no:cacheprovider -k "laid_out" 2>&1 | tail -2
 for cfg in englishcode-32000-consistent englishcode-100256-clean; do
-  timeout 900 python bench.py --steps 8 --warmup 3 --config $cfg --no-cpu-baseline --no-host-to-host --verify 0 > $OUT/bench_$cfg.json 2> $OUT/bench_$cfg.err
+  timeout 900 python bench.py --full --steps 8 --warmup 3 --config $cfg --no-cpu-baseline --no-host-to-host --verify 0 > $OUT/bench_$cfg.json 2> $OUT/bench_$cfg.err
   python - $OUT/bench_$cfg.json <<'PY'
 import json,sys
 d=json.load(open(sys.argv[1])); r=d["roofline"]

@@ -9,4 +9,4 @@ TM_SWEEP_FLAG=186 python $ROOT/tools/h2h_sweep.py 4:32 >> $OUT/h2h.txt 2>&1
 TM_SWEEP_FLAG=255 python $ROOT/tools/h2h_sweep.py 4:32 >> $OUT/h2h.txt 2>&1
 TM_SWEEP_FLAG=186 TM_RING=0 python $ROOT/tools/h2h_sweep.py 4:32 >> $OUT/h2h.txt 2>&1
 cat $OUT/h2h.txt
-python bench.py > $OUT/bench.json 2> $OUT/bench.log; tail -c 1500 $OUT/bench.json
+python bench.py --full > $OUT/bench.json 2> $OUT/bench.log; tail -c 1500 $OUT/bench.json

@@ -15,10 +15,10 @@ NS="1"; [ "$NDEV" -gt 1 ] && NS="1 $NDEV"
 COMMON="--steps 5 --warmup 2 --mbytes $MB --no-cpu-baseline --no-host-to-host --no-measure-traffic"
 for W in tokenize score; do
   for N in $NS; do
-    timeout 900 python bench.py --gpus $N --workload $W $COMMON > $OUT/ranks_${W}_$N.json 2> $OUT/ranks_${W}_$N.err || echo "ranks $W N=$N failed (see $OUT/ranks_${W}_$N.err)"
+    timeout 900 python bench.py --full --gpus $N --workload $W $COMMON > $OUT/ranks_${W}_$N.json 2> $OUT/ranks_${W}_$N.err || echo "ranks $W N=$N failed (see $OUT/ranks_${W}_$N.err)"
   done
   for N in $NSV; do
-    timeout 900 python bench.py --in-process --gpus $N --workload $W $COMMON > $OUT/inproc_${W}_$N.json 2> $OUT/inproc_${W}_$N.err || echo "in-process $W N=$N failed (see $OUT/inproc_${W}_$N.err)"
+    timeout 900 python bench.py --full --in-process --gpus $N --workload $W $COMMON > $OUT/inproc_${W}_$N.json 2> $OUT/inproc_${W}_$N.err || echo "in-process $W N=$N failed (see $OUT/inproc_${W}_$N.err)"
   done
 done
 python - "$OUT" <<'PY'

@@ -3,7 +3,7 @@
 cd "$(dirname "$0")/.."
 ROOT=$PWD
 OUT=$ROOT/gpurun_out/${1:-stats}; mkdir -p $OUT
-(cd /tmp && export TMPDIR=/tmp && timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/stats_e2e -o s --output-format csv -- python $ROOT/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-host-to-host --verify 0 > $OUT/bench_under_rocprof.json 2>/dev/null)
+(cd /tmp && export TMPDIR=/tmp && timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/stats_e2e -o s --output-format csv -- python $ROOT/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-host-to-host --verify 0 > $OUT/bench_under_rocprof.json 2>/dev/null)
 f=$(find $OUT/stats_e2e -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $OUT/kernel_stats_e2e.csv && python3 - "$f" <<'PY'
 import csv, sys
 for i, r in enumerate(csv.DictReader(open(sys.argv[1]))):
