@@ -243,7 +243,7 @@ struct WaveLds {
   // wavefronts per CU fill the 160 KB; the loops over NPOS_PAD positions guard p < NPOS)
   alignas(16) uint32_t X[NPOS];        // node value of D's token (node id = record ordinal)
   alignas(16) uint8_t text[TEXT_LEN];  // (between X and D: D[p] lies 6 * 256 bytes behind X[p], and step A1 stores both with one ds_write2st64_b32)
-  uint32_t D[NPOS];        // longest match at p                      (second-token descriptor); Db must follow (step C overlays both)
+  uint32_t D[NPOS];        // longest match at p                      (second-token descriptor); Db must follow (step C addresses Db[40..] from D)
   uint32_t Db[NPOS];       // longest match of ' '+text[p:], if usable (forward-delete descriptor), 0 = none
   uint32_t Xb[SEG];        // node value of Db's token
   uint16_t xch[64];        // dense task list of the forward-delete walks (step A3), one batch at a time
@@ -314,8 +314,8 @@ __device__ __forceinline__ uint32_t transition(const Tables& T, const WaveLds& w
 // Halo sharing (measured -1.7 % alone, -4.9 % together with the non-temporal streams, profiles/r03_k1_variants_ab.txt): the 40 halo positions of a
 // segment — 13.5 % of the positions steps A1 - A3 work on — are the first 40 positions of the NEXT segment; when the wavefront of that
 // segment sits in the same workgroup and the same document, this wavefront walks 256 positions instead of 296 (runs of 4 instead of 5
-// per lane) and copies the neighbour's descriptors after ONE workgroup barrier.  Step C's pointer-doubling table then overlays
-// D[40..] / Db[40..] instead of D[0..], so that a wavefront never overwrites what its left neighbour may still be copying.
+// per lane) and copies the neighbour's descriptors after ONE workgroup barrier.  Step C's table of contracted (p,1) hops (J1) therefore
+// overlays Db[40..], so that a wavefront never overwrites what its left neighbour may still be copying (D[0..40), Db[0..40)).
 // Host model (round 2): 70 % of the wavefronts share, 26.5 -> 24.3 rounds per wavefront in step A1.
 // For a batch whose text still lies in the device normalizer's slabs (tm_norm.hip): the piece a segment begins in, the offset of its first
 // byte in that piece's slab, and how many bytes the piece holds from there.  piece_off = the pieces' places in the packed text.
@@ -355,7 +355,7 @@ __global__ void k_seg_fill(const uint64_t* __restrict__ doc_seg_start, uint32_t 
   seg_src[g] = make_uint4((uint32_t)lo, (uint32_t)(begin - piece_off[lo]), (uint32_t)(piece_off[lo + 1] - begin), 0u);
 }
 
-constexpr int J_SKIP = NPOS - SEG, J_PLANE = NPOS;     // step C: state (p, fd) lives at word J_SKIP + fd * J_PLANE + p of {D, Db}
+constexpr int J_SKIP = NPOS - SEG, J_PLANE = NPOS;     // step C: the contracted hop of state (p, 1) lives at word J_SKIP + J_PLANE + p of {D, Db}
 __global__ __launch_bounds__(WAVES * 64, 8) void k_match_branch(Tables T, const uint8_t* __restrict__ text,
                                                                 const uint64_t* __restrict__ doc_begin,
                                                                 const uint64_t* __restrict__ doc_end,
@@ -878,114 +878,124 @@ __global__ __launch_bounds__(WAVES * 64, 8) void k_match_branch(Tables T, const 
   }
   PH(6)
   __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_s_waitcnt(0);
+  __builtin_amdgcn_s_waitcnt(0xC07F);                    // lgkmcnt(0) only: step C needs this wavefront's LDS stores, not its stores of R0 / R1 / side
 
-  // ---- step C: exit map of the segment by pointer doubling over all (p, fd) states -------------------
-  // J[s] summarises the path from state s to where it currently points: {target, #tokens emitted on the way}.  Composing J[s] with
-  // J[target] doubles the path; after <= log2(chain length) rounds every state points at a segment exit.  Only the 80 possible entry
-  // states (offset < 40, fd) are written out, but their chains run through arbitrary states, so all 2 x 256 states take part.
-  // In-place updates are safe: an entry is read and written as one 4-byte LDS access and always describes a valid prefix of its
-  // state's chain.  (What a chain emits besides its count — forward-deletes, missing characters — is counted by K4, which walks
-  // the one chain that is real.)
   if (TM_DBG_ON(dbg & 16)) { for (int e = lane; e < ENT; e += 64) exit16[g * ENT + e] = 0u; return; }   // (timing experiments only)
+  // ---- step C: exit map of the segment by pointer doubling over the 256 plain states, in registers ----------
+  // An entry {#tokens emitted on the way, where the path ends} summarises the path from a state to where it currently points; composing
+  // an entry with that of its target doubles the path.  The (p,1) states are few (a forward-delete match) and are contracted out first:
+  // each gets the hop that leads through its (.,1) successors to a plain state or out of the segment, and a plain state whose first hop
+  // leads into (q,1) takes that contracted hop with it.  What is left are the 256 plain states, state (it * 64 + lane, 0) in ja[it]:
+  // a pointer into its own block of 64 positions is a lane index, followed with ds_bpermute, no LDS store.  Every hop consumes at least
+  // one byte (only a (p,1) state can stand still, and that is a dead end below), so targets lie strictly ahead: a block first doubles
+  // within itself (<= 6 rounds for <= 63 hops), then blocks 2, 1, 0 resolve against the (finished) blocks behind them.
+  // (Rounds 2-6 doubled over all 2 x 256 states through a table in LDS, 4 reads + 4 writes and a full wait per round: K1 3.3 % slower.)
   {
-    uint32_t* J = reinterpret_cast<uint32_t*>(w.D) + J_SKIP;       // overlays D, Db (dead after step B): 2 x SEG words, state (p, fd) at J[fd * J_PLANE + p]
-    static_assert(J_SKIP + J_PLANE + SEG <= 2 * NPOS, "J overlay does not fit");
     const bool more_text = remv > (uint64_t)seglen;       // text follows the segment: the chain leaves it into an entry state
-    // J entry: #tokens [0..JF-1] | field [JF..30] | left-the-segment [31]; the field is the LDS byte address of the entry it points
-    // at, or — once the chain has left the segment — the entry state of the next segment (JNONE: the state is unreachable).
-    // Composing two entries is (x & JCNT) + x', and the address to read next is x >> JF.
-    constexpr uint32_t JF = 12, JCNT = (1u << JF) - 1u, JNONE = (1u << (31 - JF)) - 1u;      // count: 12 bits (<= 2 ids per byte of a segment), field: 19 bits
-    typedef TM_LDS_SPACE uint32_t lds_u32;
-    auto ld_j = [](uint32_t a) -> uint32_t { return *TM_LDS_PTR(lds_u32, a); };
-    const uint32_t jaddr = TM_LDS_ADDR(w.D) + 4u * (uint32_t)J_SKIP;
-    static_assert(sizeof(s_wave) + 2048 < (1u << 18), "LDS addresses must fit the field"); static_assert(2 * SEG + 2 < 4096, "id count of a segment must fit 12 bits");
+    // entry: #tokens [0..JF-1] | field [JF..30] | left-the-segment [31]; the field is the target state (p + SEG * fd) while the path is
+    // inside the segment, the entry state of the next segment once it has left it (JNONE: the state is unreachable)
+    constexpr uint32_t JF = 12, JCNT = (1u << JF) - 1u, JNONE = (1u << (31 - JF)) - 1u, JOUT = 0x80000000u;
+    static_assert(2 * SEG + 2 < 4096, "id count of a segment must fit 12 bits");
+    constexpr int N0 = SEG / 64;
+    // (in select form: as early returns, the eight calls were branches and exec-mask juggling around every state)
     auto first_hop = [&](uint32_t r, int p, uint32_t fd) -> uint32_t {
       // at/after the end of the segment: nothing is emitted here.  At the end of the text that is the terminal state; in a byte
       // range that is followed by more text, a token of the range before may cover this whole (short, last) segment: pass through
-      if (p >= seglen) return 0x80000000u | ((more_text ? (uint32_t)((p - seglen) * 2) + fd : 0u) << JF);
-      if (r == R_INVALID) return 0x80000000u | (JNONE << JF);
-      const int pn = p + (int)((r >> 24) & 63u);
-      const uint32_t fdn = (r >> 30) & 1u;
-      // a state that is its own successor (no byte consumed, same forward-delete flag: a UTF-16 vocabulary with one-byte keys beside the
-      // delete token can make one) would double its token count in every round below until the count runs over into the address field:
-      // a dead end here; K4, which walks the one chain that is real, reports the text (TM_E_INPUT)
-      // (only a forward-delete state can stand still: a plain one consumes at least the byte it stands on)
-      if (fd == 1u && pn == p && fdn == 1u) return 0x80000000u | (JNONE << JF);
+      auto out = [&](uint32_t q, uint32_t f) { return JOUT | ((more_text ? (q - (uint32_t)seglen) * 2u + f : 0u) << JF); };
+      const uint32_t pn = (uint32_t)p + ((r >> 24) & 63u), fdn = (r >> 30) & 1u;
       const uint32_t nt = ((r & ID_NONE) != ID_NONE ? 1u : 0u) + fdn;          // ids this step emits: the token (unless it is "none") + the delete token
-      const uint32_t x = pn >= seglen ? 0x80000000u | ((more_text ? (uint32_t)((pn - seglen) * 2) + fdn : 0u) << JF)
-                                      : (jaddr + 4u * (fdn * (uint32_t)J_PLANE + (uint32_t)pn)) << JF;
-      return x | nt;
+      const uint32_t xo = out(pn, fdn), xi = (fdn * (uint32_t)SEG + pn) << JF, mo = 0u - (uint32_t)(pn >= (uint32_t)seglen);
+      const uint32_t x = ((xo & mo) | (xi & ~mo)) | nt;
+      // a state that is its own successor (no byte consumed, same forward-delete flag: a UTF-16 vocabulary with one-byte keys beside the
+      // delete token can make one) would never leave the segment: a dead end here; K4, which walks the one chain that is real, reports
+      // the text (TM_E_INPUT)
+      const bool dead = r == R_INVALID || (fd == 1u && pn == (uint32_t)p && fdn == 1u);
+      return p >= seglen ? out((uint32_t)p, fd) : dead ? JOUT | (JNONE << JF) : x;
     };
-    // every lane keeps its own 2*SEG/64 states in registers and only touches LDS for states that still point inside
-    // the segment (most (p,1) states are unreachable and finished from the start)
-    constexpr int NS = 2 * SEG / 64, N0 = SEG / 64;
-    uint32_t ja[NS];
+    auto pend = [](uint32_t x) { return (int)x >= 0; };
+    auto bperm = [](uint32_t x, uint32_t v) { return (uint32_t)__builtin_amdgcn_ds_bpermute((int)(((x >> JF) & 63u) << 2), (int)v); };     // v at x's target lane
+    // 1. the (p,1) states: first hops to LDS (J1 overlays D, dead after step B), then (.,1) -> (.,1) hops composed away in place (rare: a
+    // delete token behind a delete token; every entry always describes a valid prefix of its state's chain, so reads and writes of a
+    // round may interleave).  Positions strictly increase along such a chain: <= 8 rounds for 256 states.
+    uint32_t* J1 = reinterpret_cast<uint32_t*>(w.D) + J_SKIP + J_PLANE;
+    static_assert(J_SKIP + J_PLANE + SEG <= 2 * NPOS, "J1 overlay does not fit");
+    uint32_t jb[N0], ja[N0];
 #pragma unroll
     for (int it = 0; it < N0; it++) {
       const int p = it * 64 + lane;
+      jb[it] = TM_DBG_ON(dbg & 0x400000) ? JOUT | (JNONE << JF) : first_hop(r1[it], p, 1u);      // (devel bit 22: no forward-delete states in step C)
+      J1[p] = jb[it];
       ja[it] = first_hop(r0[it], p, 0u);
-      J[p] = ja[it];
-      if (TM_DBG_ON(dbg & 0x400000)) ja[N0 + it] = 0x80000000u | (JNONE << JF);      // (devel bit 22: no forward-delete states in step C - what their four slots per lane cost)
-      else { ja[N0 + it] = first_hop(r1[it], p, 1u); J[J_PLANE + p] = ja[N0 + it]; }
     }
     __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_s_waitcnt(0);
-    // One round: every pending state (bit 31 clear: it still points inside the segment) composes itself with the state it points at.  The
-    // LDS reads of a round are issued back to back (one LDS latency per round); the (p,1) states are rarely pending and skipped as a group.
-    // The entry states sit at the start of the segment and have the longest chains, so "nothing pending" is also when they are done.
-    // No branch per state: a finished state reads its own entry and writes back what it holds.  (As `if (pend[k])` blocks - three scalar
-    // instructions around every state, twelve rounds unrolled - this was a third of the kernel's code and 268 of its 1 229 scalar
-    // instructions per segment; in select form it is 111 vector instructions more and the kernel's time is the same, measured:
-    // K1 does not wait for its scalar unit.  Kept for the smaller code.)
-    const uint32_t own = jaddr + 4u * (uint32_t)lane;         // LDS address of the lane's state 0; state k is 256 bytes further, the (p,1) states J_PLANE words
-    auto st_j = [](uint32_t a, uint32_t v) { *TM_LDS_PTR(lds_u32, a) = v; };
-    for (int round = 0; round < 12; round++) {
-      uint32_t all0 = ja[0], all1 = ja[N0];
+    __builtin_amdgcn_s_waitcnt(0xC07F);                  // lgkmcnt(0) only
+    for (int round = 0; round < 8; round++) {
+      bool any1 = false;
 #pragma unroll
-      for (int k = 1; k < N0; k++) { all0 &= ja[k]; all1 &= ja[N0 + k]; }
-      const unsigned long long m0 = __builtin_amdgcn_ballot_w64((int)all0 >= 0), m1 = __builtin_amdgcn_ballot_w64((int)all1 >= 0);
-      if ((m0 | m1) == 0ull) break;
-      uint32_t bn[N0];
+      for (int k = 0; k < N0; k++) any1 |= pend(jb[k]) && (jb[k] >> JF) >= (uint32_t)SEG;
+      if (__builtin_amdgcn_ballot_w64(any1) == 0ull) break;
 #pragma unroll
-      for (int k = 0; k < N0; k++) bn[k] = ld_j((int)ja[k] >= 0 ? ja[k] >> JF : own + 256u * (uint32_t)k);
+      for (int k = 0; k < N0; k++)
+        if (pend(jb[k]) && (jb[k] >> JF) >= (uint32_t)SEG) { jb[k] = (jb[k] & JCNT) + J1[(jb[k] >> JF) - SEG]; J1[k * 64 + lane] = jb[k]; }
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_s_waitcnt(0xC07F);                  // lgkmcnt(0) only
+      PH_INC(13)
+    }
+    // 2. a plain state whose first hop leads into (q,1) takes q's contracted hop: one LDS read
+#pragma unroll
+    for (int k = 0; k < N0; k++)
+      if (pend(ja[k]) && (ja[k] >> JF) >= (uint32_t)SEG) ja[k] = (ja[k] & JCNT) + J1[(ja[k] >> JF) - SEG];
+    // 3. doubling within each block of 64 positions, all four at once, until no state points into its own block (a pending plain entry
+    // is < 2^20: its block is x >> (JF + 6))
+    for (int round = 0; round < 6; round++) {
+      bool anyb = false;
+#pragma unroll
+      for (int k = 0; k < N0; k++) anyb |= pend(ja[k]) && (ja[k] >> (JF + 6)) == (uint32_t)k;
+      if (__builtin_amdgcn_ballot_w64(anyb) == 0ull) break;
 #pragma unroll
       for (int k = 0; k < N0; k++) {
-        ja[k] = (int)ja[k] >= 0 ? (ja[k] & JCNT) + bn[k] : ja[k];              // (a 12-bit count cannot overflow: <= 512 ids per segment)
-        st_j(own + 256u * (uint32_t)k, ja[k]);
+        const uint32_t b = bperm(ja[k], ja[k]);
+        ja[k] = pend(ja[k]) && (ja[k] >> (JF + 6)) == (uint32_t)k ? (ja[k] & JCNT) + b : ja[k];
       }
-      if (m1 != 0ull) {
-#pragma unroll
-        for (int k = 0; k < N0; k++) bn[k] = ld_j((int)ja[N0 + k] >= 0 ? ja[N0 + k] >> JF : own + 4u * (uint32_t)J_PLANE + 256u * (uint32_t)k);
-#pragma unroll
-        for (int k = 0; k < N0; k++) {
-          ja[N0 + k] = (int)ja[N0 + k] >= 0 ? (ja[N0 + k] & JCNT) + bn[k] : ja[N0 + k];
-          st_j(own + 4u * (uint32_t)J_PLANE + 256u * (uint32_t)k, ja[N0 + k]);
-        }
-      }
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_s_waitcnt(0);
       PH_INC(13)
+    }
+    // 4. blocks 2, 1, 0 against the blocks behind them, which are finished by then (6 ds_bpermute)
+#pragma unroll
+    for (int k = N0 - 2; k >= 0; k--) {
+      uint32_t b = 0u;
+#pragma unroll
+      for (int j = k + 1; j < N0; j++) {
+        const uint32_t bj = bperm(ja[k], ja[j]);
+        b = (ja[k] >> (JF + 6)) == (uint32_t)j ? bj : b;
+      }
+      ja[k] = pend(ja[k]) ? (ja[k] & JCNT) + b : ja[k];
+    }
+    // 5. the entry states (o, 1), o < 40, that lead into a plain state: contracted hop + that state's resolved entry
+    uint32_t e1 = jb[0];
+    if (__builtin_amdgcn_ballot_w64(lane < ENT / 2 && pend(e1)) != 0ull) {
+      uint32_t b = 0u;
+#pragma unroll
+      for (int j = 0; j < N0; j++) {
+        const uint32_t bj = bperm(e1, ja[j]);
+        b = (e1 >> (JF + 6)) == (uint32_t)j ? bj : b;
+      }
+      e1 = pend(e1) ? (e1 & JCNT) + b : e1;
     }
     // exit map entry (exit_entry below): next entry state [0..6] | #ids << 7 in 16 bits, 0xFFFF: the entry state cannot occur; a count that
     // does not fit 9 bits (more than 510 ids from one 256-byte segment: one-byte tokens with delete tokens) is written as 511 and the
-    // segment's map goes to the wide array as well (next entry state [0..7] | #ids << 8, 0xFFFFFFFF)
-    bool wide = false;
-    for (int e = lane; e < ENT; e += 64) {
-      const uint32_t a = J[(e & 1) * J_PLANE + (e >> 1)];
-      const uint32_t t = (a >> JF) & JNONE, cnt = a & JCNT;
-      const bool ok = (a >> 31) != 0 && t != JNONE;
-      // (an ordinary store: a map is 160 bytes, not whole lines, and k_resolve reads it next - measured against the non-temporal store: the
-      // kernel writes 0.36 GB less per GiB, k_resolve 0.19 -> 0.14 ms per 256 MiB)
-      exit16[g * ENT + e] = (uint16_t)(ok ? (t | (min(cnt, 511u) << 7)) : 0xFFFFu);
-      wide |= ok && cnt >= 511u;
-    }
-    if (__any(wide)) {
-      for (int e = lane; e < ENT; e += 64) {
-        const uint32_t a = J[(e & 1) * J_PLANE + (e >> 1)];
-        const uint32_t t = (a >> JF) & JNONE;
-        exitmap[g * ENT + e] = ((a >> 31) != 0 && t != JNONE) ? (t | ((a & JCNT) << 8)) : R_INVALID;
-      }
+    // segment's map goes to the wide array as well (next entry state [0..7] | #ids << 8, 0xFFFFFFFF).  Lane o writes entries 2o (fd 0), 2o + 1.
+    // Test hook 5 (dbg & 32) sends every segment's map that way, as if every count had run over: no text the tests can build from UTF-8
+    // reaches 511 ids in a segment, and the resolve kernels must read the wide entries the same.
+    const bool all_wide = (dbg & 32) != 0;
+    auto ok_of = [](uint32_t a) { return (a >> 31) != 0 && ((a >> JF) & JNONE) != JNONE; };
+    auto e16 = [&](uint32_t a) -> uint32_t { return ok_of(a) ? (((a >> JF) & JNONE) | ((all_wide ? 511u : min(a & JCNT, 511u)) << 7)) : 0xFFFFu; };
+    // (an ordinary store: a map is 160 bytes, not whole lines, and k_resolve reads it next - measured against the non-temporal store: the
+    // kernel writes 0.36 GB less per GiB, k_resolve 0.19 -> 0.14 ms per 256 MiB)
+    if (lane < ENT / 2) *reinterpret_cast<uint32_t*>(exit16 + g * ENT + 2 * lane) = e16(ja[0]) | (e16(e1) << 16);
+    const bool wide = all_wide || (lane < ENT / 2 && ((ok_of(ja[0]) && (ja[0] & JCNT) >= 511u) || (ok_of(e1) && (e1 & JCNT) >= 511u)));
+    if (__any(wide) && lane < ENT / 2) {
+      exitmap[g * ENT + 2 * lane] = ok_of(ja[0]) ? ((ja[0] >> JF) & JNONE) | ((ja[0] & JCNT) << 8) : R_INVALID;
+      exitmap[g * ENT + 2 * lane + 1] = ok_of(e1) ? ((e1 >> JF) & JNONE) | ((e1 & JCNT) << 8) : R_INVALID;
     }
   }
   PH(7)
@@ -2086,7 +2096,7 @@ using namespace tmh;
 namespace tmh {
 
 // Test hooks (tm_debug_flags): bits that force a rarely taken fallback path of the product so that the tests can cover it, with the
-// same results: 6 = dense T(p,1) array for every segment, 8 = per-lane normalizer kernel, 10 = K4 tile walk that stores every id
+// same results: 5 = the wide exit map for every segment (K1 step C), 6 = dense T(p,1) array for every segment, 8 = per-lane normalizer kernel, 10 = K4 tile walk that stores every id
 // directly, 11 = the device normalizer packs its text instead of leaving it in the slabs for K1, 12 = group tree of long documents with fan-out 4
 // from 9 segments on (a deep tree on a small document), 13 = a 64 KiB
 // mailbox for the small host <-> device transfers (wraps within a test), 14 = the last member of tm_score_multi gives up after the first
@@ -2096,7 +2106,7 @@ namespace tmh {
 // phases of K1 off for profiling — 0 no walks at all, 2 no hash probes, 3 no forward-delete probes, 4 no exit maps — bit 9 adds 4 KB
 // of dummy LDS per K1 workgroup, and TM_DBG in the environment sets the initial value.
 #ifndef TM_DEVEL
-constexpr int kDebugMask = 64 | 256 | 1024 | 2048 | 4096 | 8192 | 16384 | 32768 | 65536;
+constexpr int kDebugMask = 32 | 64 | 256 | 1024 | 2048 | 4096 | 8192 | 16384 | 32768 | 65536;
 #define TM_K1_EXTRA_LDS 0
 #define TM_DBG_INITIAL 0
 #endif

@@ -118,6 +118,8 @@ static inline T emu_readfirstlane(T v) {
   return r;
 }
 #define __builtin_amdgcn_readfirstlane(x) emu_readfirstlane(x)
+// ds_bpermute: the value of lane (byte address / 4) mod 64
+#define __builtin_amdgcn_ds_bpermute(addr, v) __shfl((int)(v), (int)(((unsigned)(addr) >> 2) & 63u))
 static inline uint32_t emu_mbcnt(uint32_t mask, uint32_t acc, unsigned lo) {     // bits of mask below the lane, in the low / high half
   const unsigned lane = emu::cur->lane;
   uint32_t below;
