@@ -499,6 +499,83 @@ func (d *HipDecoder) DecodeSerialized(data []byte, encodingLength uint8) ([]byte
 	return out[:n], nil
 }
 
+// ---- the streaming encoder: one document piece by piece (tm_encoder_*) -----------------------------------------------------------------------------
+
+// HipEncoder tokenizes ONE document of already normalized text that arrives in pieces (a file read in blocks, a socket, a decompressor) or is
+// too large for one device workspace: the ids of all Feed calls and of Finish, one after the other, are those of Vocab.tokenize over the
+// whole text, however it was cut.  Feed returns the ids that are final so far (those of the last 128 bytes come with a later call).  Raw text
+// has to be normalized first: the normalizer carries state of its own across a cut.  One encoder belongs to one goroutine at a time;
+// different encoders of one vocabulary run concurrently.  The device memory held depends on maxPieceBytes (0 = 32 MiB) only.
+type HipEncoder struct{ h *C.tm_encoder }
+
+func (hv *HipVocab) NewEncoder(maxPieceBytes uint64) (*HipEncoder, error) {
+	var e *C.tm_encoder
+	if _, err := locked(func() C.int { return C.tm_encoder_new(hv.h, C.uint64_t(maxPieceBytes), &e) }); err != nil {
+		return nil, err
+	}
+	return &HipEncoder{e}, nil
+}
+func (e *HipEncoder) Close() { C.tm_encoder_free(e.h) }
+
+// fetch: the ids a call left behind because its buffer was too small (the text HAS been consumed): a call without text and a buffer of the size reported
+func (e *HipEncoder) fetch(n C.uint64_t) ([]uint32, error) {
+	out := make([]uint32, uint64(n)+1)
+	if _, err := locked(func() C.int {
+		return C.tm_encoder_feed(e.h, nil, 0, (*C.uint32_t)(unsafe.Pointer(&out[0])), C.uint64_t(n), &n)
+	}); err != nil {
+		return nil, err
+	}
+	return out[:n], nil
+}
+
+func (e *HipEncoder) Feed(normalized []byte) ([]uint32, error) {
+	var p *C.uint8_t
+	if len(normalized) > 0 {
+		p = (*C.uint8_t)(unsafe.Pointer(&normalized[0]))
+	}
+	out := make([]uint32, len(normalized)/2+256)
+	var n C.uint64_t
+	rc, err := locked(func() C.int {
+		return C.tm_encoder_feed(e.h, p, C.uint64_t(len(normalized)), (*C.uint32_t)(unsafe.Pointer(&out[0])), C.uint64_t(len(out)), &n)
+	})
+	if err != nil {
+		return nil, err
+	}
+	if rc == C.TM_E_NOSPACE {
+		return e.fetch(n)
+	}
+	return out[:n], nil
+}
+
+// Finish: the text ends here -> the remaining ids and `missing` of the whole document; the encoder is ready for the next document.
+func (e *HipEncoder) Finish() ([]uint32, int, error) {
+	out := make([]uint32, 512)
+	var n C.uint64_t
+	var missing C.uint32_t
+	rc, err := locked(func() C.int {
+		return C.tm_encoder_finish(e.h, (*C.uint32_t)(unsafe.Pointer(&out[0])), C.uint64_t(len(out)), &n, &missing)
+	})
+	if err != nil {
+		return nil, 0, err
+	}
+	if rc == C.TM_E_NOSPACE {
+		out, err = e.fetch(n)
+		return out, int(missing), err
+	}
+	return out[:n], int(missing), nil
+}
+
+// Reset forgets the current document (also after an error: a failed pass leaves the encoder unusable until then).
+func (e *HipEncoder) Reset() error {
+	_, err := locked(func() C.int { return C.tm_encoder_reset(e.h) })
+	return err
+}
+
+// State is the entry state (0..79: 2 * offset of the next token start + pending forward delete) the next pass will start in.
+func (e *HipEncoder) State() int { return int(C.tm_encoder_state(e.h)) }
+
+func (e *HipEncoder) DeviceBytes() uint64 { return uint64(C.tm_encoder_device_bytes(e.h)) }
+
 // ---- the entry points that use the calling thread's CURRENT device (HipSetDevice) instead of naming one: for a host that pins a goroutine to
 // an OS thread per GPU (runtime.LockOSThread) and keeps it there ---------------------------------------------------------------------------------
 

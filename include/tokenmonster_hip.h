@@ -46,6 +46,7 @@ typedef struct tm_vocab tm_vocab;     /* immutable device-resident vocabulary ta
 typedef struct tm_batch tm_batch;     /* reusable device workspace for one batch of documents */
 typedef struct tm_dataset tm_dataset; /* device-resident normalized dataset for the scoring pass */
 typedef struct tm_decoder tm_decoder; /* streaming Decoder: per-connection host state */
+typedef struct tm_encoder tm_encoder; /* streaming encoder: one document piece by piece; a stream and a device workspace of its own */
 
 const char* tm_last_error(void);
 int tm_device_count(void);
@@ -265,6 +266,32 @@ int tm_decoder_decode(tm_decoder* d, const uint32_t* tokens, uint64_t n, uint8_t
 int tm_decoder_decode_serialized(tm_decoder* d, const uint8_t* data, uint64_t nbytes, uint32_t encoding_length, uint8_t* out,
                                  uint64_t out_cap, uint64_t* out_len);
 int tm_decoder_flush(tm_decoder* d, uint8_t* out, uint64_t out_cap, uint64_t* out_len);
+
+/* Streaming ENCODER: one document that arrives in pieces (a file read in blocks, a socket, a decompressor) or that is larger than a device
+ * workspace should be.  The ids returned by the tm_encoder_feed calls and by tm_encoder_finish, one after the other, are tm_tokenize_batch
+ * of the concatenated text as ONE document - Vocab.tokenize (go/tokenmonster.go:1017), bit for bit - however the text was cut; so is `missing`.
+ * Text is ALREADY NORMALIZED bytes: the normalizer carries state of its own across a cut (capcode's word look-ahead, NFD mark order), so raw
+ * text has to be normalized as a whole (or at boundaries the caller knows to be safe) first.  Ids come as uint32; no serialized form.
+ * How: the walk's state at a token boundary is one of 80 entry states (tm_score_begin above); a pass over the text held so far owns all but
+ * its last 128 bytes, which it may look at, emits every token that BEGINS in what it owns, and leaves the state it ended in on the device
+ * for the next pass.  A feed therefore returns the ids that are FINAL so far: those of the last 128 bytes (and of a text shorter than 192
+ * bytes altogether) come with a later call.  tm_encoder_finish says that the text ends here, returns the remaining ids and *missing (may be
+ * NULL) for the whole document; the encoder is then ready for the next document.
+ * max_piece_bytes: the most text one device pass takes (0 = 32 MiB; at least 64); a longer feed is split inside.  The device memory held
+ * (tm_encoder_device_bytes) depends on this only, never on the length of the document.
+ * On TM_E_NOSPACE (tokens_cap too small; *n_tokens = the capacity needed) the text HAS been consumed and the ids are kept: call
+ * tm_encoder_feed with n = 0 and a larger buffer.  A text the walk cannot advance on (TM_E_INPUT above) is reported by the call whose pass
+ * meets it; after any failed pass the encoder refuses work until tm_encoder_reset, which forgets the current document.
+ * tm_encoder_state: the entry state (0..79: 2 * offset of the next token start + pending forward delete) the next pass will start in.
+ * One encoder belongs to one caller at a time; different encoders of one vocabulary run concurrently: each owns a stream and a device
+ * workspace (nothing on the NULL stream, no allocation in steady state).  Free the encoders of a vocabulary before the vocabulary. */
+int tm_encoder_new(const tm_vocab* v, uint64_t max_piece_bytes, tm_encoder** out);
+void tm_encoder_free(tm_encoder* e);
+int tm_encoder_feed(tm_encoder* e, const uint8_t* text, uint64_t n, uint32_t* tokens_out, uint64_t tokens_cap, uint64_t* n_tokens);
+int tm_encoder_finish(tm_encoder* e, uint32_t* tokens_out, uint64_t tokens_cap, uint64_t* n_tokens, uint32_t* missing);
+int tm_encoder_reset(tm_encoder* e);
+uint32_t tm_encoder_state(const tm_encoder* e);
+uint64_t tm_encoder_device_bytes(const tm_encoder* e);
 
 /* ---- trainvocab scoring pass: replaces training/trainvocab.go:925-1176 ------------------------ */
 /* Upload the normalized dataset once (trainvocab.go:1660-1665 keeps it for the whole run). */

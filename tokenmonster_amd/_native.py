@@ -82,6 +82,13 @@ SIGNATURES = {
     "tm_decoder_decode": (C.c_int, [vp, vp, C.c_uint64, vp, C.c_uint64, u64p]),
     "tm_decoder_decode_serialized": (C.c_int, [vp, vp, C.c_uint64, C.c_uint32, vp, C.c_uint64, u64p]),
     "tm_decoder_flush": (C.c_int, [vp, vp, C.c_uint64, u64p]),
+    "tm_encoder_new": (C.c_int, [vp, C.c_uint64, C.POINTER(vp)]),
+    "tm_encoder_free": (None, [vp]),
+    "tm_encoder_feed": (C.c_int, [vp, vp, C.c_uint64, vp, C.c_uint64, u64p]),
+    "tm_encoder_finish": (C.c_int, [vp, vp, C.c_uint64, u64p, u32p]),
+    "tm_encoder_reset": (C.c_int, [vp]),
+    "tm_encoder_state": (C.c_uint32, [vp]),
+    "tm_encoder_device_bytes": (C.c_uint64, [vp]),
     "tm_dataset_upload": (C.c_int, [vp, C.c_uint64, C.POINTER(vp)]),
     "tm_dataset_upload_on": (C.c_int, [vp, C.c_uint64, C.c_int, C.POINTER(vp)]),
     "tm_dataset_device": (C.c_int, [vp]),

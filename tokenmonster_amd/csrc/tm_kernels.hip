@@ -1144,6 +1144,29 @@ __global__ __launch_bounds__(128) void k_doc_exits(const uint32_t* __restrict__ 
   exits[(uint64_t)d * ENT + e0] = ok ? (uint8_t)e : (uint8_t)0xFF;
 }
 
+// The streaming encoder (tm_encoder.hip) between two passes over ONE document that arrives in pieces, on the device: the pass that has
+// just run owned the bytes [0, own) of the encoder's text buffer and could look at all `have` of them.
+//   entry[0]    <- exits[entry[0]]: the state the walk left the range in is the one the next pass enters in (k_doc_exits' map; `exits` is null
+//                  behind the last pass of a document: the next one starts a new document in state 0).  A state that has no exit cannot be
+//                  reached by a walk that K3 resolved: K3 has set the error word then, the state goes back to 0.
+//   acc[0]      += the characters without a token the pass counted (K4: doc_missing), acc[1] = the state as a word
+//   text[0 ..)  <- text[own .. have): the look-ahead of this pass is the beginning of the next one's text.  The ranges overlap when the
+//                  pass was a short one, so every thread holds its byte before any is stored (keep <= the workgroup's size).
+__global__ __launch_bounds__(256) void k_enc_carry(const uint8_t* __restrict__ exits, uint8_t* __restrict__ entry, const uint32_t* __restrict__ doc_missing,
+                                                   uint32_t* __restrict__ acc, uint8_t* __restrict__ text, uint64_t own, uint32_t keep) {
+  const uint32_t t = threadIdx.x;
+  const uint8_t byte = t < keep ? text[own + t] : (uint8_t)0;
+  __syncthreads();
+  if (t < keep) text[t] = byte;
+  if (t == 0) {
+    uint32_t e = 0u;
+    if (exits) { e = exits[entry[0]]; if (e >= (uint32_t)ENT) e = 0u; }
+    entry[0] = (uint8_t)e;
+    acc[0] += doc_missing[0];
+    acc[1] = e;
+  }
+}
+
 // Count() of a document = its ids without the delete tokens (go/tokenmonster.go:1281, quirk Q2): K3 knows the ids, K4 the delete tokens
 __global__ void k_doc_events(const uint32_t* __restrict__ doc_ntok, const uint32_t* __restrict__ doc_fd, uint32_t ndocs, uint32_t* __restrict__ doc_events) {
   const uint32_t d = blockIdx.x * blockDim.x + threadIdx.x;
@@ -2389,6 +2412,11 @@ int pipeline_resolve(tm_batch* b, hipStream_t st, hipEvent_t* ev, int mode) {
 // exit state of every document for every entry state -> exits[ndocs * ENT] (device); needs pipeline_match
 void launch_doc_exits(tm_batch* b, uint8_t* d_exits, hipStream_t st) {
   if (b->ndocs) TM_LAUNCH(k_doc_exits, b->ndocs, 128, 0, st, b->d_exitmap, b->d_exit16, b->d_doc_seg_start, b->d_gmap, b->d_longs, b->nlong, d_exits, long_segs());
+}
+
+// behind a pass of the streaming encoder (k_enc_carry): d_exits null = the pass was the document's last
+void launch_enc_carry(tm_batch* b, const uint8_t* d_exits, uint8_t* d_entry, uint32_t* d_acc, uint64_t own, uint32_t keep, hipStream_t st) {
+  TM_LAUNCH(k_enc_carry, 1, 256, 0, st, d_exits, d_entry, b->d_doc_missing, d_acc, b->d_text, own, keep);
 }
 
 int run_pipeline(tm_batch* b, hipStream_t st, bool timed, float* ms, bool emit) {

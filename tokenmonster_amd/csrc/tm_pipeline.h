@@ -271,6 +271,8 @@ int run_pipeline(tm_batch* b, hipStream_t st, bool timed, float* ms, bool emit);
 int pipeline_match(tm_batch* b, hipStream_t st, hipEvent_t* ev, bool for_score = false);      // for_score: the rows are for the scoring walk (tm_score.hip)
 int pipeline_resolve(tm_batch* b, hipStream_t st, hipEvent_t* ev, int mode);
 void launch_doc_exits(tm_batch* b, uint8_t* d_exits, hipStream_t st);
+// the streaming encoder's step from one pass to the next (k_enc_carry): entry state, missing count and the `keep` bytes of look-ahead, all on the device
+void launch_enc_carry(tm_batch* b, const uint8_t* d_exits, uint8_t* d_entry, uint32_t* d_acc, uint64_t own, uint32_t keep, hipStream_t st);
 // scoring variant of the chain kernel: histogram in HBM (scores | 4 limbs | 256 counters), see tm_score.hip
 bool raw_upload_replaces_buffers(const tm_batch* b, const uint64_t* raw_offsets, uint32_t ndocs);
 void pack_text(tm_batch* b, hipStream_t st);     // tm_norm.hip: the normalizer's slabs packed into d_text (no-op unless text_in_slabs)

@@ -257,6 +257,22 @@ class Vocab:
     def decoder(self):
         return Decoder(self)
 
+    def encoder(self, max_piece_bytes=0):
+        """streaming encoder (tm_encoder_new): ONE document of normalized text fed piece by piece, ids exactly those of tokenizing it whole"""
+        return Encoder(self, max_piece_bytes)
+
+    def tokenize_normalized_stream(self, pieces, max_piece_bytes=0):
+        """an iterable of pieces of ONE already-normalized document -> (ids u32, missing): tokenize_normalized of their concatenation,
+        with device memory that depends on max_piece_bytes (0 = 32 MiB) only"""
+        enc = self.encoder(max_piece_bytes)
+        try:
+            parts = [enc.feed(p) for p in pieces]
+            last, missing = enc.finish()
+        finally:
+            enc.close()
+        parts = [p for p in parts if p.size] + [last]
+        return (np.concatenate(parts) if len(parts) > 1 else last), missing
+
     def count_packed(self, text, offsets):
         """Count (go :971 / :1281): b-branches count once (quirk Q2) -> (counts u64[D], missing u32[D])"""
         text = N.as_u8(text)
@@ -361,6 +377,58 @@ class Decoder:
             rc = N.lib.tm_decoder_decode(self._h, None, 0, N.ptr(out), out.size, C.byref(n))
         N.check(rc)
         return out[: int(n.value)].tobytes()
+
+
+class Encoder:
+    """streaming encoder (tm_encoder_*): feed() the normalized text of ONE document in pieces of any size and get the ids that are final
+    so far; finish() says the text ends and returns (remaining ids, missing) - all ids together are those of the whole document tokenized
+    at once, however it was cut.  Raw text must be normalized first (Vocab.normalize): the normalizer has state of its own across a cut."""
+
+    def __init__(self, vocab, max_piece_bytes=0):
+        self._vocab = vocab
+        self._h = C.c_void_p()
+        N.check(N.lib.tm_encoder_new(vocab.handle, int(max_piece_bytes), C.byref(self._h)))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            N.lib.tm_encoder_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _ids(self, call, guess):
+        n = C.c_uint64()
+        out = np.empty(max(int(guess), 64), dtype=np.uint32)
+        rc = call(N.ptr(out), out.size, C.byref(n))
+        if rc == N.TM_E_NOSPACE:         # the text was consumed and the ids are kept: fetch them with a buffer of the reported size
+            out = np.empty(int(n.value), dtype=np.uint32)
+            rc = N.lib.tm_encoder_feed(self._h, None, 0, N.ptr(out), out.size, C.byref(n))
+        N.check(rc)
+        return out[: int(n.value)]
+
+    def feed(self, data):
+        d = N.as_u8(data)
+        return self._ids(lambda out, cap, n: N.lib.tm_encoder_feed(self._h, N.ptr(d), d.size, out, cap, n), d.size // 2 + 256)
+
+    def finish(self):
+        missing = C.c_uint32()
+        ids = self._ids(lambda out, cap, n: N.lib.tm_encoder_finish(self._h, out, cap, n, C.byref(missing)), 512)
+        return ids, int(missing.value)
+
+    def reset(self):
+        N.check(N.lib.tm_encoder_reset(self._h))
+
+    @property
+    def state(self):
+        """the entry state (0..79: 2 * offset of the next token start + pending forward delete) the next pass will start in"""
+        return int(N.lib.tm_encoder_state(self._h))
+
+    def device_bytes(self):
+        return int(N.lib.tm_encoder_device_bytes(self._h))
 
 
 class PipelineStats(C.Structure):
