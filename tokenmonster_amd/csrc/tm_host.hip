@@ -480,6 +480,25 @@ struct PipeCall {
   std::string first_msg;
   std::atomic<size_t> next{0};
   double t0 = 0;
+  // test hook 24 (tm_debug_flags, TM_TEST_FAIL="<place>:<chunk>[:<chunks>]"): ONE chunk of this call fails with TM_E_INPUT at a place of the
+  // host code - an error return like any other, nothing on the device differs.  hook_place stays 0 in every call of a process without the hook.
+  enum { HOOK_FINISHER = 1, HOOK_EXACT, HOOK_ISSUER, HOOK_DOWNLOAD };
+  int hook_place = 0;
+  size_t hook_chunk = 0;
+  bool hook(int place, size_t k) const { return hook_place == place && hook_chunk == k; }
+  void hook_arm() {
+    static const char* const names[] = {"", "finisher", "exact", "issuer", "download"};
+    const char* e = getenv("TM_TEST_FAIL");
+    const char* colon = e ? strchr(e, ':') : nullptr;
+    if (!colon) return;
+    char* end = nullptr;
+    const unsigned long long k = strtoull(colon + 1, &end, 10);
+    if (end == colon + 1) return;
+    if (*end == ':' && strtoull(end + 1, nullptr, 10) != nchunks) return;      // (a call of another shape: a second caller beside the one under test)
+    for (int p = HOOK_FINISHER; p <= HOOK_DOWNLOAD; p++)
+      if (strlen(names[p]) == (size_t)(colon - e) && !strncmp(e, names[p], (size_t)(colon - e))) { hook_place = p; hook_chunk = (size_t)k; }
+  }
+  static int hook_fail(const char* place, size_t k) { return set_error(TM_E_INPUT, "test hook 24: chunk %zu fails at the place '%s' of the pipeline", k, place); }
   void fail(int rc) {
     { std::lock_guard<std::mutex> g(mu); if (first_error == TM_OK) { first_error = rc; first_msg = last_error(); } }
     cv.notify_all();
@@ -517,6 +536,7 @@ static int chunk_exact(PipeCall& c, const tm_vocab* v, size_t k) {
     }
     RunOut ro;
     if ((rc = lane_run(l, v, src, lo.data(), nd, c.raw != 0, true, &ro)) != TM_OK) break;
+    if (c.hook(PipeCall::HOOK_EXACT, k)) { rc = PipeCall::hook_fail("exact", k); break; }
     uint64_t base = 0;
     if (!c.order(k, ro.total_tokens, &base)) break;
     tm_batch* b = l->ws;
@@ -536,7 +556,11 @@ static int chunk_exact(PipeCall& c, const tm_vocab* v, size_t k) {
     for (uint32_t d = 1; d <= nd; d++) c.byte_offsets[d0 + d] = (base + toff[d]) * c.enc;
     if (c.stats) { std::lock_guard<std::mutex> g(c.mu); c.stats->host_fallback_docs += c.raw ? b->host_fallback_docs : 0; c.stats->normalized_bytes += b->nbytes; }
   } while (false);
-  if (rc != TM_OK) (void)hipStreamSynchronize(l->stream);
+  if (rc != TM_OK) {          // (nothing of the chunk in flight when the lane goes back, and no small transfer left that would land in `toff` later)
+    const std::string msg = last_error();
+    if (l->ws) (void)small_sync(l->ws, l->stream); else (void)hipStreamSynchronize(l->stream);
+    set_error(rc, "%s", msg.c_str());
+  }
   lane_release(v, l);
   return rc;
 }
@@ -600,12 +624,20 @@ static int pipeline_ring(PipeCall& c, const std::vector<Ring*>& rings) {
   std::vector<std::unique_ptr<Dev>> devs;
   for (uint32_t i = 0; i < c.nv; i++) { auto d = std::make_unique<Dev>(); d->v = c.vs[i]; d->r = rings[i]; d->slot_free.assign(rings[i]->slots.size(), 1); devs.push_back(std::move(d)); }
 
+  // A failure is every pair's business: the first one is recorded, and every issuer that waits for a slot - on this device or another - hears of
+  // it (the lock is taken and dropped so that the news cannot fall between a waiter's look at the predicate and its sleep).
+  auto fail_all = [&](int rc) {
+    c.fail(rc);
+    for (auto& d : devs) { { std::lock_guard<std::mutex> g(d->mu); } d->cv.notify_all(); }
+  };
+
   auto issuer = [&](Dev& dv) {
     const tm_vocab* const v = dv.v;
     Ring& r = *dv.r;
     NearDevice near_gpu(v->device);
     int rc = enter_device(v);
     size_t issued = 0;
+    bool enqueued = false;
     while (rc == TM_OK && !c.failed()) {
       const size_t k = c.next.fetch_add(1);
       if (k >= c.nchunks) break;
@@ -615,7 +647,8 @@ static int pipeline_ring(PipeCall& c, const std::vector<Ring*>& rings) {
       if (nb > 0) {
         // a free slot (the finisher hands them back in order)
         std::unique_lock<std::mutex> lk(dv.mu);
-        dv.cv.wait(lk, [&] { for (char f : dv.slot_free) if (f) return true; return false; });
+        dv.cv.wait(lk, [&] { for (char f : dv.slot_free) if (f) return true; return c.failed(); });
+        if (c.failed()) break;          // (nothing more is issued behind a failure; the finisher drains what is in flight)
         for (size_t j = 0; j < dv.slot_free.size(); j++) { const size_t q = (issued + j) % dv.slot_free.size(); if (dv.slot_free[q]) { si = (int)q; break; } }
         dv.slot_free[si] = 0;
       }
@@ -630,10 +663,12 @@ static int pipeline_ring(PipeCall& c, const std::vector<Ring*>& rings) {
         hipStream_t cs = r.comp[issued % r.comp.size()];
         hipError_t e = hipSuccess;
         const double ti0 = trace ? now_ms() : 0;
+        enqueued = true;
         if ((rc = raw_prepare(b, nb, nd, npieces, cs)) != TM_OK) break;
         if ((e = hipMemcpyAsync(b->d_raw, c.text + b0, nb, hipMemcpyHostToDevice, r.up)) != hipSuccess ||
             (e = hipMemcpyAsync(b->d_raw_off, lo, ((uint64_t)nd + 1) * 8, hipMemcpyHostToDevice, r.up)) != hipSuccess ||
             (e = hipEventRecord(s.up_done, r.up)) != hipSuccess || (e = hipStreamWaitEvent(cs, s.up_done, 0)) != hipSuccess) { rc = hip_fail(e, "ring upload"); break; }
+        if (c.hook(PipeCall::HOOK_ISSUER, k)) { rc = PipeCall::hook_fail("issuer", k); break; }
         const uint64_t seg_bound = (nb / 100 * slack_pct + 99) / SEG + nd + 1;
         s.h_status()[0] = ~0ull;
         if ((rc = ring_enqueue_normalize(b, cs, seg_bound, lo)) != TM_OK) break;
@@ -645,7 +680,12 @@ static int pipeline_ring(PipeCall& c, const std::vector<Ring*>& rings) {
       { std::lock_guard<std::mutex> g(dv.mu); dv.queue.emplace_back(k, si); }
       dv.cv.notify_all();
     }
-    if (rc != TM_OK) c.fail(rc);
+    if (rc != TM_OK) {
+      // the chunk this thread was enqueuing never reaches the finisher: its upload reads the caller's text and its kernels write a slot's
+      // workspace, and neither may outlive the call
+      if (enqueued) { (void)hipStreamSynchronize(r.up); for (hipStream_t st : r.comp) (void)hipStreamSynchronize(st); }
+      fail_all(rc);
+    }
     { std::lock_guard<std::mutex> g(dv.mu); dv.issuer_done = true; }
     dv.cv.notify_all();
   };
@@ -657,6 +697,12 @@ static int pipeline_ring(PipeCall& c, const std::vector<Ring*>& rings) {
     int rc = enter_device(v);
     struct Pending { size_t k; int si; uint64_t base, ntok; };
     Pending prev{0, -1, 0, 0};
+    // a slot whose chunk goes no further (a failure, here or elsewhere) back to the issuer, which may be waiting for it
+    auto give_back = [&](int si) {
+      if (si < 0) return;
+      { std::lock_guard<std::mutex> g(dv.mu); dv.slot_free[si] = 1; }
+      dv.cv.notify_all();
+    };
     // the downloads of a chunk are through: its offsets and counts to the caller, the slot back to the issuer
     auto complete = [&](const Pending& p) -> int {
       RingSlot& s = r.slots[p.si];
@@ -682,6 +728,7 @@ static int pipeline_ring(PipeCall& c, const std::vector<Ring*>& rings) {
       const int si = item.second;
       if (rc != TM_OK || c.failed()) {              // (drain: whatever is in flight ends before the call returns)
         if (si >= 0) (void)hipEventSynchronize(r.slots[si].comp_done);
+        give_back(si);
         continue;
       }
       bool exact = si < 0;
@@ -705,23 +752,24 @@ static int pipeline_ring(PipeCall& c, const std::vector<Ring*>& rings) {
             TM_CPU_RELAX();
           }
         }
-        if (e != hipSuccess) { rc = hip_fail(e, "ring chunk"); c.fail(rc); continue; }
+        if (e != hipSuccess) { rc = hip_fail(e, "ring chunk"); fail_all(rc); give_back(si); continue; }
+        if (c.hook(PipeCall::HOOK_FINISHER, k)) { rc = PipeCall::hook_fail("finisher", k); fail_all(rc); give_back(si); continue; }
         const uint64_t st = s.h_status()[0];
-        if (st == ~0ull) { rc = set_error(TM_E_INTERNAL, "a chunk of the ring ended without its verdict"); c.fail(rc); continue; }
+        if (st == ~0ull) { rc = set_error(TM_E_INTERNAL, "a chunk of the ring ended without its verdict"); fail_all(rc); give_back(si); continue; }
         if (trace) fprintf(stderr, "[ring] chunk %3zu computed at %7.2f ms: status %llu, %llu ids, %llu segments\n", k, now_ms() - c.t0, (unsigned long long)st,
                            (unsigned long long)s.h_status()[1], (unsigned long long)s.h_status()[3]);
-        if (st != 0) exact = true; else ntok = s.h_status()[1];
+        if (st != 0 || c.hook(PipeCall::HOOK_EXACT, k)) exact = true; else ntok = s.h_status()[1];
       }
       if (exact) {
         if (si >= 0) { std::lock_guard<std::mutex> g(dv.mu); dv.slot_free[si] = 1; }
         if (si >= 0) dv.cv.notify_all();
         if (c.stats && si >= 0) { std::lock_guard<std::mutex> g(c.mu); c.stats->ring_exact_chunks++; }
-        if ((rc = chunk_exact(c, v, k)) != TM_OK) c.fail(rc);
+        if ((rc = chunk_exact(c, v, k)) != TM_OK) fail_all(rc);
         continue;
       }
       RingSlot& s = r.slots[si];
       uint64_t base = 0;
-      if (!c.order(k, ntok, &base)) { rc = TM_E_INTERNAL; continue; }
+      if (!c.order(k, ntok, &base)) { rc = TM_E_INTERNAL; give_back(si); continue; }
       const uint32_t nd = c.first[k + 1] - c.first[k];
       const uint64_t out_b = ntok * c.enc;
       const bool fits = (base + ntok) * c.enc <= c.bytes_cap && c.bytes_out;
@@ -730,11 +778,13 @@ static int pipeline_ring(PipeCall& c, const std::vector<Ring*>& rings) {
       if (e == hipSuccess) e = hipMemcpyAsync(s.h_toff(), s.ws->d_tok_offsets, ((uint64_t)nd + 1) * 8, hipMemcpyDeviceToHost, r.down);
       if (e == hipSuccess && c.missing) e = hipMemcpyAsync(s.h_missing(), s.ws->d_doc_missing, (uint64_t)nd * 4, hipMemcpyDeviceToHost, r.down);
       if (e == hipSuccess) e = hipEventRecord(s.dl_done, r.down);
-      if (e != hipSuccess) { rc = hip_fail(e, "ring download"); c.fail(rc); continue; }
-      if (prev.si >= 0 && (rc = complete(prev)) != TM_OK) { c.fail(rc); prev.si = -1; continue; }
+      if (e != hipSuccess) { rc = hip_fail(e, "ring download"); fail_all(rc); give_back(si); continue; }
+      // (a failure behind the enqueued download: r.down is waited for before the finisher leaves, `prev` below)
+      if (c.hook(PipeCall::HOOK_DOWNLOAD, k)) { rc = PipeCall::hook_fail("download", k); fail_all(rc); give_back(si); continue; }
+      if (prev.si >= 0 && (rc = complete(prev)) != TM_OK) { fail_all(rc); give_back(prev.si); give_back(si); prev.si = -1; continue; }
       prev = Pending{k, si, base, ntok};
     }
-    if (prev.si >= 0) { if (rc == TM_OK && !c.failed()) { if ((rc = complete(prev)) != TM_OK) c.fail(rc); } else (void)hipEventSynchronize(r.slots[prev.si].dl_done); }
+    if (prev.si >= 0) { if (rc == TM_OK && !c.failed()) { if ((rc = complete(prev)) != TM_OK) fail_all(rc); } else (void)hipEventSynchronize(r.slots[prev.si].dl_done); }
     (void)hipStreamSynchronize(r.down);
   };
 
@@ -857,6 +907,7 @@ int tokenize_pipeline_on(const tm_vocab* const* vs, uint32_t nv, const uint8_t* 
   c.known.assign(c.nchunks + 1, 0);
   c.known[0] = 1;
   c.t0 = now_ms();
+  if (debug_flags() & 16777216) c.hook_arm();
   { static const bool trace = getenv("TM_TRACE") != nullptr; if (trace) fprintf(stderr, "[pipe] %zu chunks laid out in %.3f ms (%s)\n", c.nchunks, c.t0 - t_entry, use_ring ? "ring" : "lanes"); }
   if (c.nchunks < 2) use_ring = false;          // (one chunk: the lanes' form is the shorter way)
   int rc = TM_OK;
@@ -958,6 +1009,7 @@ static int pipeline_lanes(PipeCall& c) {
       RunOut ro;
       if (trace) tr1 = now_ms();
       if ((rc = lane_compute(l, v, src, loc.data(), nd, raw != 0, true, &ro, prefetch)) != TM_OK) break;
+      if (c.hook(PipeCall::HOOK_EXACT, k)) { rc = PipeCall::hook_fail("exact", k); break; }
       if (trace) tr2 = now_ms();
       if (k_next == nchunks && !next_up) k_next = next.fetch_add(1);          // (already-normalized input: nothing was prefetched)
       uint64_t base = 0;
@@ -983,6 +1035,7 @@ static int pipeline_lanes(PipeCall& c) {
         }
         if (rc != TM_OK) break;
       }
+      if (c.hook(PipeCall::HOOK_DOWNLOAD, k)) { rc = PipeCall::hook_fail("download", k); break; }
       if ((rc = small_sync(b, l->stream)) != TM_OK) break;
       if (fits && out_b && !out_pinned) std::memcpy(bytes_out + base * encoding_length, l->h_stage, out_b);
       if (trace) fprintf(stderr, "[pipe] worker %u chunk %3zu (%5.1f MiB): start %7.2f  upload/wait %5.2f  compute %5.2f  order-wait %5.2f  download %5.2f  -> end %7.2f ms\n", wi, k,
@@ -995,6 +1048,8 @@ static int pipeline_lanes(PipeCall& c) {
     }
     if (l && l->up_stream) (void)hipStreamSynchronize(l->up_stream);          // (an error may leave an upload in flight)
     if (rc != TM_OK) c.fail(rc);
+    // (... or a download into the caller's buffer, or small transfers into this thread's own arrays: they end here, not in a later call)
+    if (rc != TM_OK && l) { if (l->ws) (void)small_sync(l->ws, l->stream); else (void)hipStreamSynchronize(l->stream); }
     if (l) lane_release(v, l);
   };
   std::vector<std::thread> th;

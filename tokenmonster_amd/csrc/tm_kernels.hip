@@ -2124,12 +2124,14 @@ namespace tmh {
 // from 9 segments on (a deep tree on a small document), 13 = a 64 KiB
 // mailbox for the small host <-> device transfers (wraps within a test), 14 = the last member of tm_score_multi gives up after the first
 // meeting of the members (an ERROR path: every member must return), 15 = K4's id-staging walk for two-plane rows too, 16 = k_segments and k_seg_src one
-// behind the other for a chunk of the host-to-host ring too (which has them in one launch, k_seg_fill).  Nothing else is
+// behind the other for a chunk of the host-to-host ring too (which has them in one launch, k_seg_fill), 24 = one chunk of a
+// tm_tokenize_pipeline call fails at a place of the host code named in TM_TEST_FAIL (an ERROR path, tm_host.hip: PipeCall::hook_arm; the bits 17 - 23
+// between belong to the -DTM_DEVEL build, and the match kernel reads 17 and 18 in every build).  Nothing else is
 // reachable in the default build.  With -DTM_DEVEL (tools/ only: results are WRONG) further bits switch
 // phases of K1 off for profiling — 0 no walks at all, 2 no hash probes, 3 no forward-delete probes, 4 no exit maps — bit 9 adds 4 KB
 // of dummy LDS per K1 workgroup, and TM_DBG in the environment sets the initial value.
 #ifndef TM_DEVEL
-constexpr int kDebugMask = 32 | 64 | 256 | 1024 | 2048 | 4096 | 8192 | 16384 | 32768 | 65536;
+constexpr int kDebugMask = 32 | 64 | 256 | 1024 | 2048 | 4096 | 8192 | 16384 | 32768 | 65536 | 16777216;
 #define TM_K1_EXTRA_LDS 0
 #define TM_DBG_INITIAL 0
 #endif
