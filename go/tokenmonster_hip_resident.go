@@ -503,8 +503,8 @@ func (d *HipDecoder) DecodeSerialized(data []byte, encodingLength uint8) ([]byte
 
 // HipEncoder tokenizes ONE document of already normalized text that arrives in pieces (a file read in blocks, a socket, a decompressor) or is
 // too large for one device workspace: the ids of all Feed calls and of Finish, one after the other, are those of Vocab.tokenize over the
-// whole text, however it was cut.  Feed returns the ids that are final so far (those of the last 128 bytes come with a later call).  Raw text
-// has to be normalized first: the normalizer carries state of its own across a cut.  One encoder belongs to one goroutine at a time;
+// whole text, however it was cut.  Feed returns the ids that are final so far (those of the last 128 bytes come with a later call).  Feed
+// takes normalized text, FeedRaw raw UTF-8 (one document goes through one of the two).  One encoder belongs to one goroutine at a time;
 // different encoders of one vocabulary run concurrently.  The device memory held depends on maxPieceBytes (0 = 32 MiB) only.
 type HipEncoder struct{ h *C.tm_encoder }
 
@@ -546,6 +546,39 @@ func (e *HipEncoder) Feed(normalized []byte) ([]uint32, error) {
 	}
 	return out[:n], nil
 }
+
+// EncoderRawSupported: whether FeedRaw takes this vocabulary's raw text (capcode 0 or 2 and none of the flags quotemarks, trim, leadingspace,
+// which need the whole document).
+func (hv *HipVocab) EncoderRawSupported() bool { return C.tm_encoder_raw_supported(hv.h) != 0 }
+
+// FeedRaw takes the document's RAW text, cut anywhere (inside a UTF-8 character too): the library normalizes and tokenizes up to the last line
+// feed it has been given - the normalizer has no state there - and keeps what lies behind it (RawHeld) until more text or Finish comes.  The ids
+// are those of normalizing and tokenizing the whole text at once.  A line of more than maxPieceBytes is cut behind its last tab or ASCII
+// punctuation byte; without one the call fails (TM_E_LIMIT) and the encoder wants Reset.
+func (e *HipEncoder) FeedRaw(raw []byte) ([]uint32, error) {
+	var p *C.uint8_t
+	if len(raw) > 0 {
+		p = (*C.uint8_t)(unsafe.Pointer(&raw[0]))
+	}
+	out := make([]uint32, len(raw)/2+256)
+	var n C.uint64_t
+	rc, err := locked(func() C.int {
+		return C.tm_encoder_feed_raw(e.h, p, C.uint64_t(len(raw)), (*C.uint32_t)(unsafe.Pointer(&out[0])), C.uint64_t(len(out)), &n)
+	})
+	if err != nil {
+		return nil, err
+	}
+	if rc == C.TM_E_NOSPACE {
+		return e.fetch(n)
+	}
+	return out[:n], nil
+}
+
+// RawHeld: raw bytes kept on the host behind the last safe cut.
+func (e *HipEncoder) RawHeld() uint64 { return uint64(C.tm_encoder_raw_held(e.h)) }
+
+// HostPieces: raw pieces of the current (after Finish: the last) document that the host normalizer took.
+func (e *HipEncoder) HostPieces() int { return int(C.tm_encoder_host_pieces(e.h)) }
 
 // Finish: the text ends here -> the remaining ids and `missing` of the whole document; the encoder is ready for the next document.
 func (e *HipEncoder) Finish() ([]uint32, int, error) {

@@ -278,8 +278,8 @@ int tm_decoder_flush(tm_decoder* d, uint8_t* out, uint64_t out_cap, uint64_t* ou
 /* Streaming ENCODER: one document that arrives in pieces (a file read in blocks, a socket, a decompressor) or that is larger than a device
  * workspace should be.  The ids returned by the tm_encoder_feed calls and by tm_encoder_finish, one after the other, are tm_tokenize_batch
  * of the concatenated text as ONE document - Vocab.tokenize (go/tokenmonster.go:1017), bit for bit - however the text was cut; so is `missing`.
- * Text is ALREADY NORMALIZED bytes: the normalizer carries state of its own across a cut (capcode's word look-ahead, NFD mark order), so raw
- * text has to be normalized as a whole (or at boundaries the caller knows to be safe) first.  Ids come as uint32; no serialized form.
+ * tm_encoder_feed takes ALREADY NORMALIZED bytes, tm_encoder_feed_raw (below) raw UTF-8; one document is fed through one of the two.  Ids come
+ * as uint32; no serialized form.
  * How: the walk's state at a token boundary is one of 80 entry states (tm_score_begin above); a pass over the text held so far owns all but
  * its last 128 bytes, which it may look at, emits every token that BEGINS in what it owns, and leaves the state it ended in on the device
  * for the next pass.  A feed therefore returns the ids that are FINAL so far: those of the last 128 bytes (and of a text shorter than 192
@@ -300,6 +300,27 @@ int tm_encoder_finish(tm_encoder* e, uint32_t* tokens_out, uint64_t tokens_cap, 
 int tm_encoder_reset(tm_encoder* e);
 uint32_t tm_encoder_state(const tm_encoder* e);
 uint64_t tm_encoder_device_bytes(const tm_encoder* e);
+/* RAW text through the streaming encoder.  The normalizer carries state of its own across a cut (capcode's word look-ahead and rewrite
+ * window, the order of marks under NFD, the neighbours `collapse` and `unixlines` look at), but right behind a line feed that state is the
+ * state at the start of a text: normalize(a + b) == normalize(a) + normalize(b) when a ends in '\n'.  So the library cuts the raw text
+ * itself: tm_encoder_feed_raw normalizes and tokenizes everything up to the last '\n' it has been given - on the device, as pieces of at most
+ * max_piece_bytes; a piece with characters the device normalizer leaves to the host normalizer takes that path inside the call
+ * (tm_encoder_host_pieces counts them per document) - and keeps the raw bytes behind it on the host (tm_encoder_raw_held of them) until more
+ * text or tm_encoder_finish arrives; tm_encoder_finish normalizes them as the last piece.  The ids of the calls and of tm_encoder_finish, one
+ * after the other, and `missing` are those of tm_normalize + tm_tokenize_batch of the whole text as one document, wherever the caller cut it:
+ * inside a UTF-8 character, inside a run of capitals, between '\r' and '\n'.
+ * Once max_piece_bytes are held without a '\n' the cut goes behind the last byte of  \t . , ; : ! ? ( ) [ ] { } < > = / - "  (the same holds
+ * there); without one of those either the call returns TM_E_LIMIT - normalize such a text as a whole - and the encoder wants tm_encoder_reset.
+ * Vocabularies: capcode 0 or 2 and none of the normalization flags quotemarks 8, trim 32, leadingspace 64 - those need the whole document -
+ * (tm_encoder_raw_supported: 1 or 0).  With another vocabulary tm_encoder_feed_raw returns TM_E_INVALID, consumes nothing and leaves the
+ * encoder to tm_encoder_feed.  Within one document tm_encoder_feed and tm_encoder_feed_raw do not mix (TM_E_INVALID, nothing consumed;
+ * tm_encoder_finish and tm_encoder_reset end the document; calls with n = 0, which only fetch ids, are free).  TM_E_NOSPACE, tm_encoder_state
+ * and the threading rule are those of tm_encoder_feed.  The normalizer's device workspace is made by the first raw feed - its size depends on
+ * max_piece_bytes only - and counts in tm_encoder_device_bytes from then on; an encoder that is only fed normalized text never holds it. */
+int tm_encoder_raw_supported(const tm_vocab* v);
+int tm_encoder_feed_raw(tm_encoder* e, const uint8_t* raw, uint64_t n, uint32_t* tokens_out, uint64_t tokens_cap, uint64_t* n_tokens);
+uint64_t tm_encoder_raw_held(const tm_encoder* e);
+uint32_t tm_encoder_host_pieces(const tm_encoder* e);
 
 /* ---- trainvocab scoring pass: replaces training/trainvocab.go:925-1176 ------------------------ */
 /* Upload the normalized dataset once (trainvocab.go:1660-1665 keeps it for the whole run). */

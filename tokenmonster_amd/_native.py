@@ -89,6 +89,10 @@ SIGNATURES = {
     "tm_encoder_reset": (C.c_int, [vp]),
     "tm_encoder_state": (C.c_uint32, [vp]),
     "tm_encoder_device_bytes": (C.c_uint64, [vp]),
+    "tm_encoder_raw_supported": (C.c_int, [vp]),
+    "tm_encoder_feed_raw": (C.c_int, [vp, vp, C.c_uint64, vp, C.c_uint64, u64p]),
+    "tm_encoder_raw_held": (C.c_uint64, [vp]),
+    "tm_encoder_host_pieces": (C.c_uint32, [vp]),
     "tm_dataset_upload": (C.c_int, [vp, C.c_uint64, C.POINTER(vp)]),
     "tm_dataset_upload_on": (C.c_int, [vp, C.c_uint64, C.c_int, C.POINTER(vp)]),
     "tm_dataset_device": (C.c_int, [vp]),

@@ -15,9 +15,24 @@
 // state never visits the host.  tm_encoder_finish runs what is left as a range the text ENDS with (doc_vis == doc_end: the pad byte 0).
 // A range that is followed by more text must be at least MIN_RANGE bytes long (tm_score_begin's rule: the entry states' offsets, < 40,
 // lie inside it), so short feeds are kept on the host until HALO + MIN_RANGE bytes are there.
+//
+// RAW text (tm_encoder_feed_raw).  The normalizer has state of its own across a cut - capcode's inWord / rlast / rlast2 and its rewrite window,
+// the order of the marks behind a starter under NFD, the byte before and behind for `collapse` and `unixlines` - but behind a line feed that
+// state is the state at the start of a text (javascript/tokenmonster.js:900-1005): normalize(a + b) == normalize(a) + normalize(b) wherever a
+// ends in '\n', and in any byte of FALLBACK below (tests/test_safe_cuts.py keeps that claim checked against the host normalizer).  So the encoder
+// cuts the raw text itself: right behind the last '\n' of what it has, or - once max_piece_bytes are held without one - behind the last tab or
+// ASCII punctuation byte; what lies behind the cut waits on the host (rhold).  A raw piece goes through the batch normalizer as ONE document of
+// a normalizer workspace of the encoder's own (created by the first raw feed, sized by max_piece_bytes, on the encoder's stream), and its
+// normalized bytes go from there - slabs or packed text - behind the look-ahead in the text buffer, device to device (k_enc_pack, tm_norm.hip),
+// in portions of what the buffer has room for; each portion is then a normalized feed like any other.  A piece the device normalizer leaves to
+// the host normalizer (full-width Latin, polytonic Greek, malformed UTF-8 ...) takes that path inside the same call (tm_encoder_host_pieces).
+// Out of scope, because they need the whole document: the flags quotemarks 8 (the reference's in-place quirk counts the bytes the document has
+// lost so far), trim 32 (unbounded look-ahead for trailing blanks) and leadingspace 64 (the document's start); capcode 1.  Also out: a
+// serialized output form, and running the normalizer of piece k + 1 beside the walk of piece k.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cstddef>
 #include <cstring>
 #include <vector>
 
@@ -41,6 +56,11 @@ struct tm_encoder {
   std::vector<uint8_t> hold;         // bytes fed since, while they are too few for a pass
   std::vector<uint32_t> pending;     // ids not yet handed to the caller (a call whose buffer was too small)
   bool failed = false;               // a pass failed: the carried state means nothing until tm_encoder_reset
+  // raw text (tm_encoder_feed_raw)
+  tm_batch* nws = nullptr;           // the normalizer's workspace: one raw piece = one document of it
+  std::vector<uint8_t> rhold;        // raw bytes behind the last cut (no '\n' among them)
+  int mode = 0;                      // what the current document is fed as: 0 nothing yet, 1 normalized, 2 raw
+  uint32_t host_pieces = 0;          // raw pieces of this document (after finish: the last one) that the host normalizer took
   // the range of the last pass as the workspace holds it on the device (offsets, group tree): a stream of equal pieces uploads it once
   uint64_t r_own = ~0ull, r_have = ~0ull;
   uint32_t r_long = 0;
@@ -127,6 +147,85 @@ int enc_upload(tm_encoder* e, const uint8_t* src, uint64_t n) {
   return rc;
 }
 
+// ---- raw text ------------------------------------------------------------------------------------------------------------------------
+// bytes behind which the normalizer is in its start state (see the header): '\n' wherever there is one, these once a line outgrows a piece
+bool fallback_cut(uint8_t c) {
+  switch (c) {
+    case '\n': case '\t': case '.': case ',': case ';': case ':': case '!': case '?': case '(': case ')': case '[': case ']': case '{': case '}':
+    case '<': case '>': case '=': case '/': case '-': case '"': return true;
+    default: return false;
+  }
+}
+
+// TM_OK, or why this vocabulary's raw text cannot be cut (thread-local message set)
+int raw_refusal(const tm_vocab* v, bool say) {
+  const uint32_t capcode = v->host.capcode, flag = v->host.norm_flag;
+  const char* why = nullptr;
+  if (capcode != 0 && capcode != 2) why = "capcode 1";
+  else if (flag & 8u) why = "the normalization flag quotemarks (8)";
+  else if (flag & 32u) why = "the normalization flag trim (32)";
+  else if (flag & 64u) why = "the normalization flag leadingspace (64)";
+  else if (!normalize_supported(capcode, flag)) why = "normalization flags the normalizer does not implement";
+  if (!why) return TM_OK;
+  return say ? set_error(TM_E_INVALID, "%s needs the whole document: normalize it first and use tm_encoder_feed", why) : TM_E_INVALID;
+}
+
+// the normalized size a raw piece of max_piece bytes may have on the device: three times (a Hangul syllable under NFD) and some
+uint64_t piece_norm_cap(uint64_t max_piece) { return 3 * max_piece + 4096; }
+
+int enc_make_nws(tm_encoder* e) {
+  tm_batch* nb = nullptr;
+  int rc = make_piece_workspace(e->v, piece_norm_cap(e->max_piece), e->stream, &nb);
+  if (rc == TM_OK) rc = piece_reserve(nb, e->max_piece, e->stream);
+  if (rc != TM_OK) { tm_batch_free(nb); return rc; }
+  e->nws = nb;
+  return TM_OK;
+}
+
+// `total` normalized bytes behind the look-ahead in the text buffer, in portions of what the buffer has room for; put(off, take) places a
+// portion at d_text + have.  A pass runs as soon as there is enough for a range that is followed by more text.
+template <typename Put>
+int enc_portions(tm_encoder* e, uint64_t total, uint32_t* out, uint64_t cap, uint64_t* written, Put put) {
+  for (uint64_t off = 0; off < total;) {
+    const uint64_t take = std::min<uint64_t>(total - off, HALO + e->max_piece - e->have);
+    int rc = put(off, take);
+    if (rc != TM_OK) return rc;
+    e->have += take;
+    off += take;
+    if (e->have < HALO + MIN_RANGE) continue;           // (then off == total: the next piece goes behind it)
+    uint64_t ids = 0;
+    if ((rc = enc_pass(e, false, &ids)) != TM_OK || (rc = enc_collect(e, ids, out, cap, written)) != TM_OK) return rc;
+  }
+  return TM_OK;
+}
+
+// one raw piece [p, p + n), n > 0: a document of its own for the normalizer
+int enc_raw_piece(tm_encoder* e, const uint8_t* p, uint64_t n, uint32_t* out, uint64_t cap, uint64_t* written) {
+  tm_batch* nb = e->nws;
+  hipStream_t st = e->stream;
+  const uint64_t offs[2] = {0, n};
+  int rc = batch_upload_raw_on(nb, p, offs, 1, st);
+  if (rc == TM_OK) rc = piece_normalize_on(nb, st);
+  if (rc == TM_OK) {
+    e->host_pieces += nb->host_fallback_docs ? 1u : 0u;
+    return enc_portions(e, nb->nbytes, out, cap, written, [&](uint64_t off, uint64_t take) {
+      launch_enc_pack(nb, off, take, e->ws->d_text + e->have, st);
+      hipError_t he = hipGetLastError();
+      return he == hipSuccess ? TM_OK : hip_fail(he, "kernel launch");
+    });
+  }
+  if (rc != TM_E_LIMIT) return rc;
+  // normalized, the piece is larger than the workspace was sized for: the host normalizer, and its text uploaded in portions
+  std::vector<uint8_t> norm;
+  normalize_bytes(p, n, e->v->host.capcode, e->v->host.norm_flag, norm);
+  e->host_pieces++;
+  return enc_portions(e, norm.size(), out, cap, written, [&](uint64_t off, uint64_t take) {
+    int r2 = small_h2d(e->ws, e->ws->d_text + e->have, norm.data() + off, take, st);
+    if (r2 == TM_OK) r2 = small_sync(e->ws, st);       // (`norm` is pageable and goes away)
+    return r2;
+  });
+}
+
 }  // namespace
 
 extern "C" {
@@ -154,6 +253,7 @@ void tm_encoder_free(tm_encoder* e) {
   if (!e) return;
   if (e->stream) (void)hipStreamSynchronize(e->stream);
   tm_batch_free(e->ws);
+  tm_batch_free(e->nws);
   (void)hipFree(e->d_small);
   if (e->stream) (void)hipStreamDestroy(e->stream);
   delete e;
@@ -162,6 +262,8 @@ void tm_encoder_free(tm_encoder* e) {
 int tm_encoder_feed(tm_encoder* e, const uint8_t* text, uint64_t n, uint32_t* tokens_out, uint64_t tokens_cap, uint64_t* n_tokens) {
   { int rc = enc_usable(e); if (rc != TM_OK) return rc; }
   if (n && !text) return set_error(TM_E_INVALID, "null argument");
+  if (n && e->mode == 2) return set_error(TM_E_INVALID, "this document is being fed as raw text (tm_encoder_feed_raw): one document is fed either raw or normalized");
+  if (n) e->mode = 1;
   uint64_t written = 0, pos = 0;
   const uint64_t room = HALO + e->max_piece;
   while (pos < n) {
@@ -187,8 +289,14 @@ int tm_encoder_feed(tm_encoder* e, const uint8_t* text, uint64_t n, uint32_t* to
 int tm_encoder_finish(tm_encoder* e, uint32_t* tokens_out, uint64_t tokens_cap, uint64_t* n_tokens, uint32_t* missing) {
   { int rc = enc_usable(e); if (rc != TM_OK) return rc; }
   uint64_t written = 0, total = 0;
-  int rc = enc_upload(e, e->hold.data(), e->hold.size());
+  int rc = TM_OK;
+  if (!e->rhold.empty()) {                               // what lay behind the last cut is the last raw piece
+    rc = enc_raw_piece(e, e->rhold.data(), e->rhold.size(), tokens_out, tokens_cap, &written);
+    e->rhold.clear();
+  }
+  if (rc == TM_OK) rc = enc_upload(e, e->hold.data(), e->hold.size());
   e->hold.clear();
+  e->mode = 0;
   if (rc == TM_OK && e->have) {
     rc = enc_pass(e, true, &total);
     if (rc == TM_OK) rc = enc_collect(e, total, tokens_out, tokens_cap, &written);
@@ -208,6 +316,9 @@ int tm_encoder_reset(tm_encoder* e) {
   { int rc = enter_device(e->v); if (rc != TM_OK) return rc; }
   e->have = 0;
   e->hold.clear();
+  e->rhold.clear();
+  e->mode = 0;
+  e->host_pieces = 0;
   e->pending.clear();
   e->r_own = ~0ull;
   hipError_t he;
@@ -224,6 +335,61 @@ uint32_t tm_encoder_state(const tm_encoder* e) {
   return s;
 }
 
-uint64_t tm_encoder_device_bytes(const tm_encoder* e) { return e ? e->ws->device_bytes + SMALL_BYTES : 0; }
+uint64_t tm_encoder_device_bytes(const tm_encoder* e) {
+  if (!e) return 0;
+  return e->ws->device_bytes + SMALL_BYTES + (e->nws ? e->nws->device_bytes + piece_device_bytes(e->nws) : 0);
+}
+
+int tm_encoder_raw_supported(const tm_vocab* v) { return v && raw_refusal(v, false) == TM_OK ? 1 : 0; }
+
+int tm_encoder_feed_raw(tm_encoder* e, const uint8_t* raw, uint64_t n, uint32_t* tokens_out, uint64_t tokens_cap, uint64_t* n_tokens) {
+  { int rc = enc_usable(e); if (rc != TM_OK) return rc; }
+  { int rc = raw_refusal(e->v, true); if (rc != TM_OK) return rc; }
+  if (n && !raw) return set_error(TM_E_INVALID, "null argument");
+  if (n && e->mode == 1) return set_error(TM_E_INVALID, "this document is being fed as normalized text (tm_encoder_feed): one document is fed either raw or normalized");
+  if (n && !e->nws) { int rc = enc_make_nws(e); if (rc != TM_OK) return rc; }        // (nothing consumed, the encoder stays usable)
+  if (n && e->mode == 0) { e->mode = 2; e->host_pieces = 0; }
+  uint64_t written = 0, pos = 0;
+  while (pos < n) {
+    // the text at hand is rhold + raw[pos, n); the cut lies in its first max_piece bytes
+    const uint64_t held = e->rhold.size(), window = std::min<uint64_t>(n - pos, e->max_piece - held);
+    uint64_t take = 0;                                   // bytes of raw[pos ..) in front of the cut
+    for (uint64_t i = window; i > 0; i--) if (raw[pos + i - 1] == '\n') { take = i; break; }
+    bool cut = take > 0;
+    if (!cut && held + window == e->max_piece) {        // a line of a whole piece: behind its last separator, in the new bytes or in the held ones
+      for (uint64_t i = window; i > 0 && !cut; i--) if (fallback_cut(raw[pos + i - 1])) { take = i; cut = true; }
+      if (!cut) {
+        uint64_t h = held;
+        while (h > 0 && !fallback_cut(e->rhold[h - 1])) h--;
+        if (h == 0) {
+          e->failed = true;
+          return set_error(TM_E_LIMIT, "a line of more than max_piece_bytes without a separator: normalize it as a whole");
+        }
+        // the piece ends inside the held bytes: it goes by itself, the rest stays held
+        int rc = enc_raw_piece(e, e->rhold.data(), h, tokens_out, tokens_cap, &written);
+        if (rc != TM_OK) { e->failed = true; return rc; }
+        e->rhold.erase(e->rhold.begin(), e->rhold.begin() + (ptrdiff_t)h);
+        continue;
+      }
+    }
+    if (!cut) {                                          // no cut yet (then window == n - pos): wait for more text
+      e->rhold.insert(e->rhold.end(), raw + pos, raw + pos + window);
+      pos += window;
+      continue;
+    }
+    int rc;
+    if (held) {
+      e->rhold.insert(e->rhold.end(), raw + pos, raw + pos + take);
+      rc = enc_raw_piece(e, e->rhold.data(), e->rhold.size(), tokens_out, tokens_cap, &written);
+      e->rhold.clear();
+    } else rc = enc_raw_piece(e, raw + pos, take, tokens_out, tokens_cap, &written);
+    pos += take;
+    if (rc != TM_OK) { e->failed = true; return rc; }
+  }
+  return enc_hand_over(e, tokens_out, tokens_cap, written, n_tokens);
+}
+
+uint64_t tm_encoder_raw_held(const tm_encoder* e) { return e ? e->rhold.size() : 0; }
+uint32_t tm_encoder_host_pieces(const tm_encoder* e) { return e ? e->host_pieces : 0; }
 
 }  // extern "C"

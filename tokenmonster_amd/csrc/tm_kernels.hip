@@ -2595,6 +2595,27 @@ int make_workspace(const tm_vocab* v, uint64_t max_bytes, uint32_t max_docs, boo
   *out = b;
   return TM_OK;
 }
+// the normalizer's share of a workspace, for the raw pieces of the streaming encoder: the text buffer the normalizer packs into, the scans'
+// block sums, the totals / error words.  One document; everything else stays null (tm_batch_free and the normalizer do not mind).
+int make_piece_workspace(const tm_vocab* v, uint64_t max_bytes, hipStream_t st, tm_batch** out) {
+  *out = nullptr;
+  { int rc = enter_device(v); if (rc != TM_OK) return rc; }
+  auto* b = new tm_batch();
+  b->vocab = v;
+  b->max_bytes = max_bytes;
+  b->max_docs = 1;
+  b->max_segs = max_bytes / SEG + 2;
+  const uint64_t scan_blocks = (2 + max_bytes / 256 + 2 * SCAN_CH) / SCAN_CH + 64;
+  hipError_t e = hipSuccess;
+  if ((e = dalloc(b, &b->d_text, max_bytes + 256)) != hipSuccess || (e = dalloc(b, &b->d_scan_tmp, scan_blocks)) != hipSuccess || (e = dalloc(b, &b->d_totals, 8)) != hipSuccess ||
+      (e = hipMemsetAsync(b->d_totals, 0, 64, st)) != hipSuccess) {
+    tm_batch_free(b);
+    return hip_fail(e, "hipMalloc (piece workspace)");
+  }
+  b->d_error = reinterpret_cast<uint32_t*>(b->d_totals + 4);
+  *out = b;
+  return TM_OK;
+}
 }  // namespace tmh
 extern "C" {
 

@@ -1315,7 +1315,9 @@ static int prefilter(tm_batch* b, hipStream_t st, uint32_t norm_flag, const uint
   return TM_OK;
 }
 
-int tm_batch_normalize(tm_batch* b, void* stream) {
+// one_piece: the batch is a raw piece of the streaming encoder (tm_encoder.hip), which wants the normalized text and nothing of what the
+// tokenize pipeline needs behind it - no group tree for a long document (the workspace of such a batch has none)
+static int batch_normalize_impl(tm_batch* b, void* stream, bool one_piece) {
   if (!b) return set_error(TM_E_INVALID, "null argument");
   const tm_vocab* v = b->vocab;
   { int rc = enter_device(v); if (rc != TM_OK) return rc; }
@@ -1393,7 +1395,7 @@ int tm_batch_normalize(tm_batch* b, void* stream) {
       b->text_in_slabs = true;
       if (h_info[6] != 0 || (tm_debug_flags(-1) & 2048)) pack_text(b, st);        // a short piece inside a document (or the test hook): the packed text after all
       int rc = TM_OK;
-      if (h_info[1] > 0) {
+      if (h_info[1] > 0 && !one_piece) {
         std::vector<uint64_t> hb(nd), he(nd);
         if ((e = hipMemcpyAsync(hb.data(), b->d_nbegin, (size_t)nd * 8, hipMemcpyDeviceToHost, st)) != hipSuccess ||
             (e = hipMemcpyAsync(he.data(), b->d_nend, (size_t)nd * 8, hipMemcpyDeviceToHost, st)) != hipSuccess || (e = hipStreamSynchronize(st)) != hipSuccess) return hip_fail(e, "D2H ranges");
@@ -1517,7 +1519,7 @@ int tm_batch_normalize(tm_batch* b, void* stream) {
   b->nbytes = total;
   b->nseg = h_info[2];
   int rc = TM_OK;
-  if (h_info[1] > 0) {
+  if (h_info[1] > 0 && !one_piece) {
     std::vector<uint64_t> hb(nd), he(nd);
     if ((e = hipMemcpy(hb.data(), b->d_nbegin, (size_t)nd * 8, hipMemcpyDeviceToHost)) != hipSuccess ||
         (e = hipMemcpy(he.data(), b->d_nend, (size_t)nd * 8, hipMemcpyDeviceToHost)) != hipSuccess) return hip_fail(e, "D2H ranges");
@@ -1526,6 +1528,8 @@ int tm_batch_normalize(tm_batch* b, void* stream) {
   if (trace) fprintf(stderr, "[tm_batch_normalize] summaries %.2f ms, device pass + host fallback (%u docs) %.2f ms, info %.2f ms\n", t1 - t0, nf, t2 - t1, now() - t2);
   return rc;
 }
+
+int tm_batch_normalize(tm_batch* b, void* stream) { return batch_normalize_impl(b, stream, false); }
 
 }  // extern "C"
 namespace tmh {
@@ -1587,6 +1591,95 @@ int ring_enqueue_normalize(tm_batch* b, hipStream_t st, uint64_t seg_bound, cons
   launch_chunk_ctl(b, b->nseg, st);
   e = hipGetLastError();
   return e == hipSuccess ? TM_OK : hip_fail(e, "kernel launch");
+}
+
+// ---- the streaming encoder's raw pieces (tm_encoder.hip) ----------------------------------------------------------------------------------------
+// A raw piece is ONE document of the encoder's normalizer workspace.  piece_reserve grows every buffer the normalizer (and the filter pass in
+// front of it) takes for a piece of max_raw bytes, once, so that no later piece allocates; piece_device_bytes is what those buffers hold.
+int piece_reserve(tm_batch* b, uint64_t max_raw, hipStream_t st) {
+  const uint32_t norm_flag = b->vocab->host.norm_flag;
+  int rc = raw_prepare(b, max_raw, 1, (max_raw + PIECE - 1) / PIECE, st);
+  if (rc != TM_OK) return rc;
+  if (!(norm_flag & ~3u)) return TM_OK;
+  hipError_t e;
+  if ((e = grow(&b->d_rawf, &b->rawf_cap, max_raw + (uint64_t)PF_GAP + 256)) != hipSuccess) return hip_fail(e, "hipMalloc (filtered text)");
+  if (!b->d_rawf_off) {
+    b->rawf_docs_cap = 17;
+    if ((e = hipMalloc((void**)&b->d_rawf_off, b->rawf_docs_cap * 16)) != hipSuccess || (e = hipMalloc((void**)&b->d_pf_doc, b->rawf_docs_cap * sizeof(PfDoc))) != hipSuccess)
+      return hip_fail(e, "hipMalloc (filtered documents)");
+  }
+  if (max_raw > PF_WHOLE) {
+    uint8_t* pp = (uint8_t*)b->d_pf_piece; uint64_t cap = b->pf_piece_cap;
+    if ((e = grow(&pp, &cap, (pf_spans(max_raw) + 1) * sizeof(PfPiece))) != hipSuccess) return hip_fail(e, "hipMalloc (filter pass)");
+    b->d_pf_piece = pp; b->pf_piece_cap = cap;
+  }
+  return TM_OK;
+}
+uint64_t piece_device_bytes(const tm_batch* b) {
+  const uint64_t docs = (uint64_t)b->raw_docs_cap + 2;
+  uint64_t n = b->raw_cap + docs * 57 + 24 + 64 + NM_TABLE_BYTES + b->piece_cap * 21 + 8 + b->slab_cap;
+  if (b->d_rawf) n += b->rawf_cap + b->rawf_docs_cap * (16 + sizeof(PfDoc)) + b->pf_piece_cap;
+  if (b->vocab->host.norm_flag & 4u) n += (uint64_t)NM_TWO_SIZE * 4;      // (the accent table: made by the first piece's filter pass)
+  return n;
+}
+int piece_normalize_on(tm_batch* b, hipStream_t st) { return batch_normalize_impl(b, st, true); }
+
+// The normalized bytes [from, from + n) of the piece go to dst: from the slabs (a wavefront per slab, which takes what of its piece lies in the
+// range) or, where the normalizer has packed the text, from there (a wavefront per 2 KiB of the range).  Neither end is aligned - dst lies
+// behind the look-ahead the encoder carries, a portion begins in mid-piece -, so a run is staged in LDS: 16-byte loads from the aligned chunks
+// that hold it, 16-byte stores to the aligned chunks of dst, each made of two aligned LDS reads shifted against each other; the up to 15
+// bytes in front of and behind dst's aligned part go byte by byte.
+constexpr int EP_STAGE = SLAB / 16 + 5;
+__global__ __launch_bounds__(256) void k_enc_pack(const uint8_t* __restrict__ slab, const uint32_t* __restrict__ piece_len, const uint64_t* __restrict__ piece_off,
+                                                  const uint8_t* __restrict__ text, uint64_t nruns, uint64_t from, uint64_t n, uint8_t* __restrict__ dst) {
+  __shared__ uint4 stage[4][EP_STAGE];
+  const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const uint64_t k = (uint64_t)blockIdx.x * 4 + w;
+  const uint8_t* src = nullptr;
+  uint8_t* out = nullptr;
+  uint32_t len = 0;
+  if (k < nruns) {
+    if (slab) {
+      const uint64_t off = piece_off[k], a = off > from ? off : from, z = off + piece_len[k] < from + n ? off + piece_len[k] : from + n;
+      if (a < z) { src = slab + k * (uint64_t)SLAB + (a - off); out = dst + (a - from); len = (uint32_t)(z - a); }
+    } else {
+      const uint64_t a = k * (uint64_t)SLAB;
+      if (a < n) { src = text + from + a; out = dst + a; len = (uint32_t)(n - a < (uint64_t)SLAB ? n - a : (uint64_t)SLAB); }
+    }
+  }
+  const uint32_t sa = (uint32_t)(reinterpret_cast<uintptr_t>(src) & 15u);
+  const uint32_t nch = len ? (sa + len + 15u) / 16u : 0u;                    // <= (15 + SLAB + 15) / 16 < EP_STAGE - 2
+  const uint4* s16 = reinterpret_cast<const uint4*>(src - sa);
+  for (uint32_t c = lane; c < nch; c += 64u) stage[w][c] = s16[c];
+  __syncthreads();
+  const uint8_t* img = reinterpret_cast<const uint8_t*>(stage[w]) + sa;      // the run as it lies in LDS
+  uint32_t da = (16u - (uint32_t)(reinterpret_cast<uintptr_t>(out) & 15u)) & 15u;
+  if (da > len) da = len;
+  if (lane < da) out[lane] = img[lane];
+  const uint32_t body = (len - da) / 16u;
+  const uint32_t m = (sa + da) & 15u, base = (sa + da) / 16u, mw = m >> 2, sh = (m & 3u) * 8u;
+  for (uint32_t c = lane; c < body; c += 64u) {
+    const uint4 A = stage[w][base + c], B = stage[w][base + c + 1];
+    // the five dwords that hold the sixteen bytes from byte m of A on
+    const uint32_t d0 = mw == 0 ? A.x : mw == 1 ? A.y : mw == 2 ? A.z : A.w, d1 = mw == 0 ? A.y : mw == 1 ? A.z : mw == 2 ? A.w : B.x,
+                   d2 = mw == 0 ? A.z : mw == 1 ? A.w : mw == 2 ? B.x : B.y, d3 = mw == 0 ? A.w : mw == 1 ? B.x : mw == 2 ? B.y : B.z,
+                   d4 = mw == 0 ? B.x : mw == 1 ? B.y : mw == 2 ? B.z : B.w;
+    uint4 q;
+    q.x = (uint32_t)((((uint64_t)d1 << 32) | d0) >> sh); q.y = (uint32_t)((((uint64_t)d2 << 32) | d1) >> sh);
+    q.z = (uint32_t)((((uint64_t)d3 << 32) | d2) >> sh); q.w = (uint32_t)((((uint64_t)d4 << 32) | d3) >> sh);
+    *reinterpret_cast<uint4*>(out + da + 16u * c) = q;
+  }
+  const uint32_t t0 = da + body * 16u;
+  if (t0 + lane < len) out[t0 + lane] = img[t0 + lane];                      // (fewer than 16 bytes)
+}
+// b: the encoder's normalizer workspace behind piece_normalize_on; [from, from + n) lies inside its normalized text
+void launch_enc_pack(const tm_batch* b, uint64_t from, uint64_t n, uint8_t* dst, hipStream_t st) {
+  if (!n) return;
+  if (b->text_in_slabs) TM_LAUNCH(k_enc_pack, (uint32_t)((b->slab_pieces + 3) / 4), 256, 0, st, b->d_slab, b->d_piece_len, b->d_piece_off, nullptr, b->slab_pieces, from, n, dst);
+  else {
+    const uint64_t runs = (n + SLAB - 1) / SLAB;
+    TM_LAUNCH(k_enc_pack, (uint32_t)((runs + 3) / 4), 256, 0, st, nullptr, nullptr, nullptr, b->d_text, runs, from, n, dst);
+  }
 }
 }  // namespace tmh
 extern "C" {

@@ -336,6 +336,16 @@ uint32_t* score_error_device(tm_dataset* d);
 int score_finish_device(const tm_vocab* v, tm_dataset* d, hipStream_t st);
 // tm_norm.hip
 int batch_upload_raw_on(tm_batch* b, const uint8_t* raw, const uint64_t* raw_offsets, uint32_t ndocs, hipStream_t st);
+// the streaming encoder's raw pieces (tm_encoder.hip): a workspace that holds what the normalizer needs and nothing of the tokenizer's
+// (make_piece_workspace, tm_kernels.hip: max_bytes bounds the NORMALIZED size of a piece), every buffer a piece of max_raw bytes takes grown once
+// (piece_reserve) and counted (piece_device_bytes); then per piece batch_upload_raw_on of ONE document and piece_normalize_on - tm_batch_normalize
+// without the group tree, nothing on the NULL stream - after which b->nbytes normalized bytes lie in the slabs or packed in d_text, and
+// launch_enc_pack (k_enc_pack) copies a range of them to `dst`, device to device
+int make_piece_workspace(const tm_vocab* v, uint64_t max_bytes, hipStream_t st, tm_batch** out);
+int piece_reserve(tm_batch* b, uint64_t max_raw, hipStream_t st);
+uint64_t piece_device_bytes(const tm_batch* b);
+int piece_normalize_on(tm_batch* b, hipStream_t st);
+void launch_enc_pack(const tm_batch* b, uint64_t from, uint64_t n, uint8_t* dst, hipStream_t st);
 // tm_normalize.cpp
 bool normalize_supported(uint32_t capcode, uint32_t norm_flag);
 bool normalize_on_device(uint32_t capcode, uint32_t norm_flag);

@@ -273,6 +273,22 @@ class Vocab:
         parts = [p for p in parts if p.size] + [last]
         return (np.concatenate(parts) if len(parts) > 1 else last), missing
 
+    def encoder_raw_supported(self):
+        """whether Encoder.feed_raw takes this vocabulary's raw text (capcode 0 or 2, none of the flags quotemarks, trim, leadingspace)"""
+        return bool(N.lib.tm_encoder_raw_supported(self._h))
+
+    def tokenize_raw_stream(self, pieces, max_piece_bytes=0):
+        """an iterable of pieces of ONE raw document, cut anywhere -> (ids u32, missing): tokenize of the whole text normalized at once,
+        with device memory that depends on max_piece_bytes (0 = 32 MiB) only"""
+        enc = self.encoder(max_piece_bytes)
+        try:
+            parts = [enc.feed_raw(p) for p in pieces]
+            last, missing = enc.finish()
+        finally:
+            enc.close()
+        parts = [p for p in parts if p.size] + [last]
+        return (np.concatenate(parts) if len(parts) > 1 else last), missing
+
     def count_packed(self, text, offsets):
         """Count (go :971 / :1281): b-branches count once (quirk Q2) -> (counts u64[D], missing u32[D])"""
         text = N.as_u8(text)
@@ -382,7 +398,9 @@ class Decoder:
 class Encoder:
     """streaming encoder (tm_encoder_*): feed() the normalized text of ONE document in pieces of any size and get the ids that are final
     so far; finish() says the text ends and returns (remaining ids, missing) - all ids together are those of the whole document tokenized
-    at once, however it was cut.  Raw text must be normalized first (Vocab.normalize): the normalizer has state of its own across a cut."""
+    at once, however it was cut.  feed_raw() takes the document's RAW text instead (one document goes through one of the two): the library
+    cuts it behind line feeds, where the normalizer has no state, and keeps what lies behind the last one (raw_held) until more text or
+    finish() comes.  Vocabularies with the flags quotemarks, trim or leadingspace, or capcode 1, are normalized whole (Vocab.encoder_raw_supported)."""
 
     def __init__(self, vocab, max_piece_bytes=0):
         self._vocab = vocab
@@ -413,6 +431,20 @@ class Encoder:
     def feed(self, data):
         d = N.as_u8(data)
         return self._ids(lambda out, cap, n: N.lib.tm_encoder_feed(self._h, N.ptr(d), d.size, out, cap, n), d.size // 2 + 256)
+
+    def feed_raw(self, data):
+        d = N.as_u8(data)
+        return self._ids(lambda out, cap, n: N.lib.tm_encoder_feed_raw(self._h, N.ptr(d), d.size, out, cap, n), d.size // 2 + 256)
+
+    @property
+    def raw_held(self):
+        """raw bytes kept on the host behind the last safe cut"""
+        return int(N.lib.tm_encoder_raw_held(self._h))
+
+    @property
+    def host_pieces(self):
+        """raw pieces of the current (after finish: the last) document that the host normalizer took"""
+        return int(N.lib.tm_encoder_host_pieces(self._h))
 
     def finish(self):
         missing = C.c_uint32()
