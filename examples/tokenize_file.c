@@ -1,10 +1,11 @@
 /* tokenize_file.c — the C ABI of libtokenmonster_hip.so from plain C (what the cgo stub of INTEGRATION.md binds).
  *
- *   tokenize_file <file.vocab> <text file> [--lines]
+ *   tokenize_file <file.vocab> <text file> [--lines] [--rows L]
  *
  * Tokenizes the file (already normalized bytes, go/tokenmonster.go:963) as one document — or, with --lines, every
  * line as its own document, the batch shape of tokenmonsterserver job 1 — and prints the ids of each document on one
- * line.  Needs an MI355X: without a usable device every call fails with TM_E_NODEVICE, there is no CPU path. */
+ * line.  With --rows L the documents are tokenized on a device-resident batch instead and laid out as rows of L ids (tm_batch_collate:
+ * cut or padded with the id one past the vocabulary's last, int32) straight into page-locked host memory.  Needs an MI355X: without a usable device every call fails with TM_E_NODEVICE, there is no CPU path. */
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -26,7 +27,12 @@ static uint8_t* slurp(const char* path, size_t* n) {
 
 int main(int argc, char** argv) {
   if (argc < 3) { fprintf(stderr, "usage: %s <file.vocab> <text file> [--lines]\n", argv[0]); return 2; }
-  const int by_line = argc > 3 && strcmp(argv[3], "--lines") == 0;
+  int by_line = 0;
+  uint32_t row_len = 0;
+  for (int a = 3; a < argc; a++) {
+    if (strcmp(argv[a], "--lines") == 0) by_line = 1;
+    else if (strcmp(argv[a], "--rows") == 0 && a + 1 < argc) row_len = (uint32_t)strtoul(argv[++a], NULL, 10);
+  }
   size_t nv, nt;
   uint8_t* vfile = slurp(argv[1], &nv);
   uint8_t* text = slurp(argv[2], &nt);
@@ -46,6 +52,27 @@ int main(int argc, char** argv) {
       }
   } else {
     offsets[++ndocs] = nt;
+  }
+
+  if (row_len) {
+    /* the fixed-shape form: ids stay on the device after the run, the collate kernel writes [ndocs, row_len] rows where the caller wants them */
+    tm_batch* batch = NULL;
+    const tm_collate how = {0, ndocs, row_len, 4, tm_vocab_n_ids(vocab), TM_NONE, TM_NONE, 0};
+    int32_t* rows = (int32_t*)tm_host_alloc((size_t)ndocs * row_len * sizeof *rows);
+    uint32_t* lengths = (uint32_t*)tm_host_alloc(ndocs * sizeof *lengths);
+    if (!rows || !lengths || tm_batch_create(vocab, nt + 16, ndocs, &batch) != TM_OK || tm_batch_upload(batch, text, offsets, ndocs) != TM_OK ||
+        tm_batch_run(batch, NULL) != TM_OK || tm_batch_collate(batch, &how, NULL, rows, NULL, lengths) != TM_OK ||
+        tm_batch_totals(batch, NULL, NULL) != TM_OK) {          /* (collate is asynchronous on its stream - here the run's: this waits for it) */
+      fprintf(stderr, "collate: %s\n", tm_last_error());
+      return 1;
+    }
+    for (uint32_t d = 0; d < ndocs; d++) {
+      for (uint32_t i = 0; i < row_len; i++) printf(i ? " %d" : "%d", rows[(size_t)d * row_len + i]);
+      printf("   (%u)\n", lengths[d]);
+    }
+    tm_batch_free(batch); tm_host_free(rows); tm_host_free(lengths); tm_vocab_free(vocab);
+    free(offsets); free(text); free(vfile);
+    return 0;
   }
 
   /* worst case is two ids per byte (a forward delete before every token); TM_E_NOSPACE would report the real need */

@@ -277,6 +277,69 @@ func (b *HipBatch) DecodedText(ndocs int, capacity uint64) ([]byte, []uint64, er
 	}
 }
 
+// ---- fixed-shape id tensors on the device (tm_batch_collate / tm_batch_pack / tm_batch_load_ids) ------------------------------------------------
+// The outputs are device pointers or page-locked host memory (HipHostBuffer); stream is a hipStream_t (nil: the default stream).
+
+// HipCollate is tm_collate: which documents of the last run, the row length, the width of an id and the special ids (HipNone: none).
+type HipCollate struct {
+	FirstDoc, Docs   uint32
+	RowLen, IdBytes  uint32
+	Pad, Bos, Eos    uint32
+	PadLeft, KeepTail bool
+}
+
+const HipNone = uint32(C.TM_NONE)
+
+func (c HipCollate) c() C.tm_collate {
+	var flags C.uint32_t
+	if c.PadLeft {
+		flags |= C.TM_COLLATE_PAD_LEFT
+	}
+	if c.KeepTail {
+		flags |= C.TM_COLLATE_KEEP_TAIL
+	}
+	return C.tm_collate{first_doc: C.uint32_t(c.FirstDoc), ndocs: C.uint32_t(c.Docs), row_len: C.uint32_t(c.RowLen), id_bytes: C.uint32_t(c.IdBytes),
+		pad_id: C.uint32_t(c.Pad), bos_id: C.uint32_t(c.Bos), eos_id: C.uint32_t(c.Eos), flags: flags}
+}
+
+// Collate lays one document out per row: ids[Docs * RowLen] of IdBytes each, mask (may be nil) a byte per id, lengths (may be nil) a uint32 per row.
+func (b *HipBatch) Collate(how HipCollate, stream, ids, mask, lengths unsafe.Pointer) error {
+	h := how.c()
+	_, err := locked(func() C.int {
+		return C.tm_batch_collate(b.h, &h, stream, ids, (*C.uint8_t)(mask), (*C.uint32_t)(lengths))
+	})
+	return err
+}
+
+// PackRows is the number of rows Pack writes for these documents.
+func (b *HipBatch) PackRows(how HipCollate) (uint64, error) {
+	h := how.c()
+	var rows C.uint64_t
+	_, err := locked(func() C.int { return C.tm_batch_pack_rows(b.h, &h, &rows) })
+	return uint64(rows), err
+}
+
+// Pack cuts the EOS-separated stream of the documents into rows of RowLen: ids[rows * RowLen], docIndex and position (may be nil) a uint32 per id.
+// With rowsCap too small nothing is written and the rows needed are returned.
+func (b *HipBatch) Pack(how HipCollate, stream unsafe.Pointer, rowsCap uint64, ids, docIndex, position unsafe.Pointer) (uint64, error) {
+	h := how.c()
+	rc, err := locked(func() C.int {
+		return C.tm_batch_pack(b.h, &h, stream, C.uint64_t(rowsCap), ids, (*C.uint32_t)(docIndex), (*C.uint32_t)(position))
+	})
+	if err == nil && rc == C.TM_E_NOSPACE {
+		return b.PackRows(how)
+	}
+	return 0, err
+}
+
+// LoadIds makes the rows of a [nrows, rowLen] tensor of ids the documents of the batch, as a run would have left them (Decode, Download follow).
+func (b *HipBatch) LoadIds(rows unsafe.Pointer, nrows, rowLen, idBytes int, lengths unsafe.Pointer, pad, bos, eos uint32, stream unsafe.Pointer) error {
+	_, err := locked(func() C.int {
+		return C.tm_batch_load_ids(b.h, rows, C.uint32_t(nrows), C.uint32_t(rowLen), C.uint32_t(idBytes), (*C.uint32_t)(lengths), C.uint32_t(pad), C.uint32_t(bos), C.uint32_t(eos), stream)
+	})
+	return err
+}
+
 // ---- the host normalizer (every flag; what the device hands over to, and what Normalize of go/tokenmonster.go:953 does) ------------------------
 
 func HipNormalize(data []byte, capcode, normFlag uint8) ([]byte, error) {

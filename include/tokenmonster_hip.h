@@ -259,6 +259,52 @@ int tm_batch_decode(tm_batch* b, int raw, void* stream, uint64_t* decoded_bytes,
 int tm_batch_decode_timed(tm_batch* b, int raw, void* stream, uint64_t* decoded_bytes, uint32_t* host_docs, float* ms);
 int tm_batch_decoded_download(tm_batch* b, uint8_t* out, uint64_t out_cap, uint64_t* out_offsets);
 
+/* ---- fixed-shape id tensors on the device: collate, pack, and ids back in ------------------------------------------------------------- */
+/* What a model beside this library in the same process wants of a batch: [rows, L] integer tensors in HBM instead of the ragged ids, and
+ * the way back from a [rows, L] tensor of generated ids to text - without an id crossing the host link.  No counterpart in the reference
+ * (its callers collate on the host).  Output pointers are device pointers (the storage of a torch tensor, a slice of one: any alignment
+ * that is a multiple of the element size gets 16-byte stores between an unaligned head and tail) or page-locked host pointers from
+ * tm_host_alloc.  EVERY element of every output row is written: the caller passes uninitialized memory.  The calls are asynchronous on
+ * `stream` unless stated otherwise; tm_batch_collate and tm_batch_pack first wait for the batch's last run as tm_batch_decode does (the
+ * ids are all there, the emit stage repeated if its buffer was too small) and fail with TM_E_INVALID on a batch that holds no ids (no
+ * completed tm_batch_run or tm_batch_load_ids since its last upload).
+ * tm_collate: the documents first_doc .. first_doc + ndocs - 1 of the last run (beyond the run: TM_E_INVALID), rows of row_len ids of
+ * id_bytes 2, 4 or 8 bytes each, little-endian (8: int64 as torch wants it; 2 with a vocabulary of more than 65 536 ids or a special id
+ * >= 65 536: TM_E_INVALID).  pad_id must be given; bos_id / eos_id: TM_NONE = no such special.  Every argument error is TM_E_INVALID. */
+#define TM_COLLATE_PAD_LEFT 1u
+#define TM_COLLATE_KEEP_TAIL 2u
+typedef struct tm_collate {
+  uint32_t first_doc, ndocs;   /* documents of the last run to lay out (ndocs == rows in row mode) */
+  uint32_t row_len, id_bytes;  /* L; 2, 4 or 8 */
+  uint32_t pad_id, bos_id, eos_id;   /* TM_NONE: no such special (pad_id must be given) */
+  uint32_t flags;
+} tm_collate;
+/* One document per row: row r = [bos] content [eos], then pad_id up to row_len - on the left under TM_COLLATE_PAD_LEFT.  content: the
+ * document's ids cut to row_len - (number of specials given): its head, under TM_COLLATE_KEEP_TAIL its tail; the specials are always
+ * there (row_len smaller than their number: TM_E_INVALID).  ids_out[ndocs * row_len] elements of id_bytes; mask_out (may be NULL)
+ * [ndocs * row_len] bytes, 1 on an entry and 0 on padding; lengths_out (may be NULL) [ndocs]: entries of a row, specials included. */
+int tm_batch_collate(tm_batch* b, const tm_collate* how, void* stream,
+                     void* ids_out, uint8_t* mask_out, uint32_t* lengths_out);
+/* The pre-training form: the stream ids(first_doc) [eos] ids(first_doc + 1) [eos] ... (no separator with eos_id == TM_NONE: an empty
+ * document then leaves no trace; bos_id and flags are not used) cut into rows of row_len, the last one filled up with pad_id.
+ * tm_batch_pack_rows: the rows that takes, ceil(stream length / row_len) (synchronizes like tm_batch_totals).  tm_batch_pack writes them:
+ * ids_out[rows * row_len]; doc_index_out (may be NULL) the document of every position, counted from first_doc, 0xFFFFFFFF on padding;
+ * position_out (may be NULL) its index inside the document, the separator being the document's last position, 0 on padding.  rows_cap
+ * smaller than the rows needed: TM_E_NOSPACE, nothing is written, tm_last_error names the number (tm_batch_pack_rows returns it). */
+int tm_batch_pack_rows(tm_batch* b, const tm_collate* how, uint64_t* rows_needed);   /* synchronizes like tm_batch_totals */
+int tm_batch_pack(tm_batch* b, const tm_collate* how, void* stream, uint64_t rows_cap,
+                  void* ids_out, uint32_t* doc_index_out, uint32_t* position_out);
+/* The reverse: rows[nrows * row_len] ids of id_bytes each (device or page-locked memory, as above) become the batch's ragged ids and
+ * offsets, one document per row, and the batch is in the state a run leaves it in - ndocs = nrows, ids, offsets, totals, missing = 0 - so
+ * that tm_batch_decode, tm_batch_decoded_download, tm_batch_download and tm_batch_totals (and the two calls above) work on it.  What of a
+ * row counts, with pad_id / bos_id / eos_id TM_NONE = not given: a leading run of pad_id is skipped (left padding); from there the row
+ * extends over lengths[r] entries (device or page-locked, as tm_batch_collate writes them; NULL: to the row's end); one leading bos_id
+ * is skipped; the ids end in front of the first eos_id inside that extent.  Without lengths and eos_id a row's right padding counts as
+ * ids.  Ids >= tm_vocab_n_ids pass through (the decoder skips them).  May grow the batch's id buffer (then it waits for the device);
+ * nrows > max_docs of tm_batch_create: TM_E_LIMIT.  Lengths, a scan of them (the k_scan_* kernels of the run) and a gather, all on `stream`. */
+int tm_batch_load_ids(tm_batch* b, const void* rows, uint32_t nrows, uint32_t row_len, uint32_t id_bytes,
+                      const uint32_t* lengths, uint32_t pad_id, uint32_t bos_id, uint32_t eos_id, void* stream);
+
 /* Streaming Decoder (go/tokenmonster.go:552-700 NewDecoder / Decode / DecodeSerialized / Flush; server jobs 5-9): ids arrive a few
  * at a time, a call returns the text that is COMPLETE so far; the bytes of a character that is not (a token may end in the middle of a
  * UTF-8 sequence) and the state of the capcode decoder are carried to the next call.  Per-connection host state: the gather of a

@@ -77,7 +77,11 @@ SIGNATURES = {
     "tm_batch_decode": (C.c_int, [vp, C.c_int, vp, u64p, u32p]),
     "tm_batch_decode_timed": (C.c_int, [vp, C.c_int, vp, u64p, u32p, f32p]),
     "tm_batch_decoded_download": (C.c_int, [vp, vp, C.c_uint64, vp]),
-    "tm_decoder_new": (C.c_int, [vp, C.POINTER(vp)]),
+    "tm_batch_collate": (C.c_int, [vp, vp, vp, vp, vp, vp]),
+    "tm_batch_pack_rows": (C.c_int, [vp, vp, u64p]),
+    "tm_batch_pack": (C.c_int, [vp, vp, vp, C.c_uint64, vp, vp, vp]),
+    "tm_batch_load_ids": (C.c_int, [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp]),
+    "tm_decoder_new":(C.c_int, [vp, C.POINTER(vp)]),
     "tm_decoder_free": (None, [vp]),
     "tm_decoder_decode": (C.c_int, [vp, vp, C.c_uint64, vp, C.c_uint64, u64p]),
     "tm_decoder_decode_serialized": (C.c_int, [vp, vp, C.c_uint64, C.c_uint32, vp, C.c_uint64, u64p]),

@@ -1,0 +1,410 @@
+// tm_collate.hip — fixed-shape id tensors from the ragged ids a batch holds, and back: tm_batch_collate (one document per row, padded or
+// truncated, BOS / EOS, mask, lengths), tm_batch_pack (one EOS-separated stream cut into rows, with document numbers and positions) and
+// tm_batch_load_ids (a [rows, L] tensor of ids -> the batch's ragged ids and offsets, ready for tm_batch_decode).
+//
+// All three are streaming kernels: no table, no LDS, a few bytes read per byte written.  Every output is treated as ONE flat run of
+// elements (a [rows, L] tensor is contiguous): the elements in front of the first 16-byte boundary and behind the last whole 16 bytes are
+// stored one by one, everything between as 16-byte vectors, one per work-item, so that a wavefront writes 1 KiB of consecutive bytes per
+// store instruction whatever L and the element size are.  A work-item finds the row (the document) of its first element once - a division,
+// or a binary search over the offsets - and steps to the next one when its vector crosses a row (document) end.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+
+#include "tm_pipeline.h"
+
+namespace tmh {
+
+// ---- a flat output of n elements of T ------------------------------------------------------------------------------------------------------
+// work-items [0, nvec): the 16-byte vector at element head + t * (16 / sizeof(T)); then `head` single elements in front and the single
+// elements behind the last vector.  A base that is not even a multiple of sizeof(T) has no vectors at all (head == n).
+struct Flat { uint64_t n, head, nvec; };
+static Flat flat_of(const void* out, uint64_t n, uint32_t elem) {
+  const uint64_t a = (uint64_t)reinterpret_cast<uintptr_t>(out);
+  Flat f{n, n, 0};
+  if (a % elem) return f;
+  const uint64_t mis = a & 15u;
+  f.head = std::min<uint64_t>(mis ? (16 - mis) / elem : 0, n);
+  f.nvec = (n - f.head) / (16 / elem);
+  return f;
+}
+static uint64_t flat_items(const Flat& f, uint32_t elem) { return f.n - f.nvec * (16 / elem) + f.nvec; }
+
+template <typename T>
+__device__ __forceinline__ bool flat_span(const Flat& f, uint64_t t, uint64_t& e0, uint32_t& cnt) {
+  constexpr uint32_t PER = 16 / sizeof(T);
+  if (t < f.nvec) { e0 = f.head + t * PER; cnt = PER; return true; }
+  uint64_t u = t - f.nvec;
+  cnt = 1;
+  if (u < f.head) { e0 = u; return true; }
+  u -= f.head;
+  const uint64_t tail0 = f.head + f.nvec * PER;
+  if (u < f.n - tail0) { e0 = tail0 + u; return true; }
+  return false;
+}
+template <typename T>
+__device__ __forceinline__ void flat_store(T* __restrict__ out, uint64_t e0, uint32_t cnt, const T* vals) {
+  constexpr uint32_t PER = 16 / sizeof(T);
+  if (cnt == PER) {
+    uint4 v;
+    __builtin_memcpy(&v, vals, 16);
+    *reinterpret_cast<uint4*>(out + e0) = v;          // (e0 is on a 16-byte boundary: flat_of)
+  } else {
+    out[e0] = vals[0];
+  }
+}
+
+// ---- k_collate_rows: one document per row ------------------------------------------------------------------------------------------------------
+struct CollateArgs {
+  const uint32_t* ids;        // the batch's ids
+  const uint64_t* toff;       // tok_offsets + first_doc
+  uint32_t rows, L, pad, bos, eos, flags;      // bos / eos: TM_NONE = none
+};
+// what row r holds: `len` entries [bos?] content [eos?] from column `lo` on, the content from ids[src]
+struct RowPlan { uint64_t src; uint32_t lo, len; };
+__device__ __forceinline__ RowPlan row_plan(const CollateArgs& a, uint64_t r) {
+  const uint64_t b0 = a.toff[r], b1 = a.toff[r + 1];
+  const uint32_t ns = (a.bos != TM_NONE ? 1u : 0u) + (a.eos != TM_NONE ? 1u : 0u);
+  const uint32_t m = (uint32_t)std::min<uint64_t>(b1 - b0, a.L - ns);            // (L >= ns: checked by the host)
+  RowPlan p;
+  p.src = (a.flags & TM_COLLATE_KEEP_TAIL) ? b1 - m : b0;
+  p.len = m + ns;
+  p.lo = (a.flags & TM_COLLATE_PAD_LEFT) ? a.L - p.len : 0u;
+  return p;
+}
+// MASK: the element is 1 inside the row's entries and 0 on padding (T = uint8_t); else the id.  lengths (ids launch only, may be null):
+// the first `rows` work-items write a row's length each.
+template <typename T, bool MASK>
+__global__ __launch_bounds__(256) void k_collate_rows(CollateArgs a, Flat f, T* __restrict__ out, uint32_t* __restrict__ lengths) {
+  constexpr uint32_t PER = 16 / sizeof(T);
+  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (!MASK && lengths && t < a.rows) lengths[t] = row_plan(a, t).len;
+  uint64_t e0;
+  uint32_t cnt;
+  if (!flat_span<T>(f, t, e0, cnt)) return;
+  uint64_t r;
+  uint32_t c;
+  if (f.n <= 0xFFFFFFFFull) { r = (uint32_t)e0 / a.L; c = (uint32_t)e0 - (uint32_t)r * a.L; }      // (a 64-bit division costs more than the store it is for)
+  else { r = e0 / a.L; c = (uint32_t)(e0 - r * a.L); }
+  RowPlan p = row_plan(a, r);
+  const uint32_t hb = a.bos != TM_NONE ? 1u : 0u;
+  T vals[PER];
+#pragma unroll
+  for (uint32_t k = 0; k < PER; k++) {
+    if (k < cnt) {
+      const uint32_t j = c - p.lo;                     // (wraps to a large number left of the entries)
+      uint32_t v;
+      if (MASK) v = j < p.len ? 1u : 0u;
+      else if (j >= p.len) v = a.pad;
+      else if (hb && j == 0) v = a.bos;
+      else if (a.eos != TM_NONE && j == p.len - 1) v = a.eos;
+      else v = a.ids[p.src + (j - hb)];
+      vals[k] = (T)v;
+      if (++c == a.L && k + 1 < cnt) { c = 0; r++; p = row_plan(a, r); }
+    } else {
+      vals[k] = 0;
+    }
+  }
+  flat_store<T>(out, e0, cnt, vals);
+}
+
+// ---- a position of a stream of documents -> its document ---------------------------------------------------------------------------------------------
+// key(d) = toff[d] - toff[0] + d * sep: where document d begins in the stream (sep = 1: every document is followed by a separator).  The
+// cursor holds the document d with key(d) <= p < key(d + 1) - for an empty document without separator there is no such p, it vanishes.
+struct DocCursor {
+  const uint64_t* toff;
+  uint32_t nd, sep, d;
+  uint64_t base, next;        // key(d), key(d + 1)
+  __device__ __forceinline__ uint64_t key(uint32_t k) const { return toff[k] - toff[0] + (uint64_t)k * sep; }
+  // p < key(nd) and key(from) <= p
+  __device__ __forceinline__ void seek(uint64_t p, uint32_t from) {
+    uint32_t lo = from, hi = nd;      // invariant: key(lo) <= p < key(hi)
+    while (hi - lo > 1) {
+      const uint32_t mid = lo + (hi - lo) / 2;
+      if (key(mid) <= p) lo = mid; else hi = mid;
+    }
+    d = lo; base = key(lo); next = key(lo + 1);
+  }
+  // the next position asked for is >= the last one: stay, or search the documents behind (never a walk: a run of empty documents is legal)
+  __device__ __forceinline__ void advance(uint64_t p) { if (p >= next) seek(p, d + 1); }
+};
+
+// ---- k_pack_stream: ids(doc0) [eos] ids(doc1) [eos] ... cut into rows -------------------------------------------------------------------------------------
+struct PackArgs {
+  const uint32_t* ids;
+  const uint64_t* toff;       // tok_offsets + first_doc
+  uint32_t nd, pad, eos;      // eos: TM_NONE = none
+  uint64_t stream_len;        // key(nd)
+};
+// WHAT: 0 = ids (T of 2, 4 or 8 bytes), 1 = doc_index, 2 = position (T = uint32_t)
+template <typename T, int WHAT>
+__global__ __launch_bounds__(256) void k_pack_stream(PackArgs a, Flat f, T* __restrict__ out) {
+  constexpr uint32_t PER = 16 / sizeof(T);
+  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  uint64_t e0;
+  uint32_t cnt;
+  if (!flat_span<T>(f, t, e0, cnt)) return;
+  const uint32_t sep = a.eos != TM_NONE ? 1u : 0u;
+  DocCursor cur{a.toff, a.nd, sep, 0, 0, 0};
+  if (e0 < a.stream_len) cur.seek(e0, 0);
+  T vals[PER];
+#pragma unroll
+  for (uint32_t k = 0; k < PER; k++) {
+    const uint64_t p = e0 + k;
+    uint32_t v = 0;
+    if (k < cnt) {
+      if (p >= a.stream_len) v = WHAT == 0 ? a.pad : WHAT == 1 ? 0xFFFFFFFFu : 0u;
+      else {
+        cur.advance(p);
+        const uint64_t pos = p - cur.base;
+        if (WHAT == 1) v = cur.d;
+        else if (WHAT == 2) v = (uint32_t)pos;
+        else v = (sep && p + 1 == cur.next) ? a.eos : a.ids[a.toff[cur.d] + pos];
+      }
+    }
+    vals[k] = (T)v;
+  }
+  flat_store<T>(out, e0, cnt, vals);
+}
+
+// ---- k_ids_from_rows: [rows, L] -> ragged ids ----------------------------------------------------------------------------------------------------
+struct LoadArgs {
+  const void* rows;
+  const uint32_t* lengths;    // may be null
+  uint32_t nrows, L, pad, bos, eos;      // TM_NONE = not given
+};
+// One wavefront per row, lanes stride over its columns: the leading run of pad ids, one BOS, then the entries up to lengths[r] (if given) and
+// to the first EOS (if given) -> where the row's ids begin (col) and how many they are (ntok).  Work-item 0 leaves the batch's totals and
+// error word as a run leaves them (the id total comes from the scan behind this kernel).
+template <typename T>
+__global__ __launch_bounds__(256) void k_row_extents(LoadArgs a, uint32_t* __restrict__ ntok, uint32_t* __restrict__ col, uint32_t* __restrict__ missing,
+                                                     uint64_t* __restrict__ totals, uint32_t* __restrict__ error) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) { totals[0] = 0; totals[2] = 0; totals[3] = 0; *error = 0u; }
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint64_t r = (uint64_t)blockIdx.x * (blockDim.x / 64) + threadIdx.x / 64;
+  if (r >= a.nrows) return;                          // (the whole wavefront leaves)
+  const T* __restrict__ row = static_cast<const T*>(a.rows) + r * a.L;
+  uint32_t start = 0;
+  if (a.pad != TM_NONE) {
+    start = a.L;
+    for (uint32_t base = 0; base < a.L; base += 64) {
+      const uint32_t c = base + lane;
+      const unsigned long long m = __ballot(c < a.L && (uint64_t)row[c] != (uint64_t)a.pad);
+      if (m) { start = base + (uint32_t)__ffsll(m) - 1u; break; }
+    }
+  }
+  uint32_t end = a.L;
+  if (a.lengths) end = (uint32_t)std::min<uint64_t>((uint64_t)start + a.lengths[r], a.L);
+  if (a.bos != TM_NONE && start < end && (uint64_t)row[start] == (uint64_t)a.bos) start++;
+  if (a.eos != TM_NONE) {
+    for (uint32_t base = start; base < end; base += 64) {
+      const uint32_t c = base + lane;
+      const unsigned long long m = __ballot(c < end && (uint64_t)row[c] == (uint64_t)a.eos);
+      if (m) { end = base + (uint32_t)__ffsll(m) - 1u; break; }
+    }
+  }
+  if (lane == 0) { ntok[r] = end - start; col[r] = start; missing[r] = 0u; }
+}
+// the gather behind the scan: four ids per work-item, one 16-byte store into the batch's id buffer (which holds nrows * L + 4 ids at least;
+// the count is read from the device: toff[nrows])
+template <typename T>
+__global__ __launch_bounds__(256) void k_ids_from_rows(LoadArgs a, const uint64_t* __restrict__ toff, const uint32_t* __restrict__ col, uint32_t* __restrict__ out) {
+  const uint64_t e0 = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+  const uint64_t total = toff[a.nrows];
+  if (e0 >= total) return;
+  DocCursor cur{toff, a.nrows, 0u, 0, 0, 0};
+  cur.seek(e0, 0);
+  const T* __restrict__ rows = static_cast<const T*>(a.rows);
+  uint32_t vals[4];
+#pragma unroll
+  for (uint32_t k = 0; k < 4; k++) {
+    const uint64_t p = e0 + k;
+    uint32_t v = 0;
+    if (p < total) {
+      cur.advance(p);
+      v = (uint32_t)rows[(uint64_t)cur.d * a.L + col[cur.d] + (p - cur.base)];
+    }
+    vals[k] = v;
+  }
+  flat_store<uint32_t>(out, e0, 4, vals);
+}
+
+// ---- host side ----------------------------------------------------------------------------------------------------------------------------------------
+constexpr uint64_t COLLATE_MAX_ELEMS = 1ull << 36;       // elements of one output: keeps every grid below 2^31 workgroups
+
+static uint32_t grid_of(uint64_t items) { return (uint32_t)((items + 255) / 256); }
+static int launch_check() {
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? TM_OK : hip_fail(e, "kernel launch");
+}
+
+// the arguments both layouts share (ids_out: only that it is there)
+static int check_how(const tm_batch* b, const tm_collate* how, const void* ids_out, const char* who) {
+  if (!b || !how || !ids_out) return set_error(TM_E_INVALID, "%s: null argument", who);
+  if (how->id_bytes != 2 && how->id_bytes != 4 && how->id_bytes != 8) return set_error(TM_E_INVALID, "%s: id_bytes %u (2, 4 or 8)", who, how->id_bytes);
+  if (how->row_len == 0) return set_error(TM_E_INVALID, "%s: row_len 0", who);
+  if (how->pad_id == TM_NONE) return set_error(TM_E_INVALID, "%s: pad_id must be given", who);
+  if (how->flags & ~(TM_COLLATE_PAD_LEFT | TM_COLLATE_KEEP_TAIL)) return set_error(TM_E_INVALID, "%s: unknown flags %#x", who, how->flags);
+  if (how->id_bytes == 2) {
+    if (b->vocab->host.n_ids > 65536u) return set_error(TM_E_INVALID, "%s: two-byte ids with a vocabulary of %u ids", who, b->vocab->host.n_ids);
+    for (uint32_t s : {how->pad_id, how->bos_id, how->eos_id})
+      if (s != TM_NONE && s >= 65536u) return set_error(TM_E_INVALID, "%s: special id %u does not fit two bytes", who, s);
+  }
+  if (!b->has_output) return set_error(TM_E_INVALID, "%s: the batch holds no ids (no completed tm_batch_run or tm_batch_load_ids since the last upload)", who);
+  if ((uint64_t)how->first_doc + how->ndocs > b->ndocs)
+    return set_error(TM_E_INVALID, "%s: documents %u .. %llu of a run of %u", who, how->first_doc, (unsigned long long)how->first_doc + how->ndocs, b->ndocs);
+  return TM_OK;
+}
+
+template <typename T>
+static void launch_collate(const CollateArgs& a, void* ids_out, uint32_t* lengths_out, hipStream_t st) {
+  const Flat f = flat_of(ids_out, (uint64_t)a.rows * a.L, sizeof(T));
+  const uint64_t items = std::max<uint64_t>(flat_items(f, sizeof(T)), lengths_out ? a.rows : 0);
+  const auto kern = k_collate_rows<T, false>;
+  TM_LAUNCH(kern, grid_of(items), 256, 0, st, a, f, static_cast<T*>(ids_out), lengths_out);
+}
+template <typename T>
+static void launch_pack_ids(const PackArgs& a, void* ids_out, uint64_t n, hipStream_t st) {
+  const Flat f = flat_of(ids_out, n, sizeof(T));
+  const auto kern = k_pack_stream<T, 0>;
+  TM_LAUNCH(kern, grid_of(flat_items(f, sizeof(T))), 256, 0, st, a, f, static_cast<T*>(ids_out));
+}
+
+// stream length of the documents [first, first + nd) with `sep` separators each: two offsets from the device (synchronizes like tm_batch_totals)
+static int pack_stream_len(tm_batch* b, const tm_collate* how, uint64_t* stream_len) {
+  *stream_len = 0;
+  if (how->ndocs == 0) return TM_OK;
+  uint64_t lo = 0, hi = 0;
+  int rc = small_d2h(b, &lo, b->d_tok_offsets + how->first_doc, 8, b->last_stream);
+  if (rc == TM_OK) rc = small_d2h(b, &hi, b->d_tok_offsets + how->first_doc + how->ndocs, 8, b->last_stream);
+  if (rc == TM_OK) rc = small_sync(b, b->last_stream);
+  if (rc != TM_OK) return rc;
+  *stream_len = hi - lo + (how->eos_id != TM_NONE ? (uint64_t)how->ndocs : 0);
+  return TM_OK;
+}
+static int pack_rows(tm_batch* b, const tm_collate* how, const void* ids_out, const char* who, uint64_t* stream_len, uint64_t* rows) {
+  int rc = check_how(b, how, ids_out, who);
+  if (rc != TM_OK) return rc;
+  if ((rc = enter_device(b->vocab)) != TM_OK || (rc = ensure_output(b)) != TM_OK || (rc = pack_stream_len(b, how, stream_len)) != TM_OK) return rc;
+  *rows = (*stream_len + how->row_len - 1) / how->row_len;
+  if (*rows * how->row_len > COLLATE_MAX_ELEMS) return set_error(TM_E_LIMIT, "%s: %llu rows of %u ids in one call (split the documents)", who, (unsigned long long)*rows, how->row_len);
+  return TM_OK;
+}
+
+}  // namespace tmh
+
+using namespace tmh;
+
+extern "C" {
+
+int tm_batch_collate(tm_batch* b, const tm_collate* how, void* stream, void* ids_out, uint8_t* mask_out, uint32_t* lengths_out) {
+  int rc = check_how(b, how, ids_out, "tm_batch_collate");
+  if (rc != TM_OK) return rc;
+  const uint32_t ns = (how->bos_id != TM_NONE ? 1u : 0u) + (how->eos_id != TM_NONE ? 1u : 0u);
+  if (how->row_len < ns) return set_error(TM_E_INVALID, "tm_batch_collate: row_len %u holds no %u specials", how->row_len, ns);
+  if ((uint64_t)how->ndocs * how->row_len > COLLATE_MAX_ELEMS) return set_error(TM_E_LIMIT, "tm_batch_collate: %u rows of %u ids in one call (split the documents)", how->ndocs, how->row_len);
+  if ((rc = enter_device(b->vocab)) != TM_OK || (rc = ensure_output(b)) != TM_OK) return rc;      // (waits for the run: the ids are all there)
+  if (how->ndocs == 0) return TM_OK;
+  hipStream_t st = (hipStream_t)stream;
+  (void)hipGetLastError();
+  const CollateArgs a{b->d_out, b->d_tok_offsets + how->first_doc, how->ndocs, how->row_len, how->pad_id, how->bos_id, how->eos_id, how->flags};
+  if (how->id_bytes == 2) launch_collate<uint16_t>(a, ids_out, lengths_out, st);
+  else if (how->id_bytes == 4) launch_collate<uint32_t>(a, ids_out, lengths_out, st);
+  else launch_collate<uint64_t>(a, ids_out, lengths_out, st);
+  if (mask_out) {
+    const Flat f = flat_of(mask_out, (uint64_t)a.rows * a.L, 1);
+    const auto kern = k_collate_rows<uint8_t, true>;
+    TM_LAUNCH(kern, grid_of(flat_items(f, 1)), 256, 0, st, a, f, mask_out, (uint32_t*)nullptr);
+  }
+  return launch_check();
+}
+
+int tm_batch_pack_rows(tm_batch* b, const tm_collate* how, uint64_t* rows_needed) {
+  if (!rows_needed) return set_error(TM_E_INVALID, "tm_batch_pack_rows: null argument");
+  *rows_needed = 0;
+  uint64_t stream_len = 0;
+  return pack_rows(b, how, rows_needed, "tm_batch_pack_rows", &stream_len, rows_needed);
+}
+
+int tm_batch_pack(tm_batch* b, const tm_collate* how, void* stream, uint64_t rows_cap, void* ids_out, uint32_t* doc_index_out, uint32_t* position_out) {
+  uint64_t stream_len = 0, rows = 0;
+  int rc = pack_rows(b, how, ids_out, "tm_batch_pack", &stream_len, &rows);
+  if (rc != TM_OK) return rc;
+  if (rows > rows_cap) return set_error(TM_E_NOSPACE, "tm_batch_pack: rows_cap %llu < %llu rows required", (unsigned long long)rows_cap, (unsigned long long)rows);
+  if (rows == 0) return TM_OK;
+  hipStream_t st = (hipStream_t)stream;
+  (void)hipGetLastError();
+  const uint64_t n = rows * how->row_len;
+  const PackArgs a{b->d_out, b->d_tok_offsets + how->first_doc, how->ndocs, how->pad_id, how->eos_id, stream_len};
+  if (how->id_bytes == 2) launch_pack_ids<uint16_t>(a, ids_out, n, st);
+  else if (how->id_bytes == 4) launch_pack_ids<uint32_t>(a, ids_out, n, st);
+  else launch_pack_ids<uint64_t>(a, ids_out, n, st);
+  if (doc_index_out) {
+    const Flat f = flat_of(doc_index_out, n, 4);
+    const auto kern = k_pack_stream<uint32_t, 1>;
+    TM_LAUNCH(kern, grid_of(flat_items(f, 4)), 256, 0, st, a, f, doc_index_out);
+  }
+  if (position_out) {
+    const Flat f = flat_of(position_out, n, 4);
+    const auto kern = k_pack_stream<uint32_t, 2>;
+    TM_LAUNCH(kern, grid_of(flat_items(f, 4)), 256, 0, st, a, f, position_out);
+  }
+  return launch_check();
+}
+
+int tm_batch_load_ids(tm_batch* b, const void* rows, uint32_t nrows, uint32_t row_len, uint32_t id_bytes, const uint32_t* lengths, uint32_t pad_id,
+                      uint32_t bos_id, uint32_t eos_id, void* stream) {
+  if (!b || (nrows && !rows)) return set_error(TM_E_INVALID, "tm_batch_load_ids: null argument");
+  if (id_bytes != 2 && id_bytes != 4 && id_bytes != 8) return set_error(TM_E_INVALID, "tm_batch_load_ids: id_bytes %u (2, 4 or 8)", id_bytes);
+  if (nrows && row_len == 0) return set_error(TM_E_INVALID, "tm_batch_load_ids: row_len 0");
+  if (nrows && reinterpret_cast<uintptr_t>(rows) % id_bytes) return set_error(TM_E_INVALID, "tm_batch_load_ids: rows not aligned to id_bytes");
+  if (id_bytes == 2) {
+    if (b->vocab->host.n_ids > 65536u) return set_error(TM_E_INVALID, "tm_batch_load_ids: two-byte ids with a vocabulary of %u ids", b->vocab->host.n_ids);
+    for (uint32_t s : {pad_id, bos_id, eos_id})
+      if (s != TM_NONE && s >= 65536u) return set_error(TM_E_INVALID, "tm_batch_load_ids: special id %u does not fit two bytes", s);
+  }
+  if (nrows > b->max_docs) return set_error(TM_E_LIMIT, "tm_batch_load_ids: %u rows, workspace sized for %u documents", nrows, b->max_docs);
+  const uint64_t bound = (uint64_t)nrows * row_len;
+  if (bound > COLLATE_MAX_ELEMS) return set_error(TM_E_LIMIT, "tm_batch_load_ids: %u rows of %u ids in one call (split the rows)", nrows, row_len);
+  { int rc = enter_device(b->vocab); if (rc != TM_OK) return rc; }
+  hipError_t e;
+  hipStream_t st = (hipStream_t)stream;
+  if (bound + 4 > b->out_cap) {          // (the gather stores whole 16 bytes)
+    // what the last run left may still be read on its stream
+    if ((e = hipStreamSynchronize(b->last_stream)) != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
+    trace_grow("ids", (bound + 4) * 4);
+    (void)hipFree(b->d_out);
+    b->device_bytes -= b->out_cap * 4;
+    b->d_out = nullptr;
+    b->out_cap = 0;
+    const uint64_t cap = bound + bound / 4 + 1024;
+    if ((e = batch_alloc_bytes(b, (void**)&b->d_out, cap * 4)) != hipSuccess) return hip_fail(e, "hipMalloc output");
+    b->out_cap = cap;
+  }
+  (void)hipGetLastError();
+  b->has_output = false;
+  b->ndocs = nrows;
+  b->last_stream = st;
+  b->nbytes = 0; b->nseg = 0;
+  const LoadArgs a{rows, lengths, nrows, row_len, pad_id, bos_id, eos_id};
+  if (nrows == 0) {
+    if ((e = hipMemsetAsync(b->d_totals, 0, 40, st)) != hipSuccess || (e = hipMemsetAsync(b->d_tok_offsets, 0, 8, st)) != hipSuccess) return hip_fail(e, "hipMemsetAsync");
+    b->has_output = true;
+    return TM_OK;
+  }
+  const uint32_t g1 = (nrows + 3) / 4;
+  if (id_bytes == 2) TM_LAUNCH(k_row_extents<uint16_t>, g1, 256, 0, st, a, b->d_doc_ntok, b->d_doc_events, b->d_doc_missing, b->d_totals, b->d_error);
+  else if (id_bytes == 4) TM_LAUNCH(k_row_extents<uint32_t>, g1, 256, 0, st, a, b->d_doc_ntok, b->d_doc_events, b->d_doc_missing, b->d_totals, b->d_error);
+  else TM_LAUNCH(k_row_extents<uint64_t>, g1, 256, 0, st, a, b->d_doc_ntok, b->d_doc_events, b->d_doc_missing, b->d_totals, b->d_error);
+  scan_u32(b->d_doc_ntok, nrows, b->d_scan_tmp, b->d_totals + 1, b->d_tok_offsets, st);
+  const uint32_t g2 = grid_of((bound + 3) / 4);
+  if (id_bytes == 2) TM_LAUNCH(k_ids_from_rows<uint16_t>, g2, 256, 0, st, a, b->d_tok_offsets, b->d_doc_events, b->d_out);
+  else if (id_bytes == 4) TM_LAUNCH(k_ids_from_rows<uint32_t>, g2, 256, 0, st, a, b->d_tok_offsets, b->d_doc_events, b->d_out);
+  else TM_LAUNCH(k_ids_from_rows<uint64_t>, g2, 256, 0, st, a, b->d_tok_offsets, b->d_doc_events, b->d_out);
+  int rc = launch_check();
+  if (rc == TM_OK) b->has_output = true;
+  return rc;
+}
+
+}  // extern "C"

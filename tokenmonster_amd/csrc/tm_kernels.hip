@@ -2427,9 +2427,11 @@ int run_pipeline(tm_batch* b, hipStream_t st, bool timed, float* ms, bool emit) 
     for (auto& ev : b->ev) if ((e = hipEventCreate(&ev)) != hipSuccess) return hip_fail(e, "hipEventCreate");
     b->have_events = true;
   }
+  b->has_output = false;
   int rc = pipeline_match(b, st, timed ? b->ev : nullptr);
   if (rc == TM_OK) rc = pipeline_resolve(b, st, timed ? b->ev : nullptr, emit ? 2 : 1);
   if (rc != TM_OK) return rc;
+  b->has_output = emit;
   if (timed) {
     if ((e = hipEventSynchronize(b->ev[TM_NUM_KERNELS])) != hipSuccess) return hip_fail(e, "hipEventSynchronize");
     for (int k = 0; k < TM_NUM_KERNELS; k++) (void)hipEventElapsedTime(&ms[k], b->ev[k], b->ev[k + 1]);
@@ -2665,6 +2667,7 @@ int batch_upload_on(tm_batch* b, const uint8_t* text, const uint64_t* offsets, u
   else if (nbytes && (e = hipMemcpyAsync(b->d_text, text, nbytes, hipMemcpyHostToDevice, st)) != hipSuccess) return hip_fail(e, "H2D text");
   if (ndocs) { int rc = small_h2d(b, b->d_offsets, offsets, ((uint64_t)ndocs + 1) * 8, st); if (rc != TM_OK) return rc; }
   b->ndocs = ndocs;
+  b->has_output = false;
   b->nbytes = nbytes;
   b->nseg = nseg;
   b->d_doc_begin = b->d_offsets;

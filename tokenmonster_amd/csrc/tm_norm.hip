@@ -1196,6 +1196,7 @@ int raw_prepare(tm_batch* b, uint64_t nbytes, uint32_t ndocs, uint64_t npieces, 
   b->raw_bytes = nbytes;
   b->raw_docs = ndocs;
   b->raw_pieces = npieces;
+  b->has_output = false;
   return TM_OK;
 }
 

@@ -208,6 +208,7 @@ struct tm_batch {
   uint64_t h_fb_raw_cap = 0, h_fb_norm_cap = 0;
   uint32_t* d_out = nullptr;
   uint64_t out_cap = 0;
+  bool has_output = false;              // ids and offsets of a completed run (or of tm_batch_load_ids) lie in d_out / d_tok_offsets: what tm_batch_collate / tm_batch_pack ask for
   uint16_t* d_out16 = nullptr;          // set for the length of a launch: K4 writes two-byte ids here instead (a chunk of the ring, launch_emit)
   uint64_t out16_cap = 0;
   // a chunk of the host-to-host ring (tm_host.hip): what the host would have read back between the stages - the number of segments the normalizer
