@@ -117,6 +117,43 @@ func (hv *HipVocab) TokenizeSerializedPinned(text *HipHostBuffer, offsets []uint
 	return byteOff, missing[:n], uint8(used), byteOff[n], nil
 }
 
+// HipDocumentStats is what TokenizeDocumentPinned reports beside the ids (tm_document_stats).
+type HipDocumentStats struct {
+	Pieces, Slots          int
+	NormalizedBytes        uint64
+	HostPieces             int
+	HostNormalized         bool
+	DeviceBytes            uint64
+	InputPinned, OutPinned bool
+}
+
+// TokenizeDocumentPinned tokenizes ONE large document that is in hand as a whole (tm_tokenize_document): its pieces of pieceBytes (0 = 32 MiB)
+// run through `slots` (0 = 3) device workspaces at once, so that text goes in and ids come out behind the kernels.  raw: the text is raw
+// UTF-8 and is normalized piece by piece; otherwise it is already normalized.  The serialized ids of Vocab.Tokenize of the whole text land
+// in `out`; returns their byte count, the missing count and the id width used; ErrHipNoSpace with the size required if `out` is too small.
+func (hv *HipVocab) TokenizeDocumentPinned(text *HipHostBuffer, n int, raw bool, encodingLength uint8, pieceBytes uint64, slots int, out *HipHostBuffer) (uint64, uint32, uint8, HipDocumentStats, error) {
+	var used, missing C.uint32_t
+	var need C.uint64_t
+	var st C.tm_document_stats
+	israw := C.int(0)
+	if raw {
+		israw = 1
+	}
+	rc, err := locked(func() C.int {
+		return C.tm_tokenize_document(hv.h, (*C.uint8_t)(text.p), C.uint64_t(n), israw, C.uint32_t(encodingLength), C.uint64_t(pieceBytes), C.uint32_t(slots),
+			(*C.uint8_t)(out.p), C.uint64_t(out.n), &need, &missing, &used, &st)
+	})
+	if err != nil {
+		return 0, 0, 0, HipDocumentStats{}, err
+	}
+	if rc == C.TM_E_NOSPACE {
+		return uint64(need), 0, uint8(used), HipDocumentStats{}, ErrHipNoSpace
+	}
+	stats := HipDocumentStats{int(st.pieces), int(st.slots), uint64(st.normalized_bytes), int(st.host_pieces), st.host_normalized != 0, uint64(st.device_bytes),
+		st.input_pinned != 0, st.output_pinned != 0}
+	return uint64(need), uint32(missing), uint8(used), stats, nil
+}
+
 // TokenizeNormalizedSerialized is TokenizeToSerialized on ALREADY NORMALIZED documents in one resident batch (tm_tokenize_batch_serialized).
 func (hv *HipVocab) TokenizeNormalizedSerialized(normalized [][]byte, encodingLength uint8) ([][]byte, []int, uint8, error) {
 	n := len(normalized)

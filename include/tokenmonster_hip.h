@@ -368,6 +368,35 @@ int tm_encoder_feed_raw(tm_encoder* e, const uint8_t* raw, uint64_t n, uint32_t*
 uint64_t tm_encoder_raw_held(const tm_encoder* e);
 uint32_t tm_encoder_host_pieces(const tm_encoder* e);
 
+/* ---- one large document, host to host ------------------------------------------------------------------------------ */
+/* tm_tokenize_document: ONE document that is in hand as a whole (a file of hundreds of megabytes: the shape of the reference's own benchmark,
+ * one Vocab.tokenize of the whole content), tokenized in pieces of piece_bytes (0 = 32 MiB; 64 .. 2^36) that run through `slots` device
+ * workspaces (0 = 3; 2 .. 8) at once: while piece k resolves its entry state, emits, packs and downloads its ids, the match kernel of piece
+ * k + 1 runs and piece k + 2 uploads.  The walk's state and - for raw text - the 128 bytes of look-ahead go from slot to slot on the device.
+ * Output: what tm_tokenize_batch_serialized gives for this text as one document (after tm_normalize when raw != 0) - the ids of Vocab.tokenize
+ * (go/tokenmonster.go:1017), bit for bit, encoding_length bytes each, little-endian (2, 3 or 4; 0 = automatic, go :990-996; 4 = plain uint32)
+ * - and its *missing (may be NULL).  *bytes_needed is always set; on TM_E_NOSPACE nothing in bytes_out is promised and *bytes_needed is the
+ * capacity required.  n == 0 is an empty document.
+ * raw != 0: the text is cut behind line feeds (as tm_encoder_feed_raw cuts it) and each piece is normalized on the device, beside the walk of
+ * the piece before; a piece the device normalizer leaves to the host normalizer takes that path inside the call (stats->host_pieces).  Raw
+ * text of a vocabulary whose normalizer needs the whole document (quotemarks 8, trim 32, leadingspace 64), and a text with piece_bytes bytes
+ * without a byte to cut behind, is normalized once by the host normalizer first (stats->host_normalized = 1).  Capcode 1 with raw != 0:
+ * TM_E_INVALID.  Pageable buffers go through pinned staging; buffers from tm_host_alloc / tm_host_register are DMA'd directly.
+ * The slots come from a grow-only pool of the vocabulary shaped by (piece_bytes, raw): a second call of the same shape allocates nothing, and
+ * the device memory held (stats->device_bytes) depends on piece_bytes and slots only.  Concurrent calls take different slots (at most four
+ * calls at once, further callers wait).  Nothing runs on the NULL stream; the call uses the calling thread only. */
+typedef struct tm_document_stats {
+  uint32_t pieces, slots;
+  int input_pinned, output_pinned;
+  uint64_t normalized_bytes;
+  uint32_t host_pieces;        /* raw pieces the host normalizer took inside the call */
+  uint32_t host_normalized;    /* 1: the whole document was normalized on the host first */
+  uint64_t device_bytes;       /* device memory the call held: a function of piece_bytes and slots only */
+} tm_document_stats;
+int tm_tokenize_document(const tm_vocab* v, const uint8_t* text, uint64_t n, int raw, uint32_t encoding_length, uint64_t piece_bytes,
+                         uint32_t slots, uint8_t* bytes_out, uint64_t bytes_cap, uint64_t* bytes_needed, uint32_t* missing,
+                         uint32_t* encoding_length_used, tm_document_stats* stats);
+
 /* ---- trainvocab scoring pass: replaces training/trainvocab.go:925-1176 ------------------------ */
 /* Upload the normalized dataset once (trainvocab.go:1660-1665 keeps it for the whole run). */
 int tm_dataset_upload(const uint8_t* normalized, uint64_t n, tm_dataset** out);

@@ -115,6 +115,8 @@ struct tm_vocab;
 namespace tmh {
 struct LanePool;                       // tm_host.hip: streams + workspaces the host-buffer entry points borrow
 void pool_destroy(LanePool* p);
+struct DocPool;                        // tm_document.hip: the slots tm_tokenize_document borrows
+void doc_pool_destroy(DocPool* p);
 // Every entry point that takes a vocabulary (or a batch / dataset bound to one) runs on the device the vocabulary's tables live
 // on, whatever device is current for the calling OS thread (cgo moves goroutines between threads): makes it current.
 int enter_device(const tm_vocab* v);
@@ -138,6 +140,7 @@ struct tm_vocab {
   tmh::Row* d_rows = nullptr;
   uint8_t* d_begin_byte = nullptr;
   mutable tmh::LanePool* pool = nullptr;   // created on first use; the tables themselves are immutable
+  mutable tmh::DocPool* doc_pool = nullptr;
   // one event per stream that kernels reading the tables have been launched on, re-recorded BEHIND every such launch (note_table_use):
   // tm_vocab_free parks the device block for the next load, and the block must not be refilled while such a kernel is still in flight.
   // (Recorded at launch time, not at free time: by then the stream may have been destroyed by its owner.)

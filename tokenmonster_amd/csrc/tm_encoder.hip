@@ -27,8 +27,8 @@
 // in portions of what the buffer has room for; each portion is then a normalized feed like any other.  A piece the device normalizer leaves to
 // the host normalizer (full-width Latin, polytonic Greek, malformed UTF-8 ...) takes that path inside the same call (tm_encoder_host_pieces).
 // Out of scope, because they need the whole document: the flags quotemarks 8 (the reference's in-place quirk counts the bytes the document has
-// lost so far), trim 32 (unbounded look-ahead for trailing blanks) and leadingspace 64 (the document's start); capcode 1.  Also out: a
-// serialized output form, and running the normalizer of piece k + 1 beside the walk of piece k.
+// lost so far), trim 32 (unbounded look-ahead for trailing blanks) and leadingspace 64 (the document's start); capcode 1.  (A document that
+// is in hand as a whole goes through tm_tokenize_document, tm_document.hip: serialized ids, and the pieces overlapped in slots of their own.)
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -36,12 +36,13 @@
 #include <cstring>
 #include <vector>
 
+#include "tm_cuts.h"
 #include "tm_pipeline.h"
 
 using namespace tmh;
 
 namespace {
-constexpr uint64_t HALO = 128, MIN_RANGE = 64;
+constexpr uint64_t HALO = CUT_HALO, MIN_RANGE = CUT_MIN_RANGE;
 constexpr uint64_t DEFAULT_PIECE = 32ull << 20, MAX_PIECE = 1ull << 36;
 constexpr size_t O_EXITS = 0, O_ENTRY = 128, O_ACC = 192, SMALL_BYTES = 256;      // the encoder's own device words: exit map | entry state | missing, state
 }  // namespace
@@ -148,15 +149,7 @@ int enc_upload(tm_encoder* e, const uint8_t* src, uint64_t n) {
 }
 
 // ---- raw text ------------------------------------------------------------------------------------------------------------------------
-// bytes behind which the normalizer is in its start state (see the header): '\n' wherever there is one, these once a line outgrows a piece
-bool fallback_cut(uint8_t c) {
-  switch (c) {
-    case '\n': case '\t': case '.': case ',': case ';': case ':': case '!': case '?': case '(': case ')': case '[': case ']': case '{': case '}':
-    case '<': case '>': case '=': case '/': case '-': case '"': return true;
-    default: return false;
-  }
-}
-
+// (the bytes behind which the normalizer is in its start state, and the search for the last of them: tm_cuts.h)
 // TM_OK, or why this vocabulary's raw text cannot be cut (thread-local message set)
 int raw_refusal(const tm_vocab* v, bool say) {
   const uint32_t capcode = v->host.capcode, flag = v->host.norm_flag;
@@ -169,9 +162,6 @@ int raw_refusal(const tm_vocab* v, bool say) {
   if (!why) return TM_OK;
   return say ? set_error(TM_E_INVALID, "%s needs the whole document: normalize it first and use tm_encoder_feed", why) : TM_E_INVALID;
 }
-
-// the normalized size a raw piece of max_piece bytes may have on the device: three times (a Hangul syllable under NFD) and some
-uint64_t piece_norm_cap(uint64_t max_piece) { return 3 * max_piece + 4096; }
 
 int enc_make_nws(tm_encoder* e) {
   tm_batch* nb = nullptr;
@@ -353,14 +343,13 @@ int tm_encoder_feed_raw(tm_encoder* e, const uint8_t* raw, uint64_t n, uint32_t*
   while (pos < n) {
     // the text at hand is rhold + raw[pos, n); the cut lies in its first max_piece bytes
     const uint64_t held = e->rhold.size(), window = std::min<uint64_t>(n - pos, e->max_piece - held);
-    uint64_t take = 0;                                   // bytes of raw[pos ..) in front of the cut
-    for (uint64_t i = window; i > 0; i--) if (raw[pos + i - 1] == '\n') { take = i; break; }
+    uint64_t take = cut_behind_line_feed(raw + pos, window);      // bytes of raw[pos ..) in front of the cut
     bool cut = take > 0;
     if (!cut && held + window == e->max_piece) {        // a line of a whole piece: behind its last separator, in the new bytes or in the held ones
-      for (uint64_t i = window; i > 0 && !cut; i--) if (fallback_cut(raw[pos + i - 1])) { take = i; cut = true; }
+      take = cut_behind_fallback(raw + pos, window);
+      cut = take > 0;
       if (!cut) {
-        uint64_t h = held;
-        while (h > 0 && !fallback_cut(e->rhold[h - 1])) h--;
+        const uint64_t h = cut_behind_fallback(e->rhold.data(), held);
         if (h == 0) {
           e->failed = true;
           return set_error(TM_E_LIMIT, "a line of more than max_piece_bytes without a separator: normalize it as a whole");

@@ -1167,6 +1167,39 @@ __global__ __launch_bounds__(256) void k_enc_carry(const uint8_t* __restrict__ e
   }
 }
 
+// tm_tokenize_document (tm_document.hip): the same step between two pieces of ONE document that lie in DIFFERENT workspaces (slots), so that
+// the match kernel of piece k + 1 can run while piece k resolves, emits and downloads.  The document's state lives in one cell of the call:
+//   cell[0] = entry state of the next piece, cell[2] = error word (sticky)
+// One wavefront, behind this piece's k_match_branch + k_doc_exits and behind the chain kernel of the piece before:
+//   entry[0]  <- cell[0]: where this slot's k_resolve looks (tm_batch::d_doc_entry)
+//   cell[0]   <- exits[cell[0]] (`exits` null: a piece that owns nothing, the state passes through).  A state without an exit is the walk's
+//                dead end (k_resolve would set bit 0 of the error word): it goes into cell[2] and into this slot's error word here, and
+//   ctl       <- the slot's control words for the kernels behind (k_resolve .. K4, tm_batch::d_ctl): {nseg, 1 document}, or all zero once
+//                cell[2] is set - neither this piece nor any later one emits
+//   next_text[0 .. keep) <- text[from .. from + keep): raw input, whose look-ahead cannot be uploaded twice - the last bytes of this slot's
+//                normalized text are the first of the next slot's (different buffers: no overlap to mind)
+__global__ __launch_bounds__(64) void k_doc_chain(uint32_t* __restrict__ cell, const uint8_t* __restrict__ exits, uint8_t* __restrict__ entry, uint32_t* __restrict__ slot_error,
+                                                  uint64_t* __restrict__ ctl, uint64_t nseg, const uint8_t* __restrict__ text, uint64_t from, uint32_t keep,
+                                                  uint8_t* __restrict__ next_text) {
+  const uint32_t t = threadIdx.x;
+  for (uint32_t i = t; i < keep; i += 64u) next_text[i] = text[from + i];
+  if (t != 0) return;
+  uint32_t e = cell[0], err = cell[2];
+  if (e >= (uint32_t)ENT) { e = 0u; err |= 2u; }
+  uint32_t x = e;
+  if (exits && !err) { x = exits[e]; if (x >= (uint32_t)ENT) { x = 0u; err |= 1u; } }
+  entry[0] = (uint8_t)e;
+  cell[0] = x;
+  cell[2] = err;
+  if (err) *slot_error = *slot_error | err;
+  ctl[0] = err ? 0ull : nseg;
+  ctl[1] = err ? 0ull : 1ull;
+  ctl[2] = 0ull;
+  ctl[3] = err ? (uint64_t)RING_ERROR : 0ull;
+  ctl[4] = 0ull;
+  ctl[5] = 0ull;
+}
+
 // Count() of a document = its ids without the delete tokens (go/tokenmonster.go:1281, quirk Q2): K3 knows the ids, K4 the delete tokens
 __global__ void k_doc_events(const uint32_t* __restrict__ doc_ntok, const uint32_t* __restrict__ doc_fd, uint32_t ndocs, uint32_t* __restrict__ doc_events) {
   const uint32_t d = blockIdx.x * blockDim.x + threadIdx.x;
@@ -2056,6 +2089,20 @@ __global__ void k_chunk_done(const uint64_t* __restrict__ ctl, const uint64_t* _
   __threadfence_system();                      // (the host polls the status word: what it says must be there first)
   h_status[0] = st;
 }
+// the verdict of a piece of tm_tokenize_document (k_doc_chain has written the piece's control words): as k_chunk_done, and the piece's characters
+// without a token beside the count of its ids
+__global__ void k_doc_done(const uint64_t* __restrict__ ctl, const uint64_t* __restrict__ totals, const uint32_t* __restrict__ error_flag, const uint32_t* __restrict__ doc_missing,
+                           uint64_t out_cap, uint64_t* __restrict__ h_status) {
+  if (threadIdx.x != 0) return;
+  uint64_t st = ctl[3];
+  const uint64_t ntok = st ? 0ull : totals[1];
+  const uint32_t err = *error_flag;
+  if (!st && err) st |= RING_ERROR;
+  if (!st && ntok > out_cap) st |= RING_OUT_CAP;
+  h_status[1] = ntok; h_status[2] = st ? 0ull : (uint64_t)doc_missing[0]; h_status[3] = ctl[0]; h_status[4] = err;
+  __threadfence_system();                      // (the host watches the status word: what it says must be there first)
+  h_status[0] = st;
+}
 // ids -> enc bytes each, the count worked out on the device (the status word of k_chunk_ctl the id total, the error word); sixteen ids per work-item, 16-byte stores (`out` 16-byte aligned)
 // ... and k_chunk_done's part with it (one launch less behind K4): every work-item works the count out for itself, the first one tells the host
 template <int ENC>
@@ -2722,6 +2769,43 @@ int ring_enqueue_tokenize(tm_batch* b, hipStream_t st, uint32_t enc, uint8_t* d_
   }
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? TM_OK : hip_fail(e, "kernel launch");
+}
+
+// ---- tm_tokenize_document (tm_document.hip): the second half of a piece, behind pipeline_match + launch_doc_exits ---------------------------
+void launch_doc_chain(tm_batch* b, uint32_t* d_cell, const uint8_t* d_exits, uint8_t* d_entry, uint64_t* d_ctl, uint64_t nseg, uint64_t from, uint32_t keep,
+                      uint8_t* next_text, hipStream_t st) {
+  TM_LAUNCH(k_doc_chain, 1, 64, 0, st, d_cell, d_exits, d_entry, b->d_error, d_ctl, nseg, b->d_text, from, keep, next_text);
+}
+// K3 .. K4 under the control words k_doc_chain has written, the ids packed to `enc` bytes, the verdict to h_status (page-locked: status bits, ids,
+// characters without a token, segments, device error word).  h_scratch: eight page-locked words nobody reads (k_serialize_ctl's own verdict)
+int doc_enqueue_resolve(tm_batch* b, hipStream_t st, uint32_t enc, uint64_t* d_ctl, uint8_t* d_bytes, uint64_t d_bytes_cap, uint64_t* h_status, uint64_t* h_scratch,
+                        const uint8_t** ids_at) {
+  const uint64_t cap_ids = enc == 4 ? b->out_cap : std::min<uint64_t>(b->out_cap, d_bytes_cap / enc);
+  const bool direct16 = enc == 2 && r0_narrow(b) && !(debug_flags() & 32768);      // (as ring_enqueue_tokenize: K4 writes two-byte ids itself)
+  b->d_ctl = d_ctl;
+  b->d_out16 = direct16 ? reinterpret_cast<uint16_t*>(d_bytes) : nullptr;
+  b->out16_cap = cap_ids;
+  const int rc = pipeline_resolve(b, st, nullptr, 2);
+  b->d_out16 = nullptr;
+  b->d_ctl = nullptr;
+  if (rc != TM_OK) return rc;
+  *ids_at = enc == 4 ? reinterpret_cast<const uint8_t*>(b->d_out) : d_bytes;
+  if (!direct16 && enc != 4) {
+    const uint32_t grid = (uint32_t)((cap_ids / 16 + 1 + 255) / 256);
+    if (enc == 2) TM_LAUNCH(k_serialize_ctl<2>, grid, 256, 0, st, b->d_out, d_ctl, d_bytes, b->d_totals, b->d_error, cap_ids, h_scratch);
+    else TM_LAUNCH(k_serialize_ctl<3>, grid, 256, 0, st, b->d_out, d_ctl, d_bytes, b->d_totals, b->d_error, cap_ids, h_scratch);
+  }
+  TM_LAUNCH(k_doc_done, 1, 64, 0, st, d_ctl, b->d_totals, b->d_error, b->d_doc_missing, cap_ids, h_status);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? TM_OK : hip_fail(e, "kernel launch");
+}
+// a piece whose ids outgrew the slot's buffers (RING_OUT_CAP): the emit stage again into a larger id buffer (ensure_output), with the stream waited for
+int doc_redo_emit(tm_batch* b, hipStream_t st, uint64_t* d_ctl) {
+  b->d_ctl = d_ctl;
+  b->last_stream = st;
+  const int rc = ensure_output(b);
+  b->d_ctl = nullptr;
+  return rc;
 }
 }  // namespace tmh
 extern "C" {

@@ -274,6 +274,12 @@ int pipeline_resolve(tm_batch* b, hipStream_t st, hipEvent_t* ev, int mode);
 void launch_doc_exits(tm_batch* b, uint8_t* d_exits, hipStream_t st);
 // the streaming encoder's step from one pass to the next (k_enc_carry): entry state, missing count and the `keep` bytes of look-ahead, all on the device
 void launch_enc_carry(tm_batch* b, const uint8_t* d_exits, uint8_t* d_entry, uint32_t* d_acc, uint64_t own, uint32_t keep, hipStream_t st);
+// tm_tokenize_document's step from one slot to the next (k_doc_chain) and the second half of a piece behind it (tm_kernels.hip)
+void launch_doc_chain(tm_batch* b, uint32_t* d_cell, const uint8_t* d_exits, uint8_t* d_entry, uint64_t* d_ctl, uint64_t nseg, uint64_t from, uint32_t keep,
+                      uint8_t* next_text, hipStream_t st);
+int doc_enqueue_resolve(tm_batch* b, hipStream_t st, uint32_t enc, uint64_t* d_ctl, uint8_t* d_bytes, uint64_t d_bytes_cap, uint64_t* h_status, uint64_t* h_scratch,
+                        const uint8_t** ids_at);
+int doc_redo_emit(tm_batch* b, hipStream_t st, uint64_t* d_ctl);
 // scoring variant of the chain kernel: histogram in HBM (scores | 4 limbs | 256 counters), see tm_score.hip
 bool raw_upload_replaces_buffers(const tm_batch* b, const uint64_t* raw_offsets, uint32_t ndocs);
 void pack_text(tm_batch* b, hipStream_t st);     // tm_norm.hip: the normalizer's slabs packed into d_text (no-op unless text_in_slabs)

@@ -935,6 +935,7 @@ void tm_vocab_free(tm_vocab* v) {
   pending.clear();
   (void)hipGetLastError();             // (an event of a caller's stream that the caller has destroyed already: nothing to wait for)
   tmh::pool_destroy(v->pool);
+  tmh::doc_pool_destroy(v->doc_pool);
   if (v->d_block) block_put(v->device, false, v->d_block, v->block_bytes, std::move(pending));
   else for (hipEvent_t ev : pending) (void)hipEventDestroy(ev);
   delete v;

@@ -351,6 +351,42 @@ class Vocab:
             st = {k: getattr(stats, k) for k, _ in PipelineStats._fields_}
             return out[: int(boff[nd])], boff, missing[:nd], enc.value, st
 
+    def tokenize_document(self, data, raw=True, encoding_length=0, piece_bytes=0, slots=0, out=None):
+        """ONE large document host to host (tm_tokenize_document): its pieces of piece_bytes (0 = 32 MiB) run through `slots` (0 = 3) device
+        workspaces at once, upload | match | resolve + emit | download overlapped.  -> (ids, missing, stats dict): the ids of tokenize /
+        tokenize_normalized of the whole text as uint16 (encoding_length 2), uint32 (3 and 4; 0 = by the size of the vocabulary).
+        `data`: bytes, a numpy uint8 array or a PinnedBuffer; `out` (numpy uint8 or PinnedBuffer) receives the serialized ids."""
+        if isinstance(data, PinnedBuffer):
+            data = data.array
+        if isinstance(out, PinnedBuffer):
+            out = out.array
+        if isinstance(data, str):
+            data = data.encode("utf-8")
+        text = N.as_u8(data)
+        need, miss, enc = C.c_uint64(), C.c_uint32(), C.c_uint32()
+        stats = DocumentStats()
+        if out is None:
+            out = np.empty(int(text.size) + 64, dtype=np.uint8)
+        while True:
+            rc = N.lib.tm_tokenize_document(self._h, N.ptr(text) if text.size else None, text.size, 1 if raw else 0, encoding_length, piece_bytes, slots,
+                                            N.ptr(out), out.size, C.byref(need), C.byref(miss), C.byref(enc), C.byref(stats))
+            if rc == N.TM_E_NOSPACE:
+                out = np.empty(int(need.value), dtype=np.uint8)
+                continue
+            N.check(rc)
+            break
+        st = {k: getattr(stats, k) for k, _ in DocumentStats._fields_}
+        st["encoding_length"] = enc.value
+        packed = out[: int(need.value)]
+        if enc.value == 2:
+            ids = packed.view("<u2")
+        elif enc.value == 4:
+            ids = packed.view("<u4")
+        else:
+            t = packed.reshape(-1, 3).astype(np.uint32)
+            ids = t[:, 0] | (t[:, 1] << 8) | (t[:, 2] << 16)
+        return ids, int(miss.value), st
+
 
 class Decoder:
     """streaming decoder (go/tokenmonster.go:552-700 NewDecoder; python/tokenmonster.py Decoder): feed ids a few at a time, get the
@@ -466,6 +502,11 @@ class Encoder:
 class PipelineStats(C.Structure):
     _fields_ = [("chunks", C.c_uint32), ("lanes", C.c_uint32), ("input_pinned", C.c_int), ("output_pinned", C.c_int),
                 ("normalized_bytes", C.c_uint64), ("host_fallback_docs", C.c_uint32), ("ring", C.c_uint32), ("ring_exact_chunks", C.c_uint32)]
+
+
+class DocumentStats(C.Structure):
+    _fields_ = [("pieces", C.c_uint32), ("slots", C.c_uint32), ("input_pinned", C.c_int), ("output_pinned", C.c_int), ("normalized_bytes", C.c_uint64),
+                ("host_pieces", C.c_uint32), ("host_normalized", C.c_uint32), ("device_bytes", C.c_uint64)]
 
 
 class PinnedBuffer:
