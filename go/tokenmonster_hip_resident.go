@@ -348,6 +348,21 @@ func (b *HipBatch) Collate(how HipCollate, stream, ids, mask, lengths unsafe.Poi
 	return err
 }
 
+// Spans writes the byte span of every id of the last run to spans: uint32 [total ids][2], (begin, end) in the slot order of the ids, counted
+// from each document's start in the normalized text (tm_batch_spans).  spans: device or page-locked memory, aligned to 8 bytes, room for capIds pairs.
+func (b *HipBatch) Spans(stream, spans unsafe.Pointer, capIds uint64) error {
+	_, err := locked(func() C.int { return C.tm_batch_spans(b.h, stream, (*C.uint32_t)(spans), C.uint64_t(capIds)) })
+	return err
+}
+
+// CollateSpans is the companion of Collate: spans [Docs, RowLen, 2] elements of spanBytes 4 or 8, the pair of every column that holds an id of
+// the document, (0, 0) on BOS, EOS and padding (tm_batch_collate_spans).
+func (b *HipBatch) CollateSpans(how HipCollate, stream, spans unsafe.Pointer, spanBytes uint32) error {
+	h := how.c()
+	_, err := locked(func() C.int { return C.tm_batch_collate_spans(b.h, &h, stream, spans, C.uint32_t(spanBytes)) })
+	return err
+}
+
 // PackRows is the number of rows Pack writes for these documents.
 func (b *HipBatch) PackRows(how HipCollate) (uint64, error) {
 	h := how.c()

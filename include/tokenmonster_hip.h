@@ -305,6 +305,35 @@ int tm_batch_pack(tm_batch* b, const tm_collate* how, void* stream, uint64_t row
 int tm_batch_load_ids(tm_batch* b, const void* rows, uint32_t nrows, uint32_t row_len, uint32_t id_bytes,
                       const uint32_t* lengths, uint32_t pad_id, uint32_t bos_id, uint32_t eos_id, void* stream);
 
+/* ---- byte spans of the ids: where in the text each id came from (the offset_mapping of other tokenizers) ----------------------------------- */
+/* The walk stands at byte i of a document when it emits an id and then moves on by that token's advance: the id's span is [i, i + advance),
+ * counted in bytes from the document's start in the NORMALIZED text the walk runs on - after tm_batch_upload_raw + tm_batch_normalize the text
+ * tm_batch_download_text returns (the raw text itself for a vocabulary with capcode 0 and no normalization flags); mapping a span back through
+ * the normalizer to offsets of the raw text is not done here (the follow-up).  The delete token a forward-delete branch emits behind a token
+ * gets the empty span at that token's end; a character without a token gets [i, i + 1) when the vocabulary has an unk token and otherwise
+ * leaves no id, hence a gap; a token may advance by 0 bytes (a one-byte alternative in a forward-delete state): its span is empty.  Begins
+ * never decrease and the spans of a document never overlap.  Neither the ids nor a decode give the spans back (the "D " duplicates of a
+ * capcode vocabulary, forward deletes and alternatives of another length stand in the way).  Not offered for tm_tokenize_pipeline,
+ * tm_tokenize_document, the streaming encoder and tm_batch_pack.
+ * tm_batch_spans: spans_out (device or page-locked memory, aligned to 8 bytes) receives uint32_t[total ids][2], the pairs (begin, end) in
+ * exactly the slot order of tm_batch_device_tokens.  Waits for the batch's last run as tm_batch_collate does, is then asynchronous on `stream`.
+ * spans_cap (in ids) smaller than the total: TM_E_NOSPACE, nothing is written.  A batch whose ids did not come from a walk (no completed
+ * tm_batch_run since the last upload, or tm_batch_load_ids since): TM_E_INVALID.  A document of 2^32 normalized bytes or more: TM_E_LIMIT.
+ * The pass reads what the run left (it walks the chains again, without fetching an id) and changes none of it: ids, totals, missing and
+ * counts stay as they are. */
+int tm_batch_spans(tm_batch* b, void* stream, uint32_t* spans_out, uint64_t spans_cap);
+/* The companion of tm_batch_collate, with the same tm_collate: spans_out[ndocs * row_len * 2] elements of span_bytes 4 or 8 (8: int64 as
+ * torch wants it), (begin, end) per column.  A column that holds an id of the document gets that id's pair - head, TM_COLLATE_KEEP_TAIL and
+ * TM_COLLATE_PAD_LEFT exactly as for the ids -; BOS, EOS and padding get (0, 0).  Every element is written, with 16-byte stores between an
+ * unaligned head and tail.  The ragged pairs are produced first, on `stream`, into a grow-only buffer of the batch: two calls on one batch
+ * at the same time want the same stream.  Errors as tm_batch_collate and tm_batch_spans. */
+int tm_batch_collate_spans(tm_batch* b, const tm_collate* how, void* stream, void* spans_out, uint32_t span_bytes);
+/* tm_tokenize_batch with the spans: spans_out[tokens_cap][2] beside tokens_out[tokens_cap].  On a lane like the other host-buffer calls (no
+ * allocation in steady state, nothing on the NULL stream, callable concurrently); if tokens_cap is too small tok_offsets IS filled, nothing is
+ * written to tokens_out and spans_out, and TM_E_NOSPACE is returned. */
+int tm_tokenize_batch_spans(const tm_vocab* v, const uint8_t* text, const uint64_t* offsets, uint32_t ndocs,
+                            uint32_t* tokens_out, uint64_t tokens_cap, uint64_t* tok_offsets, uint32_t* spans_out, uint32_t* missing);
+
 /* Streaming Decoder (go/tokenmonster.go:552-700 NewDecoder / Decode / DecodeSerialized / Flush; server jobs 5-9): ids arrive a few
  * at a time, a call returns the text that is COMPLETE so far; the bytes of a character that is not (a token may end in the middle of a
  * UTF-8 sequence) and the state of the capcode decoder are carried to the next call.  Per-connection host state: the gather of a

@@ -82,6 +82,9 @@ SIGNATURES = {
     "tm_batch_pack_rows": (C.c_int, [vp, vp, u64p]),
     "tm_batch_pack": (C.c_int, [vp, vp, vp, C.c_uint64, vp, vp, vp]),
     "tm_batch_load_ids": (C.c_int, [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp]),
+    "tm_batch_spans": (C.c_int, [vp, vp, vp, C.c_uint64]),
+    "tm_batch_collate_spans": (C.c_int, [vp, vp, vp, vp, C.c_uint32]),
+    "tm_tokenize_batch_spans": (C.c_int, [vp, vp, vp, C.c_uint32, vp, C.c_uint64, vp, vp, vp]),
     "tm_decoder_new":(C.c_int, [vp, C.POINTER(vp)]),
     "tm_decoder_free": (None, [vp]),
     "tm_decoder_decode": (C.c_int, [vp, vp, C.c_uint64, vp, C.c_uint64, u64p]),

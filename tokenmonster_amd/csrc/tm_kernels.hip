@@ -129,12 +129,6 @@ __global__ void k_segments(const uint64_t* __restrict__ doc_seg_start, uint32_t 
   seg_doc[g] = lo;
 }
 
-// narrow T(p,0) rows (vocabularies of at most 65 536 ids): per segment SEG ids (u16), then SEG bytes advance [0..5] | fd' [6] | missing [7]
-constexpr uint64_t R0_NARROW = 3 * SEG;
-// ... and the two-plane form of the larger vocabularies (round 6): SEG ids (u32: id, 0xFFFFFF = none), then the same SEG flag bytes - so that K4's
-// position-staging walk (k_emit_list), which only looks at the flag plane, serves them too.  `narrow` of k_match_branch: 0 = one plane of
-// u32 words (id | advance << 24 | fd' << 30 | missing << 31: the id-staging walks k_emit_tiles<false> / k_score_tiles read these), 1 = u16 + u8, 2 = u32 + u8
-constexpr uint64_t R0_WIDE = 5 * SEG;
 // exit map of a segment as K3 reads it: next entry state [0..7] | #ids << 8, R_INVALID = the entry state cannot occur (k_match_branch, step C)
 __device__ __forceinline__ uint32_t exit_entry(const uint16_t* __restrict__ exit16, const uint32_t* __restrict__ exit_wide, uint64_t idx) {
   const uint32_t x = exit16[idx];
@@ -1314,18 +1308,6 @@ __global__ void k_seg_params(const uint64_t* __restrict__ doc_begin, const uint6
   par[g] = make_uint4((uint32_t)begin, (uint32_t)((begin >> 32) & 0xFFu) | (seglen << 8) | ((uint32_t)seg_entry[g] << 20), (uint32_t)base, (uint32_t)(base >> 32));
 }
 
-struct TileSeg { bool have; uint64_t begin, base; uint32_t seglen, entry; };   // one segment of the tile per lane (lanes >= TS: have == false)
-__device__ __forceinline__ TileSeg tile_segment(const uint4* __restrict__ par, uint64_t g, bool lane_ok, uint64_t nseg) {
-  TileSeg t{lane_ok && g < nseg, 0, 0, 0, 0};
-  if (t.have) {
-    const uint4 q = par[g];
-    t.begin = (uint64_t)q.x | ((uint64_t)(q.y & 0xFFu) << 32);
-    t.seglen = (q.y >> 8) & 0xFFFu;
-    t.entry = (q.y >> 20) & 0x7Fu;
-    t.base = (uint64_t)q.z | ((uint64_t)q.w << 32);
-  }
-  return t;
-}
 __device__ __forceinline__ uint64_t shfl_u64(uint64_t v, int src) {
   return (uint64_t)(uint32_t)__shfl((int)(uint32_t)v, src) | ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(v >> 32), src) << 32);
 }
@@ -1400,14 +1382,6 @@ __device__ __forceinline__ void tile_load(uint32_t (*tile)[TROW], const TileSeg&
     }
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_s_waitcnt(0);
-}
-// T(p,1) of a segment: from its side list, or from the dense array when the list overflowed
-__device__ __forceinline__ uint32_t side_word(const uint2* __restrict__ sl, const uint32_t* __restrict__ R1, uint64_t g, uint32_t p) {
-  const uint32_t nside = sl[0].x;
-  if (nside == SIDE_DENSE) return R1[g * SEG + p];
-  uint32_t w = R_INVALID;
-  for (uint32_t k = 1; k <= nside && k < (uint32_t)SIDE_STRIDE; k++) { const uint2 sv = sl[k]; if (sv.x == p) w = sv.y; }
-  return w;
 }
 
 // NARROW: the rows are in the two-plane form (k_match_branch: u16 ids, u8 advance | fd' | missing) and stay that way in LDS - 6 instead of
@@ -1587,10 +1561,6 @@ __global__ __launch_bounds__(64) void k_emit_tiles(const uint32_t* __restrict__ 
 //   itself and has its bit set in a 256-bit map of the segment: the second phase leaves it alone.  Positions of consecutive ids differ (a step that consumes no byte - a forward-delete state may - and everything
 //   behind it is written straight to HBM, like ids that do not fit in front of the byte being read), and a word without an id carries no
 //   forward-delete flag (tm_kernels.hip: the only producer of "missing" is T's first line), so the rule has no second reading.
-#ifndef TM_K4_TSL
-#define TM_K4_TSL 16
-#endif
-constexpr int TSL = TM_K4_TSL, TSLACK_L = 4, TROW_L = SEG + 16;
 // WIDE: the ids of the row are u32 (vocabularies of more than 65 536 ids), else u16
 // OUT16: the ids go out as 16 bits each - `out` is the serialized form of go/tokenmonster.go:1545 itself (a chunk of the host-to-host ring with
 // two-byte ids: no serializing pass behind K4, 1.6 GB less traffic per GiB of text)
@@ -2475,10 +2445,12 @@ int run_pipeline(tm_batch* b, hipStream_t st, bool timed, float* ms, bool emit) 
     b->have_events = true;
   }
   b->has_output = false;
+  b->row_form = -1;
   int rc = pipeline_match(b, st, timed ? b->ev : nullptr);
   if (rc == TM_OK) rc = pipeline_resolve(b, st, timed ? b->ev : nullptr, emit ? 2 : 1);
   if (rc != TM_OK) return rc;
   b->has_output = emit;
+  if (emit) b->row_form = r0_mode(b, false);      // (what pipeline_match has just handed to K1: the span pass reads the rows in this form)
   if (timed) {
     if ((e = hipEventSynchronize(b->ev[TM_NUM_KERNELS])) != hipSuccess) return hip_fail(e, "hipEventSynchronize");
     for (int k = 0; k < TM_NUM_KERNELS; k++) (void)hipEventElapsedTime(&ms[k], b->ev[k], b->ev[k + 1]);
@@ -2679,7 +2651,7 @@ void tm_batch_free(tm_batch* b) {
                   b->d_seg_tokbase, b->d_seg_par, b->d_doc_ntok, b->d_doc_events, b->d_doc_missing, b->d_doc_fd, b->d_tok_offsets, b->d_scan_tmp, b->d_totals,
                   b->d_out, b->d_groups, b->d_longs, b->d_gmap, b->d_group_entry, b->d_group_base,
                   b->d_raw, b->d_slab, b->d_raw_off, b->d_doc_npiece, b->d_doc_piece_start, b->d_piece_doc, b->d_piece_sum, b->d_piece_carry, b->d_piece_len,
-                  b->d_piece_off, b->d_need_host, b->d_nbegin, b->d_nend, b->d_ninfo, b->d_fb_roff, b->d_fb_noff, b->d_fb_ids, b->d_two, b->d_ctl_store, b->d_dec_a, b->d_dec_b, b->d_rawf, b->d_rawf_off, b->d_pf_piece, b->d_pf_doc, b->d_acc};
+                  b->d_piece_off, b->d_need_host, b->d_nbegin, b->d_nend, b->d_ninfo, b->d_fb_roff, b->d_fb_noff, b->d_fb_ids, b->d_two, b->d_ctl_store, b->d_dec_a, b->d_dec_b, b->d_rawf, b->d_rawf_off, b->d_pf_piece, b->d_pf_doc, b->d_acc, b->d_spans};
   for (void* p : ptrs) (void)hipFree(p);
   if (b->have_events) for (auto& ev : b->ev) (void)hipEventDestroy(ev);
   if (b->aux_stream) (void)hipStreamDestroy(b->aux_stream);

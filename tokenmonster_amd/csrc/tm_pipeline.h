@@ -118,6 +118,40 @@ __device__ __forceinline__ uint32_t mbcnt64(unsigned long long mask, uint32_t ac
   return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, acc));
 }
 
+// ---- what the chain walks behind K3 share (K4 and the scoring walks in tm_kernels.hip, the span pass in tm_spans.hip) ----------------------
+// narrow T(p,0) rows (vocabularies of at most 65 536 ids): per segment SEG ids (u16), then SEG bytes advance [0..5] | fd' [6] | missing [7]
+constexpr uint64_t R0_NARROW = 3 * SEG;
+// ... and the two-plane form of the larger vocabularies (round 6): SEG ids (u32: id, 0xFFFFFF = none), then the same SEG flag bytes - so that K4's
+// position-staging walk (k_emit_list), which only looks at the flag plane, serves them too.  `narrow` of k_match_branch: 0 = one plane of
+// u32 words (id | advance << 24 | fd' << 30 | missing << 31: the id-staging walks k_emit_tiles<false> / k_score_tiles read these), 1 = u16 + u8, 2 = u32 + u8
+constexpr uint64_t R0_WIDE = 5 * SEG;
+// the position-staging walks (k_emit_list, k_score_list, k_span_list): segments per wavefront, slack in front of a row's flag bytes, bytes per row in LDS
+#ifndef TM_K4_TSL
+#define TM_K4_TSL 16
+#endif
+constexpr int TSL = TM_K4_TSL, TSLACK_L = 4, TROW_L = SEG + 16;
+
+struct TileSeg { bool have; uint64_t begin, base; uint32_t seglen, entry; };   // one segment of the tile per lane (lanes >= TS: have == false)
+__device__ __forceinline__ TileSeg tile_segment(const uint4* __restrict__ par, uint64_t g, bool lane_ok, uint64_t nseg) {
+  TileSeg t{lane_ok && g < nseg, 0, 0, 0, 0};
+  if (t.have) {
+    const uint4 q = par[g];
+    t.begin = (uint64_t)q.x | ((uint64_t)(q.y & 0xFFu) << 32);
+    t.seglen = (q.y >> 8) & 0xFFFu;
+    t.entry = (q.y >> 20) & 0x7Fu;
+    t.base = (uint64_t)q.z | ((uint64_t)q.w << 32);
+  }
+  return t;
+}
+// T(p,1) of a segment: from its side list, or from the dense array when the list overflowed
+__device__ __forceinline__ uint32_t side_word(const uint2* __restrict__ sl, const uint32_t* __restrict__ R1, uint64_t g, uint32_t p) {
+  const uint32_t nside = sl[0].x;
+  if (nside == SIDE_DENSE) return R1[g * SEG + p];
+  uint32_t w = R_INVALID;
+  for (uint32_t k = 1; k <= nside && k < (uint32_t)SIDE_STRIDE; k++) { const uint2 sv = sl[k]; if (sv.x == p) w = sv.y; }
+  return w;
+}
+
 }  // namespace tmh
 
 struct tm_batch {
@@ -209,6 +243,9 @@ struct tm_batch {
   uint32_t* d_out = nullptr;
   uint64_t out_cap = 0;
   bool has_output = false;              // ids and offsets of a completed run (or of tm_batch_load_ids) lie in d_out / d_tok_offsets: what tm_batch_collate / tm_batch_pack ask for
+  int row_form = -1;                    // the form of the T(p,0) rows the last id-emitting run left (k_match_branch's `narrow`: 0 one plane of u32 words, 1 u16 + u8, 2 u32 + u8); -1: the ids did not come from a walk
+  uint2* d_spans = nullptr;             // tm_batch_collate_spans / tm_tokenize_batch_spans: the ragged (begin, end) pairs of the ids, grow-only (tm_spans.hip)
+  uint64_t spans_cap = 0;
   uint16_t* d_out16 = nullptr;          // set for the length of a launch: K4 writes two-byte ids here instead (a chunk of the ring, launch_emit)
   uint64_t out16_cap = 0;
   // a chunk of the host-to-host ring (tm_host.hip): what the host would have read back between the stages - the number of segments the normalizer
@@ -286,6 +323,11 @@ void pack_text(tm_batch* b, hipStream_t st);     // tm_norm.hip: the normalizer'
 void launch_chain_hist(tm_batch* b, uint32_t delete_id, int n_cu, uint32_t* d_hist, unsigned long long* d_tokens, uint32_t* d_missing_bits,
                        uint32_t n_ids, hipStream_t st);
 int ensure_output(tm_batch* b);
+// tm_spans.hip: the byte span of every id of the last run.  spans_reserve: the batch's own buffer (d_spans) for n pairs; batch_spans_on: the pass
+// itself on `st` into `out` (device or page-locked, 8-byte aligned, room for `total` pairs) - the caller has waited for the run (ensure_output)
+int spans_ready(const tm_batch* b, const char* who);
+int spans_reserve(tm_batch* b, uint64_t n);
+int batch_spans_on(tm_batch* b, hipStream_t st, void* out, uint64_t total);
 // small device <-> host transfers that bypass the copy engines (tm_kernels.hip).  small_d2h's destination is filled by small_sync
 // (which synchronizes the stream); small_h2d's source may be reused as soon as the call returns (pageable memory, or at most MAIL_MAX bytes).
 constexpr uint64_t MAIL_BYTES = 4ull << 20, MAIL_MAX = 1ull << 20;

@@ -1,0 +1,323 @@
+// tm_spans.hip — where in the text every id came from: the byte span [begin, end) of each id of a run, in the slot order of the ids
+// (tm_batch_spans), laid out like tm_batch_collate's rows (tm_batch_collate_spans).  Offsets count from the document's start in the
+// NORMALIZED text the walk ran on.
+//
+// The span pass is a sibling of K4's position-staging walk (k_emit_list, tm_kernels.hip): it reads what a run leaves behind - the T(p,0)
+// rows, the side lists / the dense T(p,1) array, the per-segment records of k_seg_params - walks every chain again and writes, for the
+// output slot K4 wrote an id to, the position the walk stood on and that position plus the advance.  It reads only the advance / flag byte of
+// a position, never an id, adds to no counter and writes nothing but its output.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
+#include "tm_pipeline.h"
+#include "tm_collate.h"
+
+namespace tmh {
+
+typedef uint32_t span_t __attribute__((ext_vector_type(2)));      // (begin, end): one 8-byte store
+
+// The flag byte of position pp of segment g where it lies in HBM.  FORM (k_match_branch's `narrow`, recorded by the run): 0 = one plane of
+// u32 words, whose top byte IS the flag byte (advance [0..5] | fd' [6] | missing [7]); 1 = u16 ids + u8 flags; 2 = u32 ids + u8 flags.
+template <int FORM>
+__device__ __forceinline__ uint32_t flag_byte(const uint32_t* __restrict__ R0, uint64_t g, uint32_t pp) {
+  if (FORM == 0) return R0[g * SEG + pp] >> 24;
+  constexpr uint64_t RS = FORM == 2 ? R0_WIDE : R0_NARROW, FO = FORM == 2 ? 4 * SEG : 2 * SEG;
+  return reinterpret_cast<const uint8_t*>(R0)[g * RS + FO + pp];
+}
+
+// k_emit_list without the id fetch.  A wavefront takes TSL consecutive segments: the flag plane of their rows goes to LDS, lane s walks the
+// chain of segment s and stages - in the bytes it has passed - the position of every output slot (the same position twice in a row: the
+// second slot is the delete token behind the token of the first); a second phase of the whole wavefront turns every listed position p into
+// (seg_off + p, seg_off + p + adv(p)), the delete slot into the end twice, with adv from the flag plane where it lies in HBM (the walk has
+// written its list over the copy in LDS), one 8-byte store per slot.  Slots of a forward-delete state - whose advance is the side list's, not
+// the plane's - are written by the walk itself and marked in the segment's bit map, like the delete slot behind them; so is everything from
+// the first slot on that no longer fits in front of the byte being read, or belongs to a step that consumes no byte (stage_after = 512, test
+// hook 10: every slot).  seg_off = (g - doc_seg_start[doc]) * SEG.  total: the number of slots (= ids) of the run; nothing is written beyond it.
+template <int FORM>
+__global__ __launch_bounds__(64) void k_span_list(const uint32_t* __restrict__ R0, const uint2* __restrict__ side, const uint32_t* __restrict__ R1,
+                                                  const uint4* __restrict__ par, uint64_t nseg, const uint32_t* __restrict__ seg_doc,
+                                                  const uint64_t* __restrict__ doc_seg_start, uint64_t total, span_t* __restrict__ out,
+                                                  uint32_t stage_after, uint32_t nounk) {
+  alignas(16) __shared__ uint8_t s_m[TSL][TROW_L];
+  __shared__ uint32_t s_side[TSL][9];                 // (a word of slack: slot numbers up to TROW_L - 1 are looked up)
+  __shared__ uint32_t s_n[TSL], s_off[TSL];
+  __shared__ uint64_t s_base[TSL];
+  const int lane = threadIdx.x;
+  const uint64_t g0 = (uint64_t)blockIdx.x * TSL;
+  if (g0 >= nseg) return;
+  const int nv = (int)(nseg - g0 < (uint64_t)TSL ? nseg - g0 : (uint64_t)TSL);
+  const TileSeg t = tile_segment(par, g0 + lane, lane < TSL, nseg);
+  constexpr uint32_t SLACK = TSLACK_L;
+  {
+    // lane l fetches the flag bytes of positions 4l .. 4l+3 of every row; all loads before the first LDS write
+    uint32_t vb[TSL];
+#pragma unroll
+    for (int s = 0; s < TSL; s++) {
+      const int ss = s < nv ? s : nv - 1;
+      const uint32_t len = s < nv ? (uint32_t)__shfl((int)t.seglen, ss) : 0u;
+      vb[s] = 0u;
+      if (4u * (uint32_t)lane < len) {
+        if (FORM == 0) {
+          typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+          const u32x4 q = TM_STREAM_LOAD(reinterpret_cast<const u32x4*>(R0 + (g0 + (uint64_t)ss) * SEG) + lane);
+          vb[s] = (q.x >> 24) | ((q.y >> 24) << 8) | ((q.z >> 24) << 16) | (q.w & 0xFF000000u);
+        } else {
+          constexpr uint64_t RS = FORM == 2 ? R0_WIDE : R0_NARROW, FO = FORM == 2 ? 4 * SEG : 2 * SEG;
+          vb[s] = TM_STREAM_LOAD(reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint8_t*>(R0) + (g0 + (uint64_t)ss) * RS + FO) + lane);
+        }
+      }
+    }
+#pragma unroll
+    for (int s = 0; s < TSL; s++) *reinterpret_cast<uint32_t*>(&s_m[s][TSLACK_L + 4 * lane]) = vb[s];
+#pragma unroll
+    for (int i = lane; i < TSL * 9; i += 64) reinterpret_cast<uint32_t*>(s_side)[i] = 0u;
+    static_assert((TSL & (TSL - 1)) == 0 && TSL >= 8 && TSL <= 64 && SEG == 256, "a lane per segment, lane & (TSL - 1); a lane fetches four flag bytes of a row");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_s_waitcnt(0);
+  }
+  uint32_t staged = 0, off = 0;
+  {
+    const int rl = lane & (TSL - 1);                                     // (lanes >= TSL have no segment; they only need valid pointers)
+    uint8_t* rowm = s_m[rl];
+    uint32_t* smap = s_side[rl];
+    const uint2* __restrict__ sl = side + (g0 + rl) * SIDE_STRIDE;
+    if (t.have) { const uint64_t g = g0 + lane; off = (uint32_t)((g - doc_seg_start[seg_doc[g]]) * SEG); }      // (a document is shorter than 2^32 bytes: checked by the host)
+    const uint32_t seglen = t.have ? t.seglen : 0u;
+    uint32_t p = t.entry >> 1, fd = t.entry & 1u, E = 0, direct = 0, hop = 0;
+    // gate: as in k_emit_list (>= 0: straight-line step; GATE_DEAD < gate < 0: general step; GATE_DEAD: the chain has left the segment)
+    constexpr int GATE_DEAD = -(1 << 24);
+    const int slack0 = (int)SLACK - 2 - (int)stage_after;
+    int gate = p < seglen ? slack0 + (int)p - (int)(fd << 16) : GATE_DEAD;
+    auto put = [&](uint32_t slot, uint32_t a, uint32_t e) __attribute__((always_inline)) {
+      if (t.base + slot < total) { span_t v; v.x = a; v.y = e; TM_STREAM_STORE(&out[t.base + slot], v); }
+    };
+    auto fast_step = [&]() __attribute__((always_inline)) {
+      const uint32_t m8 = rowm[SLACK + p];
+      const uint32_t miss = m8 >> 7, fdn = (m8 >> 6) & 1u, adv = m8 & 63u;
+      const uint32_t has = 1u - (miss & nounk);
+      rowm[E] = (uint8_t)p; E += has; rowm[E] = (uint8_t)p;              // the id's slot, then (same position again) the delete token's
+      E += fdn;
+      gate += (int)adv - (int)(fdn * 0x10001u + has);
+      fd = fdn;
+      p += max(adv, 1u);
+      gate = p < seglen ? gate : GATE_DEAD;
+    };
+    for (;;) {
+#ifndef TM_EMU
+      if (gate >= 0) {
+        do fast_step(); while (__builtin_amdgcn_ballot_w64(gate < 0) == 0ull);       // (a ballot of the lanes in the loop)
+      }
+#else
+      if (__builtin_amdgcn_ballot_w64(gate >= 0) != 0ull) {
+        const bool in = gate >= 0;
+        do { if (in) fast_step(); } while (__builtin_amdgcn_ballot_w64(in && gate < 0) == 0ull);
+      }
+#endif
+      const bool general = (uint32_t)gate > (uint32_t)GATE_DEAD;      // GATE_DEAD < gate < 0
+      if (__builtin_amdgcn_ballot_w64(general) != 0ull) {
+        if (general) {
+          // the step of state (p, fd): T(p,1) from the segment's side list, T(p,0) from the flag byte in LDS
+          uint32_t has, adv, fdn;
+          bool bad = hop > 2u * SEG;
+          if (fd != 0u) {
+            const uint32_t w = side_word(sl, R1, g0 + rl, p);
+            bad = bad || w == R_INVALID;
+            has = (w & ID_NONE) != ID_NONE ? 1u : 0u; adv = (w >> 24) & 63u; fdn = (w >> 30) & 1u;
+          } else {
+            const uint32_t m8 = rowm[SLACK + p];
+            has = 1u - ((m8 >> 7) & nounk); adv = m8 & 63u; fdn = (m8 >> 6) & 1u;
+          }
+          if (bad) { p = seglen; gate = GATE_DEAD; }      // cannot happen on a chain K1/K3 produced (the run's error word said so: ensure_output); the walk ends
+          else {
+            // staged only while the list can say it (k_emit_list): room in front of the byte being read, a byte consumed, no delete token
+            // without a token in front of it
+            const bool fits = direct == 0u && slack0 + (int)p - (int)E >= 0 && adv != 0u && !(has == 0u && fdn != 0u);
+            if (!fits && direct == 0u) { direct = 1u; staged = E; }      // from here on the segment's spans go straight to HBM
+            const uint32_t a = off + p, e = a + adv;
+            if (fits && fd == 0u) {
+              if (has) rowm[E++] = (uint8_t)p;
+              if (fdn) rowm[E++] = (uint8_t)p;
+            } else {
+              // (the advance of a forward-delete state is not in the plane: its slots go out here and are marked as written - listed all the
+              // same, so that the slot behind them has a neighbour to differ from)
+              if (has) { if (fits) { smap[E >> 5] |= 1u << (E & 31u); rowm[E] = (uint8_t)p; } put(E, a, e); E++; }
+              if (fdn) { if (fits) { smap[E >> 5] |= 1u << (E & 31u); rowm[E] = (uint8_t)p; } put(E, e, e); E++; }
+            }
+            fd = fdn;
+            p += adv;                                                      // (0 is possible: a one-byte alternative of a forward-delete state)
+            hop++;
+            gate = p < seglen ? slack0 + (int)p - (int)E - (int)((fd | direct) << 16) : GATE_DEAD;
+          }
+        }
+      } else if (__builtin_amdgcn_ballot_w64(gate >= 0) == 0ull) break;                 // no lane can step: every chain has left its segment
+    }
+    if (direct == 0u) staged = E;
+  }
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_s_waitcnt(0);
+  // second phase: the spans of the listed positions.  A round takes 64 slots of EVERY segment of the tile (k_emit_list): the flag bytes of a round
+  // are fetched back to back, then its stores.  Nothing branches before the stores: a lane without a slot reads the last byte of the row
+  // and fetches some flag byte of the row (a list entry is a byte: every position it names lies inside the row).
+  if (lane < TSL) { s_n[lane] = lane < nv ? staged : 0u; s_base[lane] = t.base; s_off[lane] = off; }
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_s_waitcnt(0);
+  uint32_t nmax = 0;
+#pragma unroll
+  for (int s = 0; s < TSL; s++) nmax = max(nmax, s_n[s]);
+  nmax = (uint32_t)__builtin_amdgcn_readfirstlane((int)nmax);
+  for (uint32_t j0 = 0; j0 < nmax; j0 += 64u) {
+    const uint32_t j = j0 + (uint32_t)lane, jj = min(j, (uint32_t)TROW_L - 1u), jp = max(jj, 1u) - 1u;
+#pragma unroll 1
+    for (int s0 = 0; s0 < TSL; s0 += 8) {
+      span_t sv[8];
+#pragma unroll
+      for (int k = 0; k < 8; k++) {
+        const int s = s0 + k, ss = s < nv ? s : nv - 1;
+        const uint32_t pp = s_m[s][jj], prev = s_m[s][jp];
+        const uint32_t adv = flag_byte<FORM>(R0, g0 + (uint64_t)ss, pp) & 63u;
+        const uint32_t a = s_off[s] + pp, e = a + adv;
+        sv[k].x = (pp == prev && j != 0u) ? e : a;
+        sv[k].y = e;
+      }
+#pragma unroll
+      for (int k = 0; k < 8; k++) {
+        const int s = s0 + k;
+        const uint64_t base = s_base[s];
+        const bool written = ((s_side[s][jj >> 5] >> (jj & 31u)) & 1u) != 0u;
+        if (j < s_n[s] && !written && base + j < total) TM_STREAM_STORE(&out[base + j], sv[k]);
+      }
+    }
+  }
+}
+
+// ---- k_collate_spans: the pairs laid out like tm_batch_collate's rows ------------------------------------------------------------------------------
+// The output [rows, L, 2] is one flat run of 2 * rows * L elements of T (tm_collate.h): element e is component e & 1 of column (e >> 1) % L of
+// row (e >> 1) / L.  A column that holds a content id gets that id's pair; BOS, EOS and padding get (0, 0).
+template <typename T>
+__global__ __launch_bounds__(256) void k_collate_spans(CollateArgs a, Flat f, const uint32_t* __restrict__ spans, T* __restrict__ out) {
+  constexpr uint32_t PER = 16 / sizeof(T);
+  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  uint64_t e0;
+  uint32_t cnt;
+  if (!flat_span<T>(f, t, e0, cnt)) return;
+  const uint64_t L2 = 2ull * a.L;
+  uint64_t r;
+  uint64_t c;                                         // element of the row: 2 * column + component
+  if (f.n <= 0xFFFFFFFFull && L2 <= 0xFFFFFFFFull) { r = (uint32_t)e0 / (uint32_t)L2; c = (uint32_t)e0 - (uint32_t)r * (uint32_t)L2; }
+  else { r = e0 / L2; c = e0 - r * L2; }
+  RowPlan p = row_plan(a, r);
+  const uint32_t hb = a.bos != TM_NONE ? 1u : 0u;
+  T vals[PER];
+#pragma unroll
+  for (uint32_t k = 0; k < PER; k++) {
+    if (k < cnt) {
+      const uint32_t j = (uint32_t)(c >> 1) - p.lo;      // (wraps to a large number left of the entries)
+      uint32_t v = 0;
+      if (j < p.len && !(hb && j == 0) && !(a.eos != TM_NONE && j == p.len - 1)) v = spans[2 * (p.src + (j - hb)) + (c & 1u)];
+      vals[k] = (T)v;
+      if (++c == L2 && k + 1 < cnt) { c = 0; r++; p = row_plan(a, r); }
+    } else {
+      vals[k] = 0;
+    }
+  }
+  flat_store<T>(out, e0, cnt, vals);
+}
+
+// ---- host side ----------------------------------------------------------------------------------------------------------------------------------------
+int spans_ready(const tm_batch* b, const char* who) {
+  if (!b->has_output || b->row_form < 0 || b->d_ctl)
+    return set_error(TM_E_INVALID, "%s: the batch's ids did not come from a walk (no completed tm_batch_run since the last upload, or tm_batch_load_ids since)", who);
+  return TM_OK;
+}
+
+int spans_reserve(tm_batch* b, uint64_t n) {
+  if (n <= b->spans_cap) return TM_OK;
+  hipError_t e;
+  if (b->spans_cap) trace_grow("spans", n * 8);
+  (void)hipFree(b->d_spans);                         // (waits for the device: no pass is still writing the old buffer)
+  b->device_bytes -= b->spans_cap * 8;
+  b->d_spans = nullptr;
+  b->spans_cap = 0;
+  const uint64_t cap = n + n / 4 + 1024;
+  if ((e = batch_alloc_bytes(b, (void**)&b->d_spans, cap * 8)) != hipSuccess) return hip_fail(e, "hipMalloc spans");
+  b->spans_cap = cap;
+  return TM_OK;
+}
+
+// offsets are 32 bits: no document of the run may be 2^32 bytes or longer.  Only a run of 2^24 segments or more can hold one; then the
+// documents' ranges are fetched and looked at (the stream of the run has been waited for).
+static int spans_check_lengths(tm_batch* b, const char* who) {
+  if (b->nseg < (1ull << 32) / SEG) return TM_OK;
+  std::vector<uint64_t> lo(b->ndocs), hi(b->ndocs);
+  hipError_t e;
+  if ((e = hipMemcpy(lo.data(), b->d_doc_begin, (size_t)b->ndocs * 8, hipMemcpyDeviceToHost)) != hipSuccess ||
+      (e = hipMemcpy(hi.data(), b->d_doc_end, (size_t)b->ndocs * 8, hipMemcpyDeviceToHost)) != hipSuccess) return hip_fail(e, "D2H document ranges");
+  for (uint32_t d = 0; d < b->ndocs; d++)
+    if (hi[d] - lo[d] >= (1ull << 32)) return set_error(TM_E_LIMIT, "%s: document %u has %llu normalized bytes (offsets are 32 bits)", who, d, (unsigned long long)(hi[d] - lo[d]));
+  return TM_OK;
+}
+
+int batch_spans_on(tm_batch* b, hipStream_t st, void* out, uint64_t total) {
+  if (total == 0 || b->nseg == 0) return TM_OK;
+  (void)hipGetLastError();
+  const uint32_t grid = (uint32_t)((b->nseg + TSL - 1) / TSL);
+  const uint32_t stage_after = (debug_flags() & 1024) ? 512u : 0u;      // (test hook 10: every span stored by the walk itself)
+  const uint32_t nounk = b->vocab->tables.unk_id != TM_NONE ? 0u : 1u;   // a character without a token leaves no id, hence no slot
+  span_t* o = static_cast<span_t*>(out);
+  if (b->row_form == 0) TM_LAUNCH(k_span_list<0>, grid, 64, 0, st, b->d_R0, b->d_side, b->d_R1, b->d_seg_par, b->nseg, b->d_seg_doc, b->d_doc_seg_start, total, o, stage_after, nounk);
+  else if (b->row_form == 1) TM_LAUNCH(k_span_list<1>, grid, 64, 0, st, b->d_R0, b->d_side, b->d_R1, b->d_seg_par, b->nseg, b->d_seg_doc, b->d_doc_seg_start, total, o, stage_after, nounk);
+  else TM_LAUNCH(k_span_list<2>, grid, 64, 0, st, b->d_R0, b->d_side, b->d_R1, b->d_seg_par, b->nseg, b->d_seg_doc, b->d_doc_seg_start, total, o, stage_after, nounk);
+  return launch_check();
+}
+
+template <typename T>
+static void launch_collate_spans(const CollateArgs& a, const uint32_t* spans, void* out, hipStream_t st) {
+  const Flat f = flat_of(out, 2ull * a.rows * a.L, sizeof(T));
+  const auto kern = k_collate_spans<T>;
+  TM_LAUNCH(kern, grid_of(flat_items(f, sizeof(T))), 256, 0, st, a, f, spans, static_cast<T*>(out));
+}
+
+}  // namespace tmh
+
+using namespace tmh;
+
+extern "C" {
+
+int tm_batch_spans(tm_batch* b, void* stream, uint32_t* spans_out, uint64_t spans_cap) {
+  if (!b) return set_error(TM_E_INVALID, "tm_batch_spans: null argument");
+  int rc = spans_ready(b, "tm_batch_spans");
+  if (rc != TM_OK) return rc;
+  if (reinterpret_cast<uintptr_t>(spans_out) % 8) return set_error(TM_E_INVALID, "tm_batch_spans: spans_out not aligned to 8 bytes (a pair leaves in one store)");
+  if ((rc = enter_device(b->vocab)) != TM_OK || (rc = ensure_output(b)) != TM_OK) return rc;      // (waits for the run: the rows are all there)
+  const uint64_t total = b->ndocs ? b->last_totals[1] : 0;
+  if (total > spans_cap) return set_error(TM_E_NOSPACE, "tm_batch_spans: spans_cap %llu < %llu ids", (unsigned long long)spans_cap, (unsigned long long)total);
+  if (total && !spans_out) return set_error(TM_E_INVALID, "tm_batch_spans: null argument");
+  if ((rc = spans_check_lengths(b, "tm_batch_spans")) != TM_OK) return rc;
+  return batch_spans_on(b, (hipStream_t)stream, spans_out, total);
+}
+
+int tm_batch_collate_spans(tm_batch* b, const tm_collate* how, void* stream, void* spans_out, uint32_t span_bytes) {
+  int rc = check_how(b, how, spans_out, "tm_batch_collate_spans");
+  if (rc != TM_OK) return rc;
+  if (span_bytes != 4 && span_bytes != 8) return set_error(TM_E_INVALID, "tm_batch_collate_spans: span_bytes %u (4 or 8)", span_bytes);
+  const uint32_t ns = (how->bos_id != TM_NONE ? 1u : 0u) + (how->eos_id != TM_NONE ? 1u : 0u);
+  if (how->row_len < ns) return set_error(TM_E_INVALID, "tm_batch_collate_spans: row_len %u holds no %u specials", how->row_len, ns);
+  if ((uint64_t)how->ndocs * how->row_len > COLLATE_MAX_ELEMS) return set_error(TM_E_LIMIT, "tm_batch_collate_spans: %u rows of %u ids in one call (split the documents)", how->ndocs, how->row_len);
+  if ((rc = spans_ready(b, "tm_batch_collate_spans")) != TM_OK) return rc;
+  if ((rc = enter_device(b->vocab)) != TM_OK || (rc = ensure_output(b)) != TM_OK) return rc;
+  if (how->ndocs == 0) return TM_OK;
+  const uint64_t total = b->last_totals[1];
+  if ((rc = spans_check_lengths(b, "tm_batch_collate_spans")) != TM_OK || (rc = spans_reserve(b, total)) != TM_OK) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  if ((rc = batch_spans_on(b, st, b->d_spans, total)) != TM_OK) return rc;      // the ragged pairs first, into the batch's own buffer
+  (void)hipGetLastError();
+  const CollateArgs a{nullptr, b->d_tok_offsets + how->first_doc, how->ndocs, how->row_len, how->pad_id, how->bos_id, how->eos_id, how->flags};
+  if (span_bytes == 4) launch_collate_spans<uint32_t>(a, reinterpret_cast<const uint32_t*>(b->d_spans), spans_out, st);
+  else launch_collate_spans<uint64_t>(a, reinterpret_cast<const uint32_t*>(b->d_spans), spans_out, st);
+  return launch_check();
+}
+
+}  // extern "C"

@@ -144,11 +144,13 @@ def _check_dtype(torch, dtype):
     return sizes[dtype]
 
 
-def encode_batch(vocab, docs, max_length, *, pad_id, bos_id=None, eos_id=None, pad_left=False, keep_tail=False, dtype=None, raw=True, device=None):
+def encode_batch(vocab, docs, max_length, *, pad_id, bos_id=None, eos_id=None, pad_left=False, keep_tail=False, dtype=None, raw=True, device=None, return_offsets=False):
     """documents (bytes or str; raw=False: already normalized bytes) -> {"input_ids" [rows, max_length] of `dtype` (default int64),
     "attention_mask" [rows, max_length] bool, "lengths" [rows] int32}, CUDA tensors on the vocabulary's device.  Row r is
     [bos] ids [eos] pad...: the ids cut to max_length less the specials given (their head; keep_tail: their tail), the padding on the
-    right (pad_left: on the left)."""
+    right (pad_left: on the left).  return_offsets=True adds "offset_mapping" [rows, max_length, 2] int64: (begin, end) of the bytes the id
+    of a column came from, counted from the document's start in the normalized text the tokenizer walks (raw=True: what Vocab.normalize
+    makes of the document), and (0, 0) on BOS, EOS and padding (tm_batch_collate_spans)."""
     torch = _torch()
     dtype = dtype or torch.int64
     id_bytes = _check_dtype(torch, dtype)
@@ -164,7 +166,12 @@ def encode_batch(vocab, docs, max_length, *, pad_id, bos_id=None, eos_id=None, p
         lengths = torch.empty((nd,), dtype=torch.int32, device=dev)
         how = _Collate(0, nd, max_length, id_bytes, int(pad_id), _special(bos_id), _special(eos_id), (PAD_LEFT if pad_left else 0) | (KEEP_TAIL if keep_tail else 0))
         N.check(N.lib.tm_batch_collate(b, C.byref(how), st, ids.data_ptr(), mask.data_ptr(), lengths.data_ptr()))
-    return {"input_ids": ids, "attention_mask": mask.view(torch.bool), "lengths": lengths}
+        res = {"input_ids": ids, "attention_mask": mask.view(torch.bool), "lengths": lengths}
+        if return_offsets:
+            spans = torch.empty((nd, max_length, 2), dtype=torch.int64, device=dev)
+            N.check(N.lib.tm_batch_collate_spans(b, C.byref(how), st, spans.data_ptr(), 8))
+            res["offset_mapping"] = spans
+    return res
 
 
 def pack_batch(vocab, docs, seq_len, *, eos_id, pad_id, dtype=None, raw=True, device=None):

@@ -173,6 +173,26 @@ class Vocab:
             N.check(rc)
             return out[: int(tok_off[nd])], tok_off, missing[:nd]
 
+    def tokenize_spans_packed(self, text, offsets):
+        """normalized packed documents -> (ids u32[T], tok_offsets u64[D+1], spans u32[T, 2], missing u32[D]): spans[k] = (begin, end) of the
+        bytes id k came from, counted from its document's start (tm_tokenize_batch_spans)"""
+        text = N.as_u8(text)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        nd = offsets.size - 1
+        tok_off = np.zeros(nd + 1, dtype=np.uint64)
+        missing = np.zeros(max(nd, 1), dtype=np.uint32)
+        cap = int(text.size // 2 + 2 * nd + 64)
+        while True:
+            out = np.empty(cap, dtype=np.uint32)
+            spans = np.empty((cap, 2), dtype=np.uint32)
+            rc = N.lib.tm_tokenize_batch_spans(self._h, N.ptr(text), N.ptr(offsets), nd, N.ptr(out), cap, N.ptr(tok_off), N.ptr(spans), N.ptr(missing))
+            if rc == N.TM_E_NOSPACE:
+                cap = int(tok_off[nd])
+                continue
+            N.check(rc)
+            n = int(tok_off[nd])
+            return out[:n], tok_off, spans[:n], missing[:nd]
+
     def tokenize_normalized(self, docs):
         """list of already-normalized documents -> list of uint32 arrays (Vocab.tokenize, go :1017)"""
         single = isinstance(docs, (bytes, bytearray, np.ndarray))
