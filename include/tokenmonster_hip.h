@@ -208,8 +208,8 @@ const char* tm_kernel_name(int k);
  * (the path of a batch with host-normalized documents) instead of leaving it in its slabs for the match kernel, 12 = group tree of
  * long documents with fan-out 4 from 9 segments on, 13 = 64 KiB mailbox for the small host <-> device transfers, 14 = the last member of tm_score_multi gives up
  * after the members' first meeting (an error path: the call must return that member's error), 15 = the id-staging form of the K4 walk (what vocabularies
- * of more than 65 536 ids use) for the two-plane rows too, instead of the position-staging form, 16 = the segment kernels of a chunk of the
- * host-to-host ring one behind the other instead of fused (what a chunk of more than 2^18 pieces takes), 24 = ONE chunk of a
+ * of more than 65 536 ids use) for the two-plane rows too, instead of the position-staging form, 16 = accepted, without effect (it split the segment kernel of a chunk of the
+ * host-to-host ring in two while the batch path had two; there is one launch for every caller now), 24 = ONE chunk of a
  * tm_tokenize_pipeline / tm_tokenize_pipeline_multi call fails with TM_E_INPUT at a place of the host code (an error path: the call must
  * return that error, with nothing of it left in flight and the handle as good as before).  Which one is read from the environment when such a
  * call begins, and only while the bit is set: TM_TEST_FAIL="<place>:<chunk>" or "<place>:<chunk>:<chunks>" (the latter: only a call that

@@ -12,7 +12,7 @@
 #include "tm_internal.h"
 #include "tm_tables.h"
 
-// Kernel launches, raw LDS addresses and the two register-pinning asm statements go through these macros so that tools/emu (test
+// Kernel launches, raw LDS addresses and the register-pinning asm statements go through these macros so that tools/emu (test
 // infrastructure: the kernel sources compiled for the host, work-items as fibers) can build the same files.  TM_EMU is never defined
 // in the product build, where every macro expands to exactly the tokens it replaced.
 #ifdef TM_EMU
@@ -24,6 +24,7 @@
 #define TM_LDS_OBJECTS(a, b) emu::lds_objects(&(a), sizeof(a), &(b), sizeof(b))
 #define TM_KEEP_IN_VGPRS2(a, b) ((void)0)
 #define TM_KEEP_IN_VGPRS4(a, b, c, d) ((void)0)
+#define TM_HAVE_IN_SGPRS6(a, b, c, d, e, f) ((void)0)
 #else
 #define TM_LAUNCH(kern, grid, block, shmem, stream, ...) kern<<<grid, block, shmem, stream>>>(__VA_ARGS__)
 #define TM_LDS_SPACE __attribute__((address_space(3)))
@@ -33,6 +34,7 @@
 #define TM_LDS_OBJECTS(a, b) ((void)0)
 #define TM_KEEP_IN_VGPRS2(a, b) asm volatile("" : "+v"(a), "+v"(b))
 #define TM_KEEP_IN_VGPRS4(a, b, c, d) asm volatile("" : "+v"(a), "+v"(b), "+v"(c), "+v"(d))
+#define TM_HAVE_IN_SGPRS6(a, b, c, d, e, f) asm volatile("" : : "s"(a), "s"(b), "s"(c), "s"(d), "s"(e), "s"(f))     // wave-uniform values that must have arrived HERE: what loads them is issued in front of it, side by side
 #endif
 
 // Streams: the data a kernel touches exactly once — the text K1 reads, the T(p,0) rows / side lists / exit maps it writes (6 GB per GiB

@@ -311,29 +311,23 @@ __device__ __forceinline__ uint32_t transition(const Tables& T, const WaveLds& w
 // per lane) and copies the neighbour's descriptors after ONE workgroup barrier.  Step C's table of contracted (p,1) hops (J1) therefore
 // overlays Db[40..], so that a wavefront never overwrites what its left neighbour may still be copying (D[0..40), Db[0..40)).
 // Host model (round 2): 70 % of the wavefronts share, 26.5 -> 24.3 rounds per wavefront in step A1.
-// For a batch whose text still lies in the device normalizer's slabs (tm_norm.hip): the piece a segment begins in, the offset of its first
-// byte in that piece's slab, and how many bytes the piece holds from there.  piece_off = the pieces' places in the packed text.
-__global__ void k_seg_src(const uint32_t* __restrict__ seg_doc, const uint64_t* __restrict__ doc_seg_start, const uint64_t* __restrict__ doc_begin,
-                          const uint64_t* __restrict__ doc_piece_start, const uint64_t* __restrict__ piece_off, uint64_t nseg, uint4* __restrict__ seg_src,
-                          const uint64_t* __restrict__ ctl = nullptr) {
+// K0: everything k_match_branch has to know about its segment before it can ask for the text, in one 16-byte record, so that a wavefront
+// starts with ONE load behind its kernel arguments instead of a chain of five (segment -> document -> ranges -> place of the text):
+//   packed text:                 x = begin[0..31]   y = begin[32..39]   z = 0
+//   text in the normalizer's slabs (tm_norm.hip): x = the piece the segment begins in   y = the offset of its first byte in that piece's slab
+//                                z = the bytes the piece holds from there (piece_off = the pieces' places in the packed text that never was)
+//   w = bytes of text from the segment's begin on that may be looked at, clamped to 2^20 [0..20] | positions of the segment [21..29] |
+//       the next segment exists and belongs to the same document [30] | text follows the segment's positions [31] (step C)
+// The same launch finds the segment's document (seg_doc: K4's records and the span pass read it).  The records live in d_seg_par, which K4's
+// parameters (k_seg_params) take over behind K3.  ctl: the number of segments is the device's (a chunk of the host-to-host ring).
+constexpr uint32_t SP_DL_BITS = 21, SP_LEN_SHIFT = 21, SP_LEN_BITS = 9, SP_SAME_DOC = 1u << 30, SP_MORE_TEXT = 1u << 31, SP_DL_MAX = 1u << 20;
+static_assert(SP_DL_MAX < (1u << SP_DL_BITS) && SEG < (1 << SP_LEN_BITS) && SP_LEN_SHIFT + SP_LEN_BITS == 30, "the packed word of a segment record");
+__global__ void k_seg_fill(const uint64_t* __restrict__ doc_seg_start, uint32_t ndocs, const uint64_t* __restrict__ doc_begin, const uint64_t* __restrict__ doc_end,
+                           const uint64_t* __restrict__ doc_vis, const uint64_t* __restrict__ doc_piece_start, const uint64_t* __restrict__ piece_off, uint64_t nseg,
+                           uint32_t* __restrict__ seg_doc, uint4* __restrict__ seg_src, const uint64_t* __restrict__ ctl = nullptr) {
   const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (ctl) nseg = ctl[0];
   if (g >= nseg) return;
-  const uint32_t d = seg_doc[g];
-  const uint64_t begin = doc_begin[d] + (g - doc_seg_start[d]) * SEG;
-  uint64_t lo = doc_piece_start[d], hi = doc_piece_start[d + 1];          // the last piece of the document that begins at or before `begin`
-  while (hi - lo > 1) {
-    const uint64_t mid = (lo + hi) >> 1;
-    if (piece_off[mid] <= begin) lo = mid; else hi = mid;
-  }
-  seg_src[g] = make_uint4((uint32_t)lo, (uint32_t)(begin - piece_off[lo]), (uint32_t)(piece_off[lo + 1] - begin), 0u);
-}
-
-// k_segments + k_seg_src in one launch, for a chunk of the host-to-host ring (the number of segments is the device's: ctl[0])
-__global__ void k_seg_fill(const uint64_t* __restrict__ doc_seg_start, uint32_t ndocs, const uint64_t* __restrict__ doc_begin, const uint64_t* __restrict__ doc_piece_start,
-                           const uint64_t* __restrict__ piece_off, uint32_t* __restrict__ seg_doc, uint4* __restrict__ seg_src, const uint64_t* __restrict__ ctl) {
-  const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (g >= ctl[0]) return;
   uint32_t dl = 0, dh = ndocs;   // invariant: start[dl] <= g < start[dh]
   while (dh - dl > 1) {
     const uint32_t mid = dl + (dh - dl) / 2;
@@ -341,89 +335,108 @@ __global__ void k_seg_fill(const uint64_t* __restrict__ doc_seg_start, uint32_t 
   }
   seg_doc[g] = dl;
   const uint64_t begin = doc_begin[dl] + (g - doc_seg_start[dl]) * SEG;
+  // A document owns the positions [doc_begin, doc_end) but may LOOK at text up to doc_vis >= doc_end: a byte range of a dataset
+  // that is scored as part of the whole-buffer walk (training/trainvocab.go:909-922) sees the text that follows it, and tokens that
+  // begin inside the range may end behind it.  For ordinary documents doc_vis == doc_end: the text ends with the document.
+  const uint64_t rem = doc_end[dl] - begin, remv = doc_vis[dl] - begin;
+  const uint32_t look = remv > (uint64_t)SP_DL_MAX ? SP_DL_MAX : (uint32_t)remv;
+  const uint32_t seglen = rem < (uint64_t)SEG ? (uint32_t)rem : (uint32_t)SEG;
+  const bool same = g + 1 < nseg && doc_seg_start[dl + 1] > g + 1;
+  const uint32_t w = look | (seglen << SP_LEN_SHIFT) | (same ? SP_SAME_DOC : 0u) | (remv > (uint64_t)seglen ? SP_MORE_TEXT : 0u);
+  if (doc_piece_start == nullptr) { seg_src[g] = make_uint4((uint32_t)begin, (uint32_t)(begin >> 32) & 0xFFu, 0u, w); return; }
   uint64_t lo = doc_piece_start[dl], hi = doc_piece_start[dl + 1];          // the last piece of the document that begins at or before `begin`
   while (hi - lo > 1) {
     const uint64_t mid = (lo + hi) >> 1;
     if (piece_off[mid] <= begin) lo = mid; else hi = mid;
   }
-  seg_src[g] = make_uint4((uint32_t)lo, (uint32_t)(begin - piece_off[lo]), (uint32_t)(piece_off[lo + 1] - begin), 0u);
+  seg_src[g] = make_uint4((uint32_t)lo, (uint32_t)(begin - piece_off[lo]), (uint32_t)(piece_off[lo + 1] - begin), w);
 }
 
 constexpr int J_SKIP = NPOS - SEG, J_PLANE = NPOS;     // step C: the contracted hop of state (p, 1) lives at word J_SKIP + J_PLANE + p of {D, Db}
-__global__ __launch_bounds__(WAVES * 64, 8) void k_match_branch(Tables T, const uint8_t* __restrict__ text,
-                                                                const uint64_t* __restrict__ doc_begin,
-                                                                const uint64_t* __restrict__ doc_end,
-                                                                const uint64_t* __restrict__ doc_vis,
-                                                                const uint32_t* __restrict__ seg_doc,
-                                                                const uint64_t* __restrict__ doc_seg_start, uint64_t nseg,
+// Walks that leave the loop of step A1: three words a task - base or chain word, node, position | depth << 16 - in the part of Db that nothing
+// touches before step A3 (the dump words of streams without positions lie in Db[0..63]; the words used are zeroed again behind the walks, as
+// step A3 expects all of Db).  A chain head that finds the list full marks its position in a bitmap (Xb[160..169]; the dump words reach
+// Xb[151]) and is walked again from its first byte behind the tasks.
+constexpr int TAIL_TASK0 = 64, TAIL_TASKS = (NPOS - TAIL_TASK0) / 3, REDO0 = 160, REDO_WORDS = (NPOS + 31) / 32;
+static_assert(REDO0 + REDO_WORDS <= SEG && offsetof(WaveLds, Db) + 4 * 63 + 6 * 256 + 4 <= offsetof(WaveLds, Xb) + 4 * REDO0, "the bitmap lies behind the dump words");
+// par: the segment records of k_seg_fill.  slab == nullptr: the text is packed (`text`); else it lies in the normalizer's slabs.
+__global__ __launch_bounds__(WAVES * 64, 8) void k_match_branch(Tables T, const uint8_t* __restrict__ text, uint64_t nseg,
                                                                 uint32_t* __restrict__ R0, uint2* __restrict__ side,
                                                                 uint32_t* __restrict__ R1, uint32_t* __restrict__ exitmap, uint16_t* __restrict__ exit16,
-                                                                int narrow, int dbg, const uint8_t* __restrict__ slab, const uint4* __restrict__ seg_src,
+                                                                int narrow, int dbg, const uint8_t* __restrict__ slab, const uint4* __restrict__ par,
                                                                 const uint64_t* __restrict__ ctl = nullptr) {
   __shared__ uint8_t s_bb[256];
   __shared__ WaveLds s_wave[WAVES];
-  const int lane = threadIdx.x & 63, wvi = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // wave-uniform: the segment, its document and lengths live in SGPRs
+  const int lane = threadIdx.x & 63, wvi = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // wave-uniform: the segment and its lengths live in SGPRs
   TM_LDS_OBJECTS(s_bb, s_wave);
-  for (int j = threadIdx.x; j < 256; j += WAVES * 64) s_bb[j] = T.begin_byte[j];
-  __syncthreads();
+  PH_INIT
+  // The prologue is two dependent rounds of loads, not more: the segment's record (with the device's segment count, where there is one), then
+  // every word of its text at once.  A wavefront's life is a chain of memory round trips, and nothing in front of step A1 needs more of them.
   const uint64_t g = (uint64_t)blockIdx.x * WAVES + wvi;
+  const uint8_t* const bbp = T.begin_byte;
+  const uint4 rec = par[g < nseg ? g : nseg - 1];          // (nseg here: the bound the grid was sized for - a record that exists, whatever the device's count says)
   if (ctl) nseg = ctl[0];
+  // (left alone, the compiler fetches a kernel argument where it is first used and the record behind the test of g, a wait each: naming them
+  // here has the arguments of the prologue fetched with one wait, and the record asked for beside the device's count.  Behind the two
+  // loads, which stay scalar loads only in front of an asm statement.)
+  TM_HAVE_IN_SGPRS6(rec.x, rec.w, nseg, text, slab, bbp);
+  // begin_byte[] (first read by step A2): every wavefront stores all 256 bytes, a dword per lane, so that it waits for nobody's stores but its
+  // own - the four wavefronts write the same values - and the workgroup has no barrier in front of the one behind step A3.  The load is issued
+  // here and comes back with the text.
+  const uint32_t bbw = reinterpret_cast<const uint32_t*>(bbp)[lane];
   if (g >= nseg) return;
   WaveLds& w = s_wave[wvi];
   const int Lmax = TM_DBG_ON(dbg & 0x180000) ? min((dbg & 0x80000) ? 12 : 20, (int)T.max_len) : (int)T.max_len;      // (devel bits 19 / 20: no walk deeper than 12 / 20 bytes - what the deep tail of step A1 costs)
-  const unsigned long long lane_below = (1ull << lane) - 1ull;
   const uint32_t idle_off = T.idle_off;                   // the always-empty entry behind the double array
-  const uint32_t doc = seg_doc[g];
-  const uint64_t begin = doc_begin[doc] + (g - doc_seg_start[doc]) * SEG;
-  // A document owns the positions [doc_begin, doc_end) but may LOOK at text up to doc_vis >= doc_end: a byte range of a dataset
-  // that is scored as part of the whole-buffer walk (training/trainvocab.go:909-922) sees the text that follows it, and tokens that
-  // begin inside the range may end behind it.  For ordinary documents doc_vis == doc_end: the text ends with the document.
-  const uint64_t rem = doc_end[doc] - begin, remv = doc_vis[doc] - begin;
-  const int dl = remv > (uint64_t)(1 << 20) ? (1 << 20) : (int)remv;   // bytes of text from `begin` on that can be looked at (clamped)
-  const int seglen = (int)(rem < (uint64_t)SEG ? rem : (uint64_t)SEG);  // positions of this segment
-  const bool share = wvi + 1 < WAVES && g + 1 < nseg && __builtin_amdgcn_readfirstlane((int)seg_doc[g + 1]) == (int)doc;   // (then rem > SEG: the text goes on)
-  PH_INIT
+  const uint32_t rw = (uint32_t)__builtin_amdgcn_readfirstlane((int)rec.w);
+  const int dl = (int)(rw & ((1u << SP_DL_BITS) - 1u));   // bytes of text from the segment's begin on that can be looked at (clamped)
+  const int seglen = (int)((rw >> SP_LEN_SHIFT) & ((1u << SP_LEN_BITS) - 1u));  // positions of this segment
+  const bool share = wvi + 1 < WAVES && (rw & SP_SAME_DOC) != 0u;      // the next segment is this document's and its wavefront sits in this workgroup (then the text goes on)
+  const bool more_text = (rw & SP_MORE_TEXT) != 0u;       // text follows the segment: step C's chains leave it into an entry state
 
   // stage the text with (unaligned) dword loads; bytes at and after the end of the document read as 0: the pad
   // byte of go/tokenmonster.go:1038-1046 (quirk Q1: we define it as 0 like tokenmonster.cpp:1724-1726)
+  // One form for both places of the text: byte i of the segment is byte i of s0 while i < len0 and byte i of s1 behind that.  Packed text is
+  // one piece without an end.  In the slabs (one 2 KiB slab per piece of a document, the pieces' bytes never packed: tm_batch_normalize skips
+  // its compaction pass, that was 2.2 GB of traffic per GiB for something these loads do on the way) the record names the piece the segment
+  // begins in; a piece that is not the last of its document holds at least TEXT_LEN bytes - tm_batch_normalize packs the text after all when
+  // one does not -, so two pieces cover what a segment looks at.
   typedef uint32_t __attribute__((aligned(1))) u32u;
-  if (slab == nullptr) {
-    for (int j = lane; j < TEXT_LEN / 4; j += 64) {
-      uint32_t tw = 0;
-      if (4 * j < dl) {
-        // (non-temporal: with ordinary loads the kernel FETCHES 20 % more - the text lines push table lines out of the L2 - at the same time)
-        tw = TM_STREAM_LOAD(reinterpret_cast<const u32u*>(text + begin + 4 * j));
-        if (4 * j + 4 > dl) tw &= (1u << (8 * (dl - 4 * j))) - 1u;
-      }
-      reinterpret_cast<uint32_t*>(w.text)[j] = tw;
-    }
-  } else {
-    // The text as the device normalizer left it: one 2 KiB slab per piece of a document, the pieces' bytes not yet packed (tm_batch_normalize
-    // skips its compaction pass: that was 2.2 GB of traffic per GiB for something this loop does on the way).  `begin` and the documents'
-    // ranges stay positions in the packed text that never was; k_seg_src has found the piece the segment begins in: byte i of the segment is
-    // byte i of s0 while i < len0 and of the next piece's slab after that (a piece that is not the last of its document holds at least
-    // TEXT_LEN bytes - tm_batch_normalize packs the text after all when one does not -, so two pieces cover what a segment looks at).
-    const uint4 ss = seg_src[g];
-    const uint8_t* s0 = slab + (uint64_t)ss.x * SLAB_BYTES + ss.y;
-    const int len0 = (int)ss.z;
-    const uint8_t* s1 = slab + ((uint64_t)ss.x + 1) * SLAB_BYTES - len0;                // byte i >= len0 of the segment
-    for (int j = lane; j < TEXT_LEN / 4; j += 64) {
-      uint32_t tw = 0;
-      const int i = 4 * j;
-      if (i < dl) {
-        tw = TM_STREAM_LOAD(reinterpret_cast<const u32u*>((i + 4 <= len0 ? s0 : s1) + i));
-        const int n0 = len0 - i;                                                        // bytes of this word that lie in the first piece
-        if (n0 > 0 && n0 < 4) {
-          const uint32_t lo = TM_STREAM_LOAD(reinterpret_cast<const u32u*>(s0 + i)), m = (1u << (8 * n0)) - 1u;
-          tw = (lo & m) | (tw & ~m);
-        }
-        if (i + 4 > dl) tw &= (1u << (8 * (dl - i))) - 1u;
-      }
-      reinterpret_cast<uint32_t*>(w.text)[j] = tw;
-    }
+  const uint32_t rx = (uint32_t)__builtin_amdgcn_readfirstlane((int)rec.x), ry = (uint32_t)__builtin_amdgcn_readfirstlane((int)rec.y),
+                 rz = (uint32_t)__builtin_amdgcn_readfirstlane((int)rec.z);
+  const uint8_t *s0, *s1;
+  int len0;
+  if (slab == nullptr) { s0 = s1 = text + ((uint64_t)rx | ((uint64_t)ry << 32)); len0 = 0x7FFFFFF0; }
+  else { s0 = slab + (uint64_t)rx * SLAB_BYTES + ry; len0 = (int)rz; s1 = slab + ((uint64_t)rx + 1) * SLAB_BYTES - len0; }
+  // a lane's two words (TEXT_LEN / 4 = 88 over 64 lanes) and, where a word lies across the end of the first piece, the first piece's bytes of
+  // it: all of them are asked for before the first is waited for
+  static_assert(TEXT_LEN / 4 > 64 && TEXT_LEN / 4 <= 128 && TEXT_LEN % 4 == 0, "two words of text per lane");
+  const int i0 = 4 * lane, i1 = 4 * lane + 256;
+  const bool h0 = i0 < dl, h1 = i1 < TEXT_LEN && i1 < dl;
+  const int n00 = len0 - i0, n01 = len0 - i1;               // bytes of the word that lie in the first piece
+  const bool x0 = h0 && n00 > 0 && n00 < 4, x1 = h1 && n01 > 0 && n01 < 4;
+  uint32_t tw0 = 0u, tw1 = 0u, twx = 0u;
+  // (non-temporal: with ordinary loads the kernel FETCHES 20 % more - the text lines push table lines out of the L2 - at the same time)
+  if (h0) tw0 = TM_STREAM_LOAD(reinterpret_cast<const u32u*>((n00 >= 4 ? s0 : s1) + i0));
+  if (h1) tw1 = TM_STREAM_LOAD(reinterpret_cast<const u32u*>((n01 >= 4 ? s0 : s1) + i1));
+  if (x0 || x1) twx = TM_STREAM_LOAD(reinterpret_cast<const u32u*>(s0 + (x0 ? i0 : i1)));      // (at most one word of a segment)
+  // ... and while they are under way: D, Db and the bitmap of step A1 zeroed
+  static_assert((2 * NPOS * 4) % 16 == 0 && offsetof(WaveLds, D) % 16 == 0, "D and Db are zeroed as 16-byte words");
+  for (int j = lane; j < 2 * NPOS / 4; j += 64) reinterpret_cast<uint4*>(w.D)[j] = make_uint4(0u, 0u, 0u, 0u);      // D and Db
+  if (lane < REDO_WORDS) w.Xb[REDO0 + lane] = 0u;
+  reinterpret_cast<uint32_t*>(s_bb)[lane] = bbw;
+  {
+    const uint32_t mx = (1u << (8 * ((x0 ? n00 : n01) & 3))) - 1u;
+    if (x0) tw0 = (twx & mx) | (tw0 & ~mx);
+    if (x1) tw1 = (twx & mx) | (tw1 & ~mx);
+    if (h0 && i0 + 4 > dl) tw0 &= (1u << (8 * (dl - i0))) - 1u;
+    if (h1 && i1 + 4 > dl) tw1 &= (1u << (8 * (dl - i1))) - 1u;
+    reinterpret_cast<uint32_t*>(w.text)[lane] = tw0;
+    if (i1 < TEXT_LEN) reinterpret_cast<uint32_t*>(w.text)[lane + 64] = tw1;
   }
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_s_waitcnt(0);
+  PH(0)
 
   // ---- step A: descriptors for every position the segment can look at -----------------------------
   // What bounds this kernel is the number of divergent gathers (every lane of a probe touches its own cache line; the
@@ -432,10 +445,6 @@ __global__ __launch_bounds__(WAVES * 64, 8) void k_match_branch(Tables T, const 
   // start over at p+1 but follows the suffix link of n (tm_tables.h) — the state of the walk of text[p+1:] after the
   // bytes already known to match — and only probes for what may come after them.  ~3.1 gathers per position instead of
   // ~4.9 (two-byte map + one probe per further byte).  (pansearch LongestSubstring, call sites go/tokenmonster.go:1049..)
-  static_assert((2 * NPOS * 4) % 16 == 0 && offsetof(WaveLds, D) % 16 == 0, "D and Db are zeroed as 16-byte words");
-  for (int j = lane; j < 2 * NPOS / 4; j += 64) reinterpret_cast<uint4*>(w.D)[j] = make_uint4(0u, 0u, 0u, 0u);      // D and Db
-  __builtin_amdgcn_wave_barrier();
-  PH(0)
   PH_COUNT(12, 1)
   const int ntask = TM_DBG_ON(dbg & 1) ? 0 : (share ? SEG : min(NPOS, dl));       // positions >= dl keep descriptor 0 (nothing there); a shared halo is the neighbour's work
   // the walks of steps A1 and A3: a lane's state is its key — KEY_SET (A1: the gather is a link-format entry), KEY_IDLE (nothing to
@@ -542,12 +551,7 @@ __global__ __launch_bounds__(WAVES * 64, 8) void k_match_branch(Tables T, const 
     uint32_t v_link = T.link_off, v_direct = T.direct_off, v_idle = idle_off;
     TM_KEEP_IN_VGPRS2(v_link, v_direct);
     TM_KEEP_IN_VGPRS2(v_idle, v_link);            // operands of the selects: registers for the whole loop, not moves per round
-    // Walks that leave the loop (below): three words a task - base or chain word, node, position | depth << 16 - in the part of Db that nothing
-    // touches before step A3 (the dump words of streams without positions lie in Db[0..63]; the words used are zeroed again behind the walks, as
-    // step A3 expects all of Db).  A chain head that finds the list full marks its position in a bitmap (Xb[160..169]; the dump words reach
-    // Xb[151]) and is walked again from its first byte behind the tasks.
-    constexpr int TAIL_TASK0 = 64, TAIL_TASKS = (NPOS - TAIL_TASK0) / 3, REDO0 = 160, REDO_WORDS = (NPOS + 31) / 32;
-    static_assert(REDO0 + REDO_WORDS <= SEG && offsetof(WaveLds, Db) + 4 * 63 + 6 * 256 + 4 <= offsetof(WaveLds, Xb) + 4 * REDO0, "the bitmap lies behind the dump words");
+    // (walks that leave the loop go to the task list at Db[TAIL_TASK0], chain heads that find it full to the bitmap at Xb[REDO0]: above the kernel)
     // A walk that is DEFER bytes deep and wants to go on is handed to the task list as well: the deep end of a walk is what a lane's whole run
     // of positions waits for, and behind the loop the deep walks of a wavefront run side by side.  Measured (profiles/r05_k1_tails.txt, K1 per
     // 256 MiB, 32 000 / 100 256 ids): chains only 4.92 / 6.21 ms, DEFER 16: 4.90, 12: 4.85 / 6.14, 10: 4.87 / 6.18, 8: 5.14 / 6.71, 6: 5.31.
@@ -557,7 +561,6 @@ __global__ __launch_bounds__(WAVES * 64, 8) void k_match_branch(Tables T, const 
     constexpr int DEFER = TM_K1_DEFER_DEPTH;
     int ntask_tail = 0;
     bool redo_any = false;                       // (wave-uniform)
-    if (lane < REDO_WORDS) w.Xb[REDO0 + lane] = 0u;
     // the gather of a stream's next round and the LDS bytes that round may need - the next key byte, the first two bytes of the next position
     auto issue = [&](Run& r) {
       r.e = *reinterpret_cast<const uint4*>(tabb + r.off);
@@ -885,7 +888,6 @@ __global__ __launch_bounds__(WAVES * 64, 8) void k_match_branch(Tables T, const 
   // within itself (<= 6 rounds for <= 63 hops), then blocks 2, 1, 0 resolve against the (finished) blocks behind them.
   // (Rounds 2-6 doubled over all 2 x 256 states through a table in LDS, 4 reads + 4 writes and a full wait per round: K1 3.3 % slower.)
   {
-    const bool more_text = remv > (uint64_t)seglen;       // text follows the segment: the chain leaves it into an entry state
     // entry: #tokens [0..JF-1] | field [JF..30] | left-the-segment [31]; the field is the target state (p + SEG * fd) while the path is
     // inside the segment, the entry state of the next segment once it has left it (JNONE: the state is unreachable)
     constexpr uint32_t JF = 12, JCNT = (1u << JF) - 1u, JNONE = (1u << (31 - JF)) - 1u, JOUT = 0x80000000u;
@@ -2140,8 +2142,8 @@ namespace tmh {
 // directly, 11 = the device normalizer packs its text instead of leaving it in the slabs for K1, 12 = group tree of long documents with fan-out 4
 // from 9 segments on (a deep tree on a small document), 13 = a 64 KiB
 // mailbox for the small host <-> device transfers (wraps within a test), 14 = the last member of tm_score_multi gives up after the first
-// meeting of the members (an ERROR path: every member must return), 15 = K4's id-staging walk for two-plane rows too, 16 = k_segments and k_seg_src one
-// behind the other for a chunk of the host-to-host ring too (which has them in one launch, k_seg_fill), 24 = one chunk of a
+// meeting of the members (an ERROR path: every member must return), 15 = K4's id-staging walk for two-plane rows too, 16 = nothing any more (it split k_seg_fill into
+// two launches for a chunk of the host-to-host ring while the batch path had them apart; every caller has the one launch now), 24 = one chunk of a
 // tm_tokenize_pipeline call fails at a place of the host code named in TM_TEST_FAIL (an ERROR path, tm_host.hip: PipeCall::hook_arm; the bits 17 - 23
 // between belong to the -DTM_DEVEL build, and the match kernel reads 17 and 18 in every build).  Nothing else is
 // reachable in the default build.  With -DTM_DEVEL (tools/ only: results are WRONG) further bits switch
@@ -2376,19 +2378,15 @@ int pipeline_match(tm_batch* b, hipStream_t st, hipEvent_t* ev, bool for_score) 
   if (nd > 0) {
     TM_LAUNCH(k_doc_nseg, (nd + 255) / 256, 256, 0, st, b->d_doc_begin, b->d_doc_end, nd, b->d_doc_nseg, (uint32_t)SEG, b->d_error);
     scan_u32(b->d_doc_nseg, nd, b->d_scan_tmp, b->d_totals + 0, b->d_doc_seg_start, st);
-    if (nseg > 0 && b->d_ctl && b->text_in_slabs && !(debug_flags() & 65536))
-      TM_LAUNCH(k_seg_fill, (uint32_t)((nseg + 255) / 256), 256, 0, st, b->d_doc_seg_start, nd, b->d_doc_begin, b->d_doc_piece_start, b->d_piece_off, b->d_seg_doc, b->d_seg_par, b->d_ctl);
-    else if (nseg > 0) TM_LAUNCH(k_segments, (uint32_t)((nseg + 255) / 256), 256, 0, st, b->d_doc_seg_start, nd, nseg, b->d_seg_doc, b->d_ctl);
-    // the text still lies in the normalizer's slabs: where each segment begins in them (in d_seg_par, which K4's parameters take over after K3)
-    if (nseg > 0 && b->text_in_slabs && !(b->d_ctl && !(debug_flags() & 65536)))
-      TM_LAUNCH(k_seg_src, (uint32_t)((nseg + 255) / 256), 256, 0, st, b->d_seg_doc, b->d_doc_seg_start, b->d_doc_begin, b->d_doc_piece_start, b->d_piece_off, nseg, b->d_seg_par, b->d_ctl);
+    // the segments' documents and the records K1 starts from (in d_seg_par, which K4's parameters take over after K3), in one launch
+    if (nseg > 0)
+      TM_LAUNCH(k_seg_fill, (uint32_t)((nseg + 255) / 256), 256, 0, st, b->d_doc_seg_start, nd, b->d_doc_begin, b->d_doc_end, b->d_doc_vis ? b->d_doc_vis : b->d_doc_end,
+                b->text_in_slabs ? b->d_doc_piece_start : nullptr, b->d_piece_off, nseg, b->d_seg_doc, b->d_seg_par, b->d_ctl);
   }
   mark(1);
   if (nseg > 0)
-    TM_LAUNCH(k_match_branch, (uint32_t)((nseg + WAVES - 1) / WAVES), WAVES * 64, TM_K1_EXTRA_LDS, st, v->tables, b->d_text, b->d_doc_begin, b->d_doc_end,
-                                                                                          b->d_doc_vis ? b->d_doc_vis : b->d_doc_end, b->d_seg_doc,
-                                                                                          b->d_doc_seg_start, nseg, b->d_R0, b->d_side, b->d_R1, b->d_exitmap, b->d_exit16, r0_mode(b, for_score),
-                                                                                          debug_flags(), b->text_in_slabs ? b->d_slab : nullptr, b->d_seg_par, b->d_ctl);
+    TM_LAUNCH(k_match_branch, (uint32_t)((nseg + WAVES - 1) / WAVES), WAVES * 64, TM_K1_EXTRA_LDS, st, v->tables, b->d_text, nseg, b->d_R0, b->d_side, b->d_R1, b->d_exitmap,
+              b->d_exit16, r0_mode(b, for_score), debug_flags(), b->text_in_slabs ? b->d_slab : nullptr, b->d_seg_par, b->d_ctl);
     note_table_use(v, st);
   mark(2);
   for (size_t lvl = 0; lvl + 1 < b->level_first.size() && b->ngroups > 0; lvl++) {     // bottom up: a level reads the maps of the one below

@@ -1379,7 +1379,7 @@ static int batch_normalize_impl(tm_batch* b, void* stream, bool one_piece) {
                                             nullptr, b->d_need_host, b->d_piece_len, nullptr, b->d_slab, ninfo + 3, b->d_two, nullptr);
     TM_LAUNCH(k_norm_bad, (uint32_t)((std::max<uint64_t>(np, nd) + 255) / 256), 256, 0, st, b->d_piece_doc, b->d_need_host, b->d_doc_piece_start, np, nd, b->d_piece_len, ninfo, b->d_fb_ids, nullptr);
     scan_u32(b->d_piece_len, np, b->d_scan_tmp, reinterpret_cast<uint64_t*>(ninfo + 5), b->d_piece_off, st);      // (the total lands beside the info words: one copy brings everything)
-    // NO compaction pass here: in the usual case the text stays in the slabs and k_match_branch stages its segments from there (k_seg_src) —
+    // NO compaction pass here: in the usual case the text stays in the slabs and k_match_branch stages its segments from there (k_seg_fill) —
     // packing it was 2.2 GB of traffic and 0.8 ms per GiB; pack_text() below is for the cases that need the packed text after all
     TM_LAUNCH(k_norm_ranges_info, (nd + 255) / 256, 256, 0, st, b->d_piece_off, b->d_doc_piece_start, b->d_need_host, nd, b->d_nbegin, b->d_nend, ninfo, long_segs());
     { int rc = small_d2h(b, h_info, ninfo, 56, st); if (rc == TM_OK) rc = small_sync(b, st);

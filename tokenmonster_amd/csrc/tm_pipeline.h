@@ -182,7 +182,7 @@ struct tm_batch {
   uint16_t* d_exit16 = nullptr;        // per segment: 80 entries {next entry state | #ids << 7}, 0xFFFF = unreachable (exit_entry, tm_kernels.hip)
   uint8_t* d_seg_entry = nullptr;
   uint32_t* d_seg_tokbase = nullptr;
-  uint4* d_seg_par = nullptr;          // per segment: begin | length | entry state | first output index (k_seg_params)
+  uint4* d_seg_par = nullptr;          // per segment: what K1 starts from (k_seg_fill); behind K3: begin | length | entry state | first output index (k_seg_params)
   uint32_t* d_doc_ntok = nullptr;
   uint32_t* d_doc_events = nullptr;
   uint32_t* d_doc_missing = nullptr;
@@ -209,7 +209,7 @@ struct tm_batch {
   uint32_t* d_acc = nullptr;             // what `accents` leaves of the two-byte characters
   uint8_t* d_slab = nullptr;            // normalizer: one 2 KiB slab per 1 KiB piece
   uint64_t slab_pieces = 0;             // pieces of the batch that was normalized last (raw_pieces may already count the next upload)
-  bool text_in_slabs = false;           // the normalized text of this batch has not been packed into d_text: K1 stages it from the slabs (k_seg_src)
+  bool text_in_slabs = false;           // the normalized text of this batch has not been packed into d_text: K1 stages it from the slabs (k_seg_fill)
   uint64_t slab_cap = 0;
   uint64_t* d_raw_off = nullptr;
   uint64_t raw_cap = 0, raw_bytes = 0, raw_pieces = 0, piece_cap = 0;

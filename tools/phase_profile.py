@@ -33,11 +33,11 @@ for _ in range(reps):
 lib.tm_debug_phases(out, 0)
 v = np.array(list(out), dtype=np.float64)
 nseg = v[12]
-names = ["stage+zero", "B: rows + T(p,0)", "A1 main loop", "barrier wait", "A2", "A3", "B: T(p,1) + stores", "C"]
+names = ["prologue (entry -> text staged, D / Db zeroed)", "B: rows + T(p,0)", "A1 main loop", "barrier wait", "A2", "A3", "B: T(p,1) + stores", "C"]
 tot = v[:8].sum()
 print("segments %d (x%d passes), k_match_branch %.3f ms" % (nseg / reps, reps, ms[1]))
 for i, n in enumerate(names):
-    print("%-20s %9.0f cycles/segment  %5.1f %%" % (n, v[i] / nseg, 100 * v[i] / tot))
+    print("%-48s %9.0f cycles/segment  %5.1f %%" % (n, v[i] / nseg, 100 * v[i] / tot))
 print("total %.0f cycles/segment" % (tot / nseg))
 print("per segment: A1 loop rounds %.1f, walks handed to the task list %.1f, their rounds behind the loop %.1f, A3 + task probe rounds %.1f, C rounds %.1f, A3 tasks %.1f, (p,1) states %.1f"
       % (v[8] / nseg, v[9] / nseg, v[10] / nseg, v[11] / nseg, v[13] / nseg, v[14] / nseg, v[15] / nseg))
