@@ -231,6 +231,41 @@ func (hv *HipVocab) TokenizeBatchSpans(normalized [][]byte) ([][]uint32, [][]uin
 	}
 }
 
+// TokenizeBatchRawSpans takes RAW documents - normalized on the way, like CountBatchRaw - and returns the ids with their byte spans counted in
+// the raw documents: spans[d][2*k], spans[d][2*k+1] = begin and end of the bytes of document d that id k came from (tm_tokenize_batch_raw_spans).
+func (hv *HipVocab) TokenizeBatchRawSpans(raw [][]byte) ([][]uint32, [][]uint32, []int, error) {
+	n := len(raw)
+	text, offsets := pack(raw)
+	capTok := uint64(2*len(text) + 2*n + 64)
+	tokOff := make([]uint64, n+1)
+	missing := make([]uint32, n+1)
+	for {
+		out := make([]uint32, capTok+1)
+		spans := make([]uint32, 2*capTok+2)
+		rc, err := locked(func() C.int {
+			return C.tm_tokenize_batch_raw_spans(hv.h, (*C.uint8_t)(unsafe.Pointer(&text[0])), (*C.uint64_t)(unsafe.Pointer(&offsets[0])),
+				C.uint32_t(n), (*C.uint32_t)(unsafe.Pointer(&out[0])), C.uint64_t(capTok),
+				(*C.uint64_t)(unsafe.Pointer(&tokOff[0])), (*C.uint32_t)(unsafe.Pointer(&spans[0])), (*C.uint32_t)(unsafe.Pointer(&missing[0])))
+		})
+		if err != nil {
+			return nil, nil, nil, err
+		}
+		if rc == C.TM_E_NOSPACE {
+			capTok = tokOff[n]
+			continue
+		}
+		res := make([][]uint32, n)
+		sp := make([][]uint32, n)
+		miss := make([]int, n)
+		for i := range raw {
+			res[i] = out[tokOff[i]:tokOff[i+1]]
+			sp[i] = spans[2*tokOff[i] : 2*tokOff[i+1]]
+			miss[i] = int(missing[i])
+		}
+		return res, sp, miss, nil
+	}
+}
+
 // CountBatch is Count (go :971) over many RAW documents: server job 20.
 func (hv *HipVocab) CountBatch(docs [][]byte) ([]int, error) {
 	n := len(docs)

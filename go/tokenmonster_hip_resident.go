@@ -363,6 +363,32 @@ func (b *HipBatch) CollateSpans(how HipCollate, stream, spans unsafe.Pointer, sp
 	return err
 }
 
+// RawSpans is Spans counted in the RAW text of a batch that went through UploadRaw + Normalize + Run: uint32 [total ids][2], (begin, end) of the
+// bytes of the raw document every id came from (tm_batch_raw_spans).  Returns the number of documents that were mapped on the host.
+func (b *HipBatch) RawSpans(stream, spans unsafe.Pointer, capIds uint64) (uint32, error) {
+	var hostDocs C.uint32_t
+	_, err := locked(func() C.int { return C.tm_batch_raw_spans(b.h, stream, (*C.uint32_t)(spans), C.uint64_t(capIds), &hostDocs) })
+	return uint32(hostDocs), err
+}
+
+// RawSpansTimed is RawSpans with the milliseconds of its three parts - normalized pairs, origin pass, map - between HIP events on the stream
+// (tm_batch_raw_spans_timed); it synchronizes.
+func (b *HipBatch) RawSpansTimed(stream, spans unsafe.Pointer, capIds uint64) (uint32, [3]float32, error) {
+	var hostDocs C.uint32_t
+	var ms [3]C.float
+	_, err := locked(func() C.int {
+		return C.tm_batch_raw_spans_timed(b.h, stream, (*C.uint32_t)(spans), C.uint64_t(capIds), &hostDocs, &ms[0])
+	})
+	return uint32(hostDocs), [3]float32{float32(ms[0]), float32(ms[1]), float32(ms[2])}, err
+}
+
+// CollateRawSpans is CollateSpans counted in the raw text (tm_batch_collate_raw_spans).
+func (b *HipBatch) CollateRawSpans(how HipCollate, stream, spans unsafe.Pointer, spanBytes uint32) error {
+	h := how.c()
+	_, err := locked(func() C.int { return C.tm_batch_collate_raw_spans(b.h, &h, stream, spans, C.uint32_t(spanBytes)) })
+	return err
+}
+
 // PackRows is the number of rows Pack writes for these documents.
 func (b *HipBatch) PackRows(how HipCollate) (uint64, error) {
 	h := how.c()
@@ -409,6 +435,28 @@ func HipNormalize(data []byte, capcode, normFlag uint8) ([]byte, error) {
 	res := make([]byte, int(n))
 	copy(res, unsafe.Slice((*byte)(unsafe.Pointer(out)), int(n))) // (not C.GoBytes: its length is a C int)
 	return res, nil
+}
+// HipNormalizeOrigins is HipNormalize with the origin of every byte: own[k] is the offset in data of the first byte of the character (unit)
+// that normalized byte k came from (tm_normalize_origins).
+func HipNormalizeOrigins(data []byte, capcode, normFlag uint8) ([]byte, []uint32, error) {
+	if len(data) == 0 {
+		return []byte{}, []uint32{}, nil
+	}
+	var out *C.uint8_t
+	var own *C.uint32_t
+	var n C.size_t
+	if _, err := locked(func() C.int {
+		return C.tm_normalize_origins((*C.uint8_t)(unsafe.Pointer(&data[0])), C.size_t(len(data)), C.uint32_t(capcode), C.uint32_t(normFlag), &out, &n, &own)
+	}); err != nil {
+		return nil, nil, err
+	}
+	defer C.tm_free(unsafe.Pointer(out))
+	defer C.tm_free(unsafe.Pointer(own))
+	res := make([]byte, int(n))
+	copy(res, unsafe.Slice((*byte)(unsafe.Pointer(out)), int(n)))
+	owners := make([]uint32, int(n))
+	copy(owners, unsafe.Slice((*uint32)(unsafe.Pointer(own)), int(n)))
+	return res, owners, nil
 }
 func HipNormalizeBatch(docs [][]byte, capcode, normFlag uint8, threads int) ([]byte, []uint64, error) {
 	text, offsets := pack(docs)

@@ -45,6 +45,15 @@ int tm_vocab_build_all(struct tm_devices* g, const uint8_t* blob, const uint32_t
 /* Host-side normalize + capcode (go/tokenmonster.go:242-253).  Returns a malloc'd buffer. */
 int tm_normalize(const uint8_t* data, size_t n, uint32_t capcode, uint32_t norm_flag, uint8_t** out,
                  size_t* out_n);
+/* tm_normalize with the origin of every byte it writes: *out / *out_n are byte for byte tm_normalize's, own_out[*out_n] the raw offset of the
+ * first byte of the UNIT that owns each normalized byte (both malloc'd: tm_free).  A unit is one character of the raw text (a well-formed
+ * UTF-8 sequence; a byte that belongs to none is a unit by itself); a stretch of characters whose combining marks NFD puts into another order
+ * is ONE unit, from its first character to its last.  The bytes a character turns into (lower-casing, NFD, Hangul jamo) are its own; so are
+ * the marker bytes capcode writes in front of its letter ("D ", "DC ", "DW ", the space behind a 'W' / 'C' that took the place of a raw space);
+ * a 'W' / 'C' that overwrites a raw space is the space's; the space `leadingspace` invents belongs to offset 0.  own never decreases.  This
+ * is the map tm_batch_raw_spans (tokenmonster_hip.h) applies, and the reference for the device's own.  Every flag set tm_normalize takes;
+ * n < 2^32. */
+int tm_normalize_origins(const uint8_t* data, size_t n, uint32_t capcode, uint32_t norm_flag, uint8_t** out, size_t* out_n, uint32_t** own_out);
 /* The way back for ONE byte string (a token, a decoded fragment): capcode decoding as Vocab.Denormalize does it (go/tokenmonster.go:445-462;
  * tokenmonster-cpp/src/tokenmonster.cpp:3248-3253) - level 2 by the decoder of javascript/tokenmonster.js:1007-1065, level 1 drops the 0x7F
  * marker and the character behind it, level 0 copies.  Host code (token lists are small); documents go through tm_decode_batch.  Returns a

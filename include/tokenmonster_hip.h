@@ -309,7 +309,7 @@ int tm_batch_load_ids(tm_batch* b, const void* rows, uint32_t nrows, uint32_t ro
 /* The walk stands at byte i of a document when it emits an id and then moves on by that token's advance: the id's span is [i, i + advance),
  * counted in bytes from the document's start in the NORMALIZED text the walk runs on - after tm_batch_upload_raw + tm_batch_normalize the text
  * tm_batch_download_text returns (the raw text itself for a vocabulary with capcode 0 and no normalization flags); mapping a span back through
- * the normalizer to offsets of the raw text is not done here (the follow-up).  The delete token a forward-delete branch emits behind a token
+ * the normalizer to offsets of the raw text is what tm_batch_raw_spans below does.  The delete token a forward-delete branch emits behind a token
  * gets the empty span at that token's end; a character without a token gets [i, i + 1) when the vocabulary has an unk token and otherwise
  * leaves no id, hence a gap; a token may advance by 0 bytes (a one-byte alternative in a forward-delete state): its span is empty.  Begins
  * never decrease and the spans of a document never overlap.  Neither the ids nor a decode give the spans back (the "D " duplicates of a
@@ -333,6 +333,37 @@ int tm_batch_collate_spans(tm_batch* b, const tm_collate* how, void* stream, voi
  * written to tokens_out and spans_out, and TM_E_NOSPACE is returned. */
 int tm_tokenize_batch_spans(const tm_vocab* v, const uint8_t* text, const uint64_t* offsets, uint32_t ndocs,
                             uint32_t* tokens_out, uint64_t tokens_cap, uint64_t* tok_offsets, uint32_t* spans_out, uint32_t* missing);
+
+/* ---- raw-text spans: the same pairs as offsets into the bytes the caller uploaded ---------------------------------------------------------- */
+/* After tm_batch_upload_raw + tm_batch_normalize + tm_batch_run, the span of every id counted in bytes from its document's start in the RAW
+ * text.  Every normalized byte is owned by one unit of the raw document (tm_build.h, tm_normalize_origins: a character; the bytes it turns
+ * into and the capcode markers in front of its letter are its own, a 'W' / 'C' over a raw space is the space's); own[n] is the raw offset
+ * of the owner of normalized byte n.  An id with the normalized span [nb, ne), ne > nb, gets [own[nb], next(ne - 1)): next(n) is the first
+ * own[n'] > own[n] with n' > n, or the raw length of the document - so what the normalizer drops (a collapsed space, a '\r', a removed mark)
+ * falls into the span in front of it, and the spans of a document of a vocabulary with an unk token tile it.  An id without bytes (a delete
+ * token, a step that consumes none) gets the empty span (x, x), x = next(nb - 1), or 0 at the document's start.
+ *  - Begins and ends never decrease.
+ *  - Two neighbouring ids may have the SAME or overlapping raw spans: a token boundary inside one character's output ("D" | " h" are both
+ *    that 'H'), or inside a stretch whose combining marks NFD reordered (one unit on the host).
+ *  - With capcode 0 and normalization flags 0 the raw spans ARE the normalized spans.
+ * The documents the device normalized, of a vocabulary with capcode 0 or 2 and no flag but NFD and lowercase, are mapped on the device (the
+ * normalizer's exact path again over the resident raw text, writing owners instead of text); every other document - those the normalizer left
+ * to the host, and all of them under accents, quotemarks, collapse, trim, leadingspace or unixlines - is fetched back, mapped by
+ * tm_normalize_origins on the host and its owners uploaded; *host_docs (may be NULL) receives their number.  The owners live in a grow-only
+ * buffer of the batch (4 bytes per normalized byte, counted in tm_batch_device_bytes) made on request only: tm_batch_normalize and
+ * tm_batch_run do nothing for it.  The call waits for the run like tm_batch_spans, and for its own host part where there is one; it changes
+ * nothing a later call reads.
+ * Slot order, alignment, TM_E_NOSPACE (nothing written) and the errors of tm_batch_spans / tm_batch_collate_spans / tm_tokenize_batch_spans
+ * apply unchanged; besides: a batch whose text did not come from tm_batch_upload_raw + tm_batch_normalize: TM_E_INVALID; a raw document of
+ * 2^32 bytes or more: TM_E_LIMIT.  Not offered for tm_tokenize_pipeline, tm_tokenize_document, the streaming encoder and tm_batch_pack. */
+int tm_batch_raw_spans(tm_batch* b, void* stream, uint32_t* spans_out, uint64_t spans_cap, uint32_t* host_docs);
+/* As tm_batch_raw_spans, with its three parts between HIP events on `stream`: ms[0] the normalized pairs (tm_batch_spans' pass), ms[1] the
+ * origin pass (with the host's share where documents are mapped there), ms[2] the map.  Synchronizes.  ms NULL: tm_batch_raw_spans. */
+int tm_batch_raw_spans_timed(tm_batch* b, void* stream, uint32_t* spans_out, uint64_t spans_cap, uint32_t* host_docs, float* ms);
+int tm_batch_collate_raw_spans(tm_batch* b, const tm_collate* how, void* stream, void* spans_out, uint32_t span_bytes);
+/* tm_tokenize_batch_spans for RAW documents: normalize, run and map on a lane, like tm_count_batch_raw. */
+int tm_tokenize_batch_raw_spans(const tm_vocab* v, const uint8_t* raw, const uint64_t* offsets, uint32_t ndocs,
+                                uint32_t* tokens_out, uint64_t tokens_cap, uint64_t* tok_offsets, uint32_t* spans_out, uint32_t* missing);
 
 /* Streaming Decoder (go/tokenmonster.go:552-700 NewDecoder / Decode / DecodeSerialized / Flush; server jobs 5-9): ids arrive a few
  * at a time, a call returns the text that is COMPLETE so far; the bytes of a character that is not (a token may end in the middle of a

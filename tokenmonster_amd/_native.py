@@ -85,6 +85,10 @@ SIGNATURES = {
     "tm_batch_spans": (C.c_int, [vp, vp, vp, C.c_uint64]),
     "tm_batch_collate_spans": (C.c_int, [vp, vp, vp, vp, C.c_uint32]),
     "tm_tokenize_batch_spans": (C.c_int, [vp, vp, vp, C.c_uint32, vp, C.c_uint64, vp, vp, vp]),
+    "tm_batch_raw_spans": (C.c_int, [vp, vp, vp, C.c_uint64, u32p]),
+    "tm_batch_raw_spans_timed": (C.c_int, [vp, vp, vp, C.c_uint64, u32p, f32p]),
+    "tm_batch_collate_raw_spans": (C.c_int, [vp, vp, vp, vp, C.c_uint32]),
+    "tm_tokenize_batch_raw_spans": (C.c_int, [vp, vp, vp, C.c_uint32, vp, C.c_uint64, vp, vp, vp]),
     "tm_decoder_new":(C.c_int, [vp, C.POINTER(vp)]),
     "tm_decoder_free": (None, [vp]),
     "tm_decoder_decode": (C.c_int, [vp, vp, C.c_uint64, vp, C.c_uint64, u64p]),
@@ -137,6 +141,7 @@ SIGNATURES = {
     "tm_tok_read": (C.c_int, [vp, C.c_size_t, vp, C.POINTER(vp), C.POINTER(vp), u32p, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), u32p]),
     "tm_tok_write": (C.c_int, [vp, vp, vp, C.c_uint32, vp, vp, vp, C.c_uint32, C.POINTER(vp), C.POINTER(C.c_size_t)]),
     "tm_normalize": (C.c_int, [vp, C.c_size_t, C.c_uint32, C.c_uint32, C.POINTER(vp), C.POINTER(C.c_size_t)]),
+    "tm_normalize_origins": (C.c_int, [vp, C.c_size_t, C.c_uint32, C.c_uint32, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(vp)]),
     "tm_denormalize": (C.c_int, [vp, C.c_size_t, C.c_uint32, C.POINTER(vp), C.POINTER(C.c_size_t)]),
     "tm_normalize_batch": (C.c_int, [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(vp), vp]),
 }

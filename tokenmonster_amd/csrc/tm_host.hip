@@ -422,6 +422,37 @@ int tm_tokenize_batch_spans(const tm_vocab* v, const uint8_t* text, const uint64
   return rc;
 }
 
+int tm_tokenize_batch_raw_spans(const tm_vocab* v, const uint8_t* raw, const uint64_t* offsets, uint32_t ndocs, uint32_t* tokens_out,
+                                uint64_t tokens_cap, uint64_t* tok_offsets, uint32_t* spans_out, uint32_t* missing) {
+  if (!v || (ndocs && !offsets)) return set_error(TM_E_INVALID, "null argument");
+  Lane* l = nullptr;
+  int rc = lane_acquire(v, &l);
+  if (rc != TM_OK) return rc;
+  RunOut ro;
+  rc = lane_run(l, v, raw, offsets, ndocs, true, true, &ro);
+  if (rc == TM_OK) {
+    tm_batch* b = l->ws;
+    if (tok_offsets) rc = small_d2h(b, tok_offsets, b->d_tok_offsets, ((uint64_t)ndocs + 1) * 8, l->stream);
+    if (rc == TM_OK && missing && ndocs) rc = small_d2h(b, missing, b->d_doc_missing, (uint64_t)ndocs * 4, l->stream);
+    if (rc == TM_OK && ro.total_tokens > tokens_cap) {
+      (void)small_sync(b, l->stream);
+      rc = set_error(TM_E_NOSPACE, "tokens_cap %llu < %llu required", (unsigned long long)tokens_cap, (unsigned long long)ro.total_tokens);
+    }
+    if (rc == TM_OK && ro.total_tokens && (!tokens_out || !spans_out)) rc = set_error(TM_E_INVALID, "null argument");
+    // the raw pairs behind the run on the lane's stream, in place in the workspace's own buffer
+    if (rc == TM_OK) rc = spans_ready(b, "tm_tokenize_batch_raw_spans");
+    if (rc == TM_OK) rc = origin_ready(b, "tm_tokenize_batch_raw_spans");
+    if (rc == TM_OK) rc = spans_reserve(b, ro.total_tokens);
+    if (rc == TM_OK) rc = batch_raw_spans_on(b, l->stream, b->d_spans, ro.total_tokens, nullptr);
+    if (rc == TM_OK) rc = small_d2h(b, tokens_out, b->d_out, ro.total_tokens * 4, l->stream);
+    if (rc == TM_OK) rc = small_d2h(b, spans_out, b->d_spans, ro.total_tokens * 8, l->stream);
+    if (rc == TM_OK) rc = small_sync(b, l->stream); else (void)small_sync(b, l->stream);
+    if (ndocs == 0 && tok_offsets) tok_offsets[0] = 0;
+  }
+  lane_release(v, l);
+  return rc;
+}
+
 static int count_batch(const tm_vocab* v, const uint8_t* text, const uint64_t* offsets, uint32_t ndocs, bool raw, uint64_t* counts, uint32_t* missing) {
   if (!v || (ndocs && !offsets)) return set_error(TM_E_INVALID, "null argument");
   Lane* l = nullptr;

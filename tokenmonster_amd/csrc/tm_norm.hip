@@ -2,6 +2,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cstring>
 #include <mutex>
@@ -309,8 +310,17 @@ __global__ void k_norm_carry(const uint32_t* __restrict__ piece_sum, const uint6
 // private slab (SLAB bytes apart; a piece that would not fit raises the overflow flag) and the length.  MODE 3: a vocabulary WITHOUT
 // capcode in one pass, as k_norm_emit2<false> is for capcode 2: nothing is known about the documents beforehand (no k_norm_summary /
 // k_norm_carry: without capcode a byte's output depends on nothing but its character), the bytes go into the slabs, and a piece that finds
-// a byte it cannot normalize marks its document in need_host.
+// a byte it cannot normalize marks its document in need_host.  MODE 4: the origin pass behind tm_batch_raw_spans - the same path over the
+// resident raw text with the carries given, but no text: for every normalized byte, packed at piece_off like MODE 1's text, the offset in the
+// raw document of the first byte of the character whose lane wrote it (`out` is that array of u32; need_host and piece_len are only read).
 constexpr int SLAB = 2 * PIECE;
+// the first byte of the character that byte x of a staged piece belongs to: steps back over its continuation bytes (the documents the device
+// normalizes are well-formed UTF-8: anything else is NF_BAD and the host's)
+__device__ __forceinline__ uint32_t norm_lead_back(const uint8_t* raw_x) {
+  uint32_t back = 0;
+  while (back < 3u && (raw_x[-(int)back] & 0xC0u) == 0x80u) back++;
+  return back;
+}
 static_assert(SLAB == SLAB_BYTES, "k_match_branch stages the text from these slabs");
 template <int MODE>
 __global__ __launch_bounds__(256) void k_norm_emit(const uint8_t* __restrict__ raw, const uint64_t* __restrict__ rbegin,
@@ -334,10 +344,17 @@ __global__ __launch_bounds__(256) void k_norm_emit(const uint8_t* __restrict__ r
   if (k >= npieces) return;
   PieceLds& L = s_l[wv];
   const uint32_t d = piece_doc[k];
-  if (MODE != 3 && need_host[d]) { if (MODE != 1 && lane == 0) piece_len[k] = 0; return; }
+  if (MODE != 3 && need_host[d]) { if (MODE != 1 && MODE != 4 && lane == 0) piece_len[k] = 0; return; }
   const uint64_t rb = rbegin[d], re = rend[d], pb = rb + (k - doc_piece_start[d]) * PIECE;
   const int m = norm_load_piece(L, raw, rb, re, pb, lane, s_cls, &s_tab, two);
-  uint8_t* dst = MODE == 1 ? out + piece_off[k] : (MODE >= 2 ? out + k * (uint64_t)SLAB : nullptr);
+  uint8_t* dst = MODE == 1 ? out + piece_off[k] : ((MODE == 2 || MODE == 3) ? out + k * (uint64_t)SLAB : nullptr);
+  // MODE 4: where the piece's owners go, what they count from, and how many there are (the pass that wrote the text left the length)
+  uint32_t* own = MODE == 4 ? reinterpret_cast<uint32_t*>(out) + piece_off[k] : nullptr;
+  const uint32_t own_base = MODE == 4 ? (uint32_t)(pb - rb) : 0u, own_n = MODE == 4 ? piece_len[k] : 0u;
+  if (MODE == 4 && capcode != 2) {                          // no capcode: byte i of the piece is byte i of its output
+    for (int i = lane; i < m && (uint32_t)i < own_n; i += 64) own[i] = own_base + (uint32_t)i - norm_lead_back(L.raw + PMARGIN + i);
+    return;
+  }
   if (capcode != 2 || MODE == 3) {                          // no capcode: same length, only the lower-case flag applies
     if (MODE != 1 && lane == 0) piece_len[k] = (uint32_t)m;
     bool bad = false;
@@ -465,7 +482,13 @@ __global__ __launch_bounds__(256) void k_norm_emit(const uint8_t* __restrict__ r
       const unsigned long long bq = __ballot(len >= q);
       incl = __builtin_amdgcn_mbcnt_hi((uint32_t)(bq >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bq, incl));
     }
-    if (WRITE && in && (MODE == 1 || pos + incl <= (uint32_t)SLAB)) {
+    if (MODE == 4) {
+      if (in && pos + incl <= own_n) {
+        const uint32_t o = own_base + (uint32_t)i - norm_lead_back(L.raw + x);
+        uint32_t* w = own + pos + (incl - len);
+        for (uint32_t q = 0; q < len; q++) w[q] = o;
+      }
+    } else if (WRITE && in && (MODE == 1 || pos + incl <= (uint32_t)SLAB)) {
       uint8_t* w = dst + pos + (incl - len);
       if (len == 4) { w[0] = (uint8_t)o0; w[1] = (uint8_t)o1; w[2] = (uint8_t)o2; w[3] = (uint8_t)o3; }
       else if (len == 3) { w[0] = (uint8_t)o1; w[1] = (uint8_t)o2; w[2] = (uint8_t)o3; }
@@ -474,7 +497,7 @@ __global__ __launch_bounds__(256) void k_norm_emit(const uint8_t* __restrict__ r
     }
     pos += __shfl(incl, 63);
   }
-  if (MODE != 1 && lane == 0) {
+  if (MODE != 1 && MODE != 4 && lane == 0) {
     piece_len[k] = pos;
     if (MODE == 2 && pos > (uint32_t)SLAB) atomicAdd(overflow, 1ull);
   }
@@ -1534,6 +1557,117 @@ int tm_batch_normalize(tm_batch* b, void* stream) { return batch_normalize_impl(
 
 }  // extern "C"
 namespace tmh {
+// ---- the origin pass (tm_batch_raw_spans, tm_spans.hip) ---------------------------------------------------------------------------------------
+// For every byte of the batch's normalized text, where the documents' ranges (d_nbegin) put it, the offset in its RAW document of the first byte
+// of the unit that owns it (tm_build.h: tm_normalize_origins) - a u32 per normalized byte in the batch's grow-only d_own.  The documents the
+// device normalized, of a vocabulary without a filter pass, get theirs from k_norm_emit<4> over the resident raw text, with the carries of
+// k_norm_summary + k_norm_carry (made again here: the one-pass normalizer never makes them) - the carry kernel's document flags and list go to
+// a scratch buffer, nothing the normalizer left is written.  Every other document - the host-normalized ones; all of them under a byte-level
+// flag or `accents` - is fetched back from d_raw, mapped by normalize_origins on the pooled workers and its owners uploaded.
+int origin_ready(const tm_batch* b, const char* who) {
+  if (!b->d_nbegin || b->d_doc_begin != b->d_nbegin || b->raw_docs != b->ndocs || !b->d_raw)
+    return set_error(TM_E_INVALID, "%s: the batch's text did not come from tm_batch_upload_raw + tm_batch_normalize (there is no raw text to point into)", who);
+  for (uint32_t d = 0; d < b->ndocs; d++)
+    if (b->h_raw_off[d + 1] - b->h_raw_off[d] >= (1ull << 32))
+      return set_error(TM_E_LIMIT, "%s: document %u has %llu raw bytes (offsets are 32 bits)", who, d, (unsigned long long)(b->h_raw_off[d + 1] - b->h_raw_off[d]));
+  return TM_OK;
+}
+
+int origin_pass_on(tm_batch* b, hipStream_t st, uint32_t* host_docs) {
+  if (host_docs) *host_docs = 0;
+  const uint32_t nd = b->ndocs;
+  if (nd == 0 || b->nbytes == 0) return TM_OK;
+  const uint32_t capcode = b->vocab->host.capcode, norm_flag = b->vocab->host.norm_flag;
+  hipError_t e;
+  if (b->nbytes > b->own_cap) {
+    if (b->own_cap) trace_grow("origins", b->nbytes * 4);
+    (void)hipFree(b->d_own);
+    b->device_bytes -= b->own_cap * 4;
+    b->d_own = nullptr; b->own_cap = 0;
+    const uint64_t cap = b->nbytes + b->nbytes / 4 + 1024;
+    if ((e = batch_alloc_bytes(b, (void**)&b->d_own, cap * 4)) != hipSuccess) return hip_fail(e, "hipMalloc origins");
+    b->own_cap = cap;
+  }
+  // scratch of the carry kernel: need_host[nd] | ninfo[8] | fb_ids[nd]
+  const uint64_t o_info = ((uint64_t)nd + 7) & ~7ull, o_ids = o_info + 64, tmp_bytes = o_ids + (uint64_t)nd * 4;
+  if (tmp_bytes > b->own_tmp_cap) {
+    (void)hipFree(b->d_own_tmp);
+    b->device_bytes -= b->own_tmp_cap;
+    b->d_own_tmp = nullptr; b->own_tmp_cap = 0;
+    const uint64_t cap = tmp_bytes + tmp_bytes / 4 + 256;
+    if ((e = batch_alloc_bytes(b, (void**)&b->d_own_tmp, cap)) != hipSuccess) return hip_fail(e, "hipMalloc origins");
+    b->own_tmp_cap = cap;
+  }
+  (void)hipGetLastError();
+  const bool on_device = (norm_flag & ~3u) == 0u && (capcode == 0 || capcode == 2);
+  const uint64_t np = b->slab_pieces;
+  std::vector<uint8_t> need(nd, 1);
+  if (on_device) {
+    const uint32_t lower_all = (norm_flag & 2u) ? 1u : 0u;
+    const uint32_t pgrid = (uint32_t)((np + 3) / 4);
+    const uint64_t* RB = b->d_raw_off;
+    const uint64_t* RE = b->d_raw_off + 1;
+    if (np > 0 && capcode == 2) {
+      TM_LAUNCH(k_norm_summary, pgrid, 256, 0, st, b->d_raw, RB, RE, b->d_piece_doc, b->d_doc_piece_start, np, lower_all, b->d_two, b->d_piece_sum);
+      (void)hipMemsetAsync(b->d_own_tmp + o_info, 0, 64, st);
+      TM_LAUNCH(k_norm_carry, (nd + 255) / 256, 256, 0, st, b->d_piece_sum, b->d_doc_piece_start, nd, b->d_piece_carry, b->d_own_tmp,
+                (unsigned long long*)(b->d_own_tmp + o_info), reinterpret_cast<uint32_t*>(b->d_own_tmp + o_ids), 0u);
+    }
+    if (np > 0)
+      TM_LAUNCH(k_norm_emit<4>, pgrid, 256, 0, st, b->d_raw, RB, RE, b->d_piece_doc, b->d_doc_piece_start, np, capcode, lower_all, b->d_piece_carry,
+                b->d_need_host, b->d_piece_len, b->d_piece_off, reinterpret_cast<uint8_t*>(b->d_own), nullptr, b->d_two, nullptr);
+    if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "kernel launch");
+    if (b->host_fallback_docs == 0) return TM_OK;
+    if ((e = hipMemcpyAsync(need.data(), b->d_need_host, nd, hipMemcpyDeviceToHost, st)) != hipSuccess) return hip_fail(e, "D2H document flags");
+  }
+  // the host's documents: ranges, raw bytes (neighbouring documents in one copy), owners
+  std::vector<uint64_t> nb(nd), ne(nd);
+  if ((e = hipMemcpyAsync(nb.data(), b->d_nbegin, (size_t)nd * 8, hipMemcpyDeviceToHost, st)) != hipSuccess ||
+      (e = hipMemcpyAsync(ne.data(), b->d_nend, (size_t)nd * 8, hipMemcpyDeviceToHost, st)) != hipSuccess || (e = hipStreamSynchronize(st)) != hipSuccess)
+    return hip_fail(e, "D2H ranges");
+  std::vector<uint32_t> ids;
+  uint64_t lo = ~0ull, hi = 0;
+  for (uint32_t d = 0; d < nd; d++) if (need[d]) { ids.push_back(d); lo = std::min(lo, nb[d]); hi = std::max(hi, ne[d]); }
+  if (host_docs) *host_docs = (uint32_t)ids.size();
+  if (ids.empty() || hi <= lo) return TM_OK;
+  if (hi > b->nbytes) return set_error(TM_E_INTERNAL, "origin pass: a document's range ends at %llu of %llu normalized bytes", (unsigned long long)hi, (unsigned long long)b->nbytes);
+  const std::vector<uint64_t>& ro = b->h_raw_off;
+  std::vector<uint8_t> rawh;
+  std::vector<uint64_t> at(ids.size());
+  {
+    uint64_t total = 0;
+    for (size_t k = 0; k < ids.size(); k++) { at[k] = total; total += ro[ids[k] + 1] - ro[ids[k]]; }
+    rawh.resize(total + 1);
+    for (size_t k = 0; k < ids.size();) {
+      size_t j = k + 1;
+      while (j < ids.size() && ids[j] == ids[j - 1] + 1) j++;
+      const uint64_t s = ro[ids[k]], n = ro[ids[j - 1] + 1] - s;
+      if (n && (e = hipMemcpyAsync(rawh.data() + at[k], b->d_raw + s, n, hipMemcpyDeviceToHost, st)) != hipSuccess) return hip_fail(e, "D2H raw documents");
+      k = j;
+    }
+    if ((e = hipStreamSynchronize(st)) != hipSuccess) return hip_fail(e, "D2H raw documents");
+  }
+  std::vector<uint32_t> stage(hi - lo, 0u);
+  static const uint32_t host_share = std::max(8u, std::max(1u, std::thread::hardware_concurrency()) / (uint32_t)std::max(1, tm_device_count()));
+  const uint32_t threads = (uint32_t)std::min<size_t>(std::min<size_t>(std::min<uint32_t>(128u, host_share), ids.size() / 8 + 1), (size_t)(rawh.size() >> 16) + 1);
+  std::atomic<uint32_t> next{0};
+  std::atomic<int> bad{0};
+  run_on_workers(threads, [&]() {
+    std::vector<uint8_t> text;
+    std::vector<uint32_t> own;
+    for (;;) {
+      const uint32_t k = next.fetch_add(1);
+      if (k >= ids.size()) break;
+      const uint32_t d = ids[k];
+      if (!normalize_origins(rawh.data() + at[k], (size_t)(ro[d + 1] - ro[d]), capcode, norm_flag, text, own) || own.size() != ne[d] - nb[d]) { bad = 1; continue; }
+      if (!own.empty()) std::memcpy(stage.data() + (nb[d] - lo), own.data(), own.size() * 4);
+    }
+  });
+  if (bad) return set_error(TM_E_INTERNAL, "origin pass: the host's owners do not fit the batch's normalized text");
+  if ((e = hipMemcpyAsync(b->d_own + lo, stage.data(), stage.size() * 4, hipMemcpyHostToDevice, st)) != hipSuccess || (e = hipStreamSynchronize(st)) != hipSuccess)
+    return hip_fail(e, "H2D owners");
+  return TM_OK;
+}
 // The host-to-host ring takes a vocabulary whose normalizer pass is the one-pass form (capcode 0 or 2 with flags the device implements)
 bool ring_supported(const tm_vocab* v) {
   const uint32_t capcode = v->host.capcode, norm_flag = v->host.norm_flag;

@@ -760,6 +760,328 @@ void normalize_bytes(const uint8_t* data, size_t n, uint32_t capcode, uint32_t n
   else out.swap(tmp);
 }
 
+// ---- the normalizer with owners (tm_normalize_origins) -----------------------------------------------------------------------------------
+// Siblings of the passes above that carry, beside every byte, the raw offset of the first byte of the UNIT that owns it (tm_build.h: a unit is
+// one character of the raw document as next_cp decodes it, a byte that belongs to none by itself; a stretch whose marks NFD reorders is one
+// unit).  normalize_bytes and its passes stay as they are - this is what maps the ids' spans back to the raw text, not the hot host path - and
+// normalize_origins compares its bytes with theirs before it returns.
+namespace {
+
+struct Owned {
+  std::vector<uint8_t> b;
+  std::vector<uint32_t> o;
+  void push(uint8_t x, uint32_t own) { b.push_back(x); o.push_back(own); }
+  void append(const uint8_t* p, size_t n, uint32_t own) { b.insert(b.end(), p, p + n); o.insert(o.end(), n, own); }
+  void append(const Owned& s, size_t from, size_t to) {
+    b.insert(b.end(), s.b.begin() + (ptrdiff_t)from, s.b.begin() + (ptrdiff_t)to);
+    o.insert(o.end(), s.o.begin() + (ptrdiff_t)from, s.o.begin() + (ptrdiff_t)to);
+  }
+};
+
+void squeeze_own(Owned& t, bool quotes, bool collapse, bool fused_unix) {      // squeeze, in place like it: an output byte keeps the owner of the byte it was
+  std::vector<uint8_t>& b = t.b;
+  std::vector<uint32_t>& o = t.o;
+  const size_t n = b.size();
+  size_t on = 0;
+  uint8_t last = 0;
+  for (size_t i = 0; i < n; i++) {
+    const uint8_t c = b[i];
+    if (collapse && c == ' ') { if (last != ' ') { b[on] = ' '; o[on++] = o[i]; } last = ' '; continue; }
+    if (fused_unix && c == '\n' && last == '\r') { b[on - 1] = '\n'; o[on - 1] = o[i]; last = '\n'; continue; }      // (the '\r' is the byte that goes)
+    last = c;
+    if (quotes && (c == 0x98 || c == 0x99 || c == 0x9C || c == 0x9D) && i > 1 && b[i - 1] == 0x80 && b[i - 2] == 0xE2) {
+      b[on - 2] = c < 0x9C ? '\'' : '"';                      // (the owner of the quote's first byte stays where it is)
+      on--;
+      continue;
+    }
+    b[on] = c; o[on++] = o[i];
+  }
+  b.resize(on); o.resize(on);
+}
+void unix_lines_own(Owned& t) {
+  const size_t n = t.b.size();
+  if (n < 2) return;
+  size_t on = 0;
+  for (size_t i = 0; i + 1 < n; i++) if (!(t.b[i] == '\r' && t.b[i + 1] == '\n')) { t.b[on] = t.b[i]; t.o[on++] = t.o[i]; }
+  t.b[on] = t.b[n - 1]; t.o[on++] = t.o[n - 1];
+  t.b.resize(on); t.o.resize(on);
+}
+void trim_and_lead_own(Owned& t, bool trim, bool lead) {
+  const ptrdiff_t n = (ptrdiff_t)t.b.size();
+  // the invented space belongs to the first unit of the document
+  auto add_lead = [](Owned& x) { if (!x.b.empty() && x.b[0] != ' ') { x.b.insert(x.b.begin(), ' '); x.o.insert(x.o.begin(), 0u); } };
+  auto cut = [](Owned& x, ptrdiff_t from, ptrdiff_t to) {
+    x.b = std::vector<uint8_t>(x.b.begin() + from, x.b.begin() + to);
+    x.o = std::vector<uint32_t>(x.o.begin() + from, x.o.begin() + to);
+  };
+  if (!trim) { if (lead) add_lead(t); return; }
+  ptrdiff_t i = 0, i2 = n - 1;
+  while (i < n && t.b[(size_t)i] <= 32) i++;
+  while (i2 >= 0 && t.b[(size_t)i2] <= 32) i2--;
+  if (i2 < 0) { t.b.clear(); t.o.clear(); return; }
+  if (!lead) { cut(t, i, i2 + 1); return; }
+  if (i == 0) { t.b.resize((size_t)i2); t.o.resize((size_t)i2); add_lead(t); return; }
+  t.b[(size_t)(i - 1)] = ' ';                                 // (a blank of the document turned into the leading space: its own owner)
+  cut(t, i - 1, i2 + 1);
+}
+
+void utf8_of(const icu::UnicodeString& u, std::string& s) { s.clear(); u.toUTF8String(s); }
+
+// A run of bytes no well-formed character claims, as ICU reads it: one U+FFFD per maximal ill-formed subsequence.  One per byte where the
+// counts agree; otherwise (a truncated sequence of several bytes gave one) the run is one unit.
+void bad_run_own(const Owned& in, size_t from, size_t to, Owned& out) {
+  icu::UnicodeString u = icu::UnicodeString::fromUTF8(icu::StringPiece((const char*)in.b.data() + from, (int32_t)(to - from)));
+  std::string s;
+  utf8_of(u, s);
+  const size_t per = (size_t)u.length() == to - from ? s.size() / (to - from) : 0;
+  for (size_t k = 0; k < s.size(); k++) out.push((uint8_t)s[k], in.o[per ? from + k / per : from]);
+}
+
+void nfd_own(Owned& t) {
+  if (is_ascii(t.b.data(), t.b.size())) return;
+  UErrorCode status = U_ZERO_ERROR;
+  const icu::Normalizer2* nz = icu::Normalizer2::getNFDInstance(status);
+  Owned out;
+  out.b.reserve(t.b.size() + t.b.size() / 8 + 16); out.o.reserve(out.b.capacity());
+  const size_t n = t.b.size();
+  std::string whole, one, cat;
+  std::vector<uint32_t> cat_own;
+  size_t i = 0;
+  while (i < n) {
+    // (an ASCII character is a stretch by itself unless marks follow it: "a" + two marks NFD swaps is one stretch, from the letter on)
+    if (!(t.b[i] & 0x80) && (i + 1 >= n || !(t.b[i + 1] & 0x80))) { out.push(t.b[i], t.o[i]); i++; continue; }
+    Cp c = next_cp(&t.b[i], n - i);
+    size_t j = i;
+    if (c.raw) {                                              // bytes of no character, up to the next character
+      while (j < n && (t.b[j] & 0x80)) { const Cp x = next_cp(&t.b[j], n - j); if (!x.raw) break; j++; }
+      bad_run_own(t, i, j, out);
+      i = j;
+      continue;
+    }
+    // a stretch between two NFD boundaries: its first character and every following one that has none in front of it
+    j = i + (size_t)c.n;
+    while (j < n && (t.b[j] & 0x80)) {
+      const Cp x = next_cp(&t.b[j], n - j);
+      if (x.raw || nz->hasBoundaryBefore((UChar32)x.r)) break;
+      j += (size_t)x.n;
+    }
+    icu::UnicodeString o;
+    nz->normalize(icu::UnicodeString::fromUTF8(icu::StringPiece((const char*)t.b.data() + i, (int32_t)(j - i))), o, status);
+    utf8_of(o, whole);
+    cat.clear(); cat_own.clear();
+    for (size_t k = i; k < j;) {
+      const Cp x = next_cp(&t.b[k], n - k);
+      icu::UnicodeString oc;
+      nz->normalize(icu::UnicodeString((UChar32)x.r), oc, status);
+      utf8_of(oc, one);
+      cat += one;
+      cat_own.insert(cat_own.end(), one.size(), t.o[k]);
+      k += (size_t)x.n;
+    }
+    // the characters' own results in a row: every byte belongs to its character.  Anything else - NFD put the marks into another order - is one unit.
+    const bool same = cat == whole;
+    for (size_t k = 0; k < whole.size(); k++) out.push((uint8_t)whole[k], same ? cat_own[k] : t.o[i]);
+    i = j;
+  }
+  t.b.swap(out.b); t.o.swap(out.o);
+}
+
+// lower_bytes lower-cases the whole text at once (the final sigma looks at its neighbours): the whole result, walked beside the characters'
+// own lower-case forms - which have the same lengths in UTF-16 units (sigma's two forms are one unit each)
+bool lower_own(Owned& t) {
+  bool need = false;
+  for (auto x : t.b) if ((x & 0x80) || (x >= 'A' && x <= 'Z')) { need = true; break; }
+  if (!need) return true;
+  icu::UnicodeString u = icu::UnicodeString::fromUTF8(icu::StringPiece((const char*)t.b.data(), (int32_t)t.b.size()));
+  u.toLower(icu::Locale::getRoot());
+  Owned out;
+  out.b.reserve(t.b.size() + 16); out.o.reserve(t.b.size() + 16);
+  const size_t n = t.b.size();
+  int32_t at = 0;
+  std::string s;
+  for (size_t i = 0; i < n;) {
+    const Cp c = next_cp(&t.b[i], n - i);
+    size_t j = i + (size_t)c.n;
+    int32_t units;
+    if (c.raw) {
+      while (j < n) { const Cp x = next_cp(&t.b[j], n - j); if (!x.raw) break; j++; }
+      units = icu::UnicodeString::fromUTF8(icu::StringPiece((const char*)t.b.data() + i, (int32_t)(j - i))).length();
+      if (at + units > u.length()) return false;
+      utf8_of(u.tempSubString(at, units), s);
+      const size_t per = (size_t)units == j - i ? s.size() / (j - i) : 0;
+      for (size_t k = 0; k < s.size(); k++) out.push((uint8_t)s[k], t.o[per ? i + k / per : i]);
+    } else {
+      icu::UnicodeString lc((UChar32)c.r);
+      lc.toLower(icu::Locale::getRoot());
+      units = lc.length();
+      if (at + units > u.length()) return false;
+      utf8_of(u.tempSubString(at, units), s);
+      out.append((const uint8_t*)s.data(), s.size(), t.o[i]);
+    }
+    at += units;
+    i = j;
+  }
+  if (at != u.length()) return false;
+  t.b.swap(out.b); t.o.swap(out.o);
+  return true;
+}
+
+void remove_marks_own(Owned& t) {
+  nfd_own(t);
+  Owned out;
+  for (size_t i = 0; i < t.b.size();) {
+    const Cp c = next_cp(t.b.data() + i, t.b.size() - i);
+    if (c.raw || u_charType((UChar32)c.r) != U_NON_SPACING_MARK) out.append(t, i, i + (size_t)c.n);
+    i += (size_t)c.n;
+  }
+  t.b.swap(out.b); t.o.swap(out.o);
+}
+
+// mark_run_letters: the "DC " in front of a letter of the run belongs to that letter
+void mark_run_letters_own(Owned& buf, size_t from) {
+  Owned tail;
+  tail.append(buf, from, buf.b.size());
+  buf.b.resize(from); buf.o.resize(from);
+  const std::vector<uint8_t>& tb = tail.b;
+  size_t i = 0, n = tb.size();
+  while (i < n) {
+    if (tb[i] == 'D' && i + 1 < n && tb[i + 1] == ' ') {
+      bool lower_next = false; int ln = 0;
+      if (i + 2 < n) { Cp c = next_cp(&tb[i + 2], n - (i + 2)); lower_next = (classify(c) & kLower) != 0; ln = c.n; }
+      if (lower_next) {
+        buf.append((const uint8_t*)"DC ", 3, tail.o[i + 2]);
+        buf.append(tail, i + 2, i + 2 + (size_t)ln);
+        i += 2 + (size_t)ln;
+      } else {
+        size_t skip = 2;
+        if (i + 2 < n) skip += (size_t)next_cp(&tb[i + 2], n - (i + 2)).n;
+        if (i + skip > n) skip = n - i;
+        buf.append(tail, i, i + skip);
+        i += skip;
+      }
+      continue;
+    }
+    Cp c = next_cp(&tb[i], n - i);
+    if (classify(c) & kLower) buf.append((const uint8_t*)"DC ", 3, tail.o[i]);
+    buf.append(tail, i, i + (size_t)c.n);
+    i += (size_t)c.n;
+  }
+}
+
+// capcode_encode, statement for statement: markers written in front of a character's letter belong to that character, a 'W' / 'C' that
+// overwrites a space stays the space's
+void capcode_encode_own(const Owned& src, Owned& buf) {
+  const uint8_t* in = src.b.data();
+  const size_t n = src.b.size();
+  buf.b.clear(); buf.o.clear();
+  buf.b.reserve(n + n / 2 + 8); buf.o.reserve(n + n / 2 + 8);
+  size_t goback = 0, word_token_pos = 0;
+  Last last, last2;
+  bool in_word = false, multi = false;
+  size_t i = 0;
+  while (i < n) {
+    if (!in_word && (last.space || last.letter) && in[i] - 'a' < 26u) {
+      size_t j = i;
+      while (j < n) {
+        const uint8_t x = in[j];
+        if (x - 'a' < 26u) j++;
+        else if (x == ' ' && j + 1 < n && in[j + 1] - 'a' < 26u) j++;
+        else break;
+      }
+      buf.append(src, i, j);
+      Last letter; letter.letter = true;
+      Last space; space.space = true;
+      if (j - i >= 2) last2 = in[j - 2] == ' ' ? space : letter; else last2 = last;
+      last = letter;
+      i = j;
+      continue;
+    }
+    Cp c = next_cp(in + i, n - i);
+    uint8_t cls = classify(c);
+    const uint32_t own = src.o[i];
+    auto lower = [&]() { std::vector<uint8_t> l; put_lower(l, c); buf.append(l.data(), l.size(), own); };
+    auto mark = [&](const char* m, size_t k) { buf.append((const uint8_t*)m, k, own); };
+    if (in_word) {
+      if (cls & kUpper) {
+        if (!last.joiner()) mark("D ", 2);
+        multi = true;
+        lower();
+      } else {
+        if (cls & kLower) {
+          in_word = false;
+          buf.b[word_token_pos] = 'C';
+          if (multi) mark_run_letters_own(buf, goback);
+          if (!last.joiner()) mark("D ", 2);
+        } else if (cls & kDigit) {
+          if (!last.digit) mark("D ", 2);
+        } else if (!((!c.raw && (c.r == '\'' || c.r == 0x2019)) || (cls & kMark))) {
+          in_word = false;
+        }
+        buf.append(src, i, i + (size_t)c.n);
+      }
+    } else {
+      if (cls & kLower) {
+        if (!(last.space || last.letter || (last2.letter && last.apostrophe) || last.mark)) mark("D ", 2);
+        buf.append(src, i, i + (size_t)c.n);
+      } else if (cls & kUpper) {
+        if (last.space) {
+          word_token_pos = buf.b.size() - 1;
+          buf.b[word_token_pos] = 'W';
+          mark(" ", 1);
+        } else {
+          mark("D", 1);
+          word_token_pos = buf.b.size();
+          mark("W ", 2);
+        }
+        lower();
+        goback = buf.b.size();
+        multi = false;
+        in_word = true;
+      } else if (cls & kDigit) {
+        if (!(last.space || last.digit)) mark("D ", 2);
+        buf.append(src, i, i + (size_t)c.n);
+      } else {
+        buf.append(src, i, i + (size_t)c.n);
+      }
+    }
+    last2 = last;
+    last = describe(c, cls);
+    i += (size_t)c.n;
+  }
+}
+
+}  // namespace
+
+// normalize_bytes with the owner of every byte it writes; false if the bytes came out different from normalize_bytes' (a fault of this file)
+bool normalize_origins(const uint8_t* data, size_t n, uint32_t capcode, uint32_t norm_flag, std::vector<uint8_t>& out, std::vector<uint32_t>& own) {
+  Owned t;
+  t.b.assign(data, data + n);
+  t.o.resize(n);
+  for (size_t i = 0; i < n;) {
+    const Cp c = next_cp(data + i, n - i);
+    for (int k = 0; k < c.n; k++) t.o[i + (size_t)k] = (uint32_t)i;
+    i += (size_t)c.n;
+  }
+  bool ok = true;
+  if (norm_flag > 1) {
+    const bool q = norm_flag & 8, c = norm_flag & 16, u = norm_flag & 128;
+    if (u && c) squeeze_own(t, q, true, true);
+    else {
+      if (u) unix_lines_own(t);
+      if (q || c) squeeze_own(t, q, c, false);
+    }
+    if (norm_flag & (32 | 64)) trim_and_lead_own(t, norm_flag & 32, norm_flag & 64);
+  }
+  if (norm_flag & 4) { remove_marks_own(t); if (norm_flag & 2) ok = lower_own(t); }
+  else if (norm_flag & 2) { if (norm_flag & 1) nfd_own(t); ok = lower_own(t); }
+  else if (norm_flag & 1) nfd_own(t);
+  if (capcode == 2) { Owned e; capcode_encode_own(t, e); t.b.swap(e.b); t.o.swap(e.o); }
+  std::vector<uint8_t> plain;
+  normalize_bytes(data, n, capcode, norm_flag, plain);
+  out.swap(t.b); own.swap(t.o);
+  return ok && out == plain;
+}
+
 void capcode_decode_batch(const uint8_t* text, const uint64_t* offsets, uint32_t ndocs, uint32_t capcode, uint32_t threads,
                           std::vector<std::vector<uint8_t>>& outs) {
   outs.assign(ndocs, {});
@@ -837,6 +1159,24 @@ int tm_normalize(const uint8_t* data, size_t n, uint32_t capcode, uint32_t norm_
   *out = (uint8_t*)std::malloc(o.size() ? o.size() : 1);
   if (!*out) { *out_n = 0; return tmh::set_error(TM_E_HIP, "out of host memory (%zu bytes)", o.size()); }
   if (!o.empty()) std::memcpy(*out, o.data(), o.size());
+  *out_n = o.size();
+  return TM_OK;
+}
+
+int tm_normalize_origins(const uint8_t* data, size_t n, uint32_t capcode, uint32_t norm_flag, uint8_t** out, size_t* out_n, uint32_t** own_out) {
+  if (!out || !out_n || !own_out || (n && !data)) return tmh::set_error(TM_E_INVALID, "null argument");
+  if (!tmh::normalize_supported(capcode, norm_flag))
+    return tmh::set_error(TM_E_INVALID, "normalization flags %u / capcode %u not supported by the host normalizer", norm_flag, capcode);
+  if (n >= (1ull << 32)) return tmh::set_error(TM_E_LIMIT, "tm_normalize_origins: a document of %zu bytes (owners are 32 bits)", n);
+  std::vector<uint8_t> o;
+  std::vector<uint32_t> w;
+  *out = nullptr; *own_out = nullptr; *out_n = 0;
+  if (!tmh::normalize_origins(data, n, capcode, norm_flag, o, w))
+    return tmh::set_error(TM_E_INTERNAL, "tm_normalize_origins: the owner-carrying normalizer and tm_normalize disagree about the text");
+  *out = (uint8_t*)std::malloc(o.size() ? o.size() : 1);
+  *own_out = (uint32_t*)std::malloc(o.size() ? o.size() * 4 : 4);
+  if (!*out || !*own_out) { std::free(*out); std::free(*own_out); *out = nullptr; *own_out = nullptr; return tmh::set_error(TM_E_HIP, "out of host memory (%zu bytes)", o.size() * 5); }
+  if (!o.empty()) { std::memcpy(*out, o.data(), o.size()); std::memcpy(*own_out, w.data(), o.size() * 4); }
   *out_n = o.size();
   return TM_OK;
 }

@@ -246,6 +246,10 @@ struct tm_batch {
   int row_form = -1;                    // the form of the T(p,0) rows the last id-emitting run left (k_match_branch's `narrow`: 0 one plane of u32 words, 1 u16 + u8, 2 u32 + u8); -1: the ids did not come from a walk
   uint2* d_spans = nullptr;             // tm_batch_collate_spans / tm_tokenize_batch_spans: the ragged (begin, end) pairs of the ids, grow-only (tm_spans.hip)
   uint64_t spans_cap = 0;
+  uint32_t* d_own = nullptr;            // tm_batch_raw_spans: per byte of the normalized text, the raw offset of the unit that owns it, grow-only (origin pass, tm_norm.hip)
+  uint64_t own_cap = 0;
+  uint8_t* d_own_tmp = nullptr;         // ... and what k_norm_carry writes on the side when the origin pass runs it again
+  uint64_t own_tmp_cap = 0;
   uint16_t* d_out16 = nullptr;          // set for the length of a launch: K4 writes two-byte ids here instead (a chunk of the ring, launch_emit)
   uint64_t out16_cap = 0;
   // a chunk of the host-to-host ring (tm_host.hip): what the host would have read back between the stages - the number of segments the normalizer
@@ -328,6 +332,12 @@ int ensure_output(tm_batch* b);
 int spans_ready(const tm_batch* b, const char* who);
 int spans_reserve(tm_batch* b, uint64_t n);
 int batch_spans_on(tm_batch* b, hipStream_t st, void* out, uint64_t total);
+// tm_norm.hip: origin_ready - the batch's text came from tm_batch_upload_raw + tm_batch_normalize and every raw document is shorter than 2^32
+// bytes; origin_pass_on - the owner of every normalized byte into b->d_own (indexed like the documents' ranges d_doc_begin), *host_docs = the
+// documents mapped on the host.  Reads what the normalizer and the run left, changes none of it.
+int origin_ready(const tm_batch* b, const char* who);
+int origin_pass_on(tm_batch* b, hipStream_t st, uint32_t* host_docs);
+int batch_raw_spans_on(tm_batch* b, hipStream_t st, void* out, uint64_t total, uint32_t* host_docs, float* ms = nullptr);      // tm_spans.hip: spans_reserve, batch_spans_on, origin_pass_on, k_raw_spans
 // small device <-> host transfers that bypass the copy engines (tm_kernels.hip).  small_d2h's destination is filled by small_sync
 // (which synchronizes the stream); small_h2d's source may be reused as soon as the call returns (pageable memory, or at most MAIL_MAX bytes).
 constexpr uint64_t MAIL_BYTES = 4ull << 20, MAIL_MAX = 1ull << 20;
@@ -398,5 +408,6 @@ void launch_enc_pack(const tm_batch* b, uint64_t from, uint64_t n, uint8_t* dst,
 // tm_normalize.cpp
 bool normalize_supported(uint32_t capcode, uint32_t norm_flag);
 bool normalize_on_device(uint32_t capcode, uint32_t norm_flag);
+bool normalize_origins(const uint8_t* data, size_t n, uint32_t capcode, uint32_t norm_flag, std::vector<uint8_t>& out, std::vector<uint32_t>& own);      // tm_normalize_origins
 
 }  // namespace tmh

@@ -226,6 +226,35 @@ __global__ __launch_bounds__(256) void k_collate_spans(CollateArgs a, Flat f, co
   flat_store<T>(out, e0, cnt, vals);
 }
 
+// ---- k_raw_spans: the pairs mapped back through the normalizer ----------------------------------------------------------------------------------------
+// Id t of the run, with the normalized pair (nb, ne) of its document d: own[nbegin[d] + n] is the raw offset of the unit that owns normalized
+// byte n (the origin pass, tm_norm.hip).  The raw pair is (own(nb), next(ne - 1)) - next(n) the owner of the first byte behind n that has
+// another one, or the raw length of the document - and (x, x) with x = next(nb - 1), or 0 at the document's start, for an id without bytes.
+// A unit writes a bounded number of bytes, so next() is a short scan.  `in` and `out` may be the same array: a work-item reads and writes its
+// own pair only.
+__global__ __launch_bounds__(256) void k_raw_spans(const span_t* in, const uint64_t* __restrict__ tok_offsets, uint32_t ndocs,
+                                                   const uint64_t* __restrict__ nbegin, const uint64_t* __restrict__ nend, const uint64_t* __restrict__ raw_off,
+                                                   const uint32_t* __restrict__ own, uint64_t total, span_t* out) {
+  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= total) return;
+  uint32_t lo = 0, hi = ndocs;                        // the last document whose first id is not behind t (documents without ids share their offset with the next)
+  while (hi - lo > 1u) { const uint32_t mid = lo + (hi - lo) / 2u; if (tok_offsets[mid] <= t) lo = mid; else hi = mid; }
+  const uint32_t d = lo;
+  const span_t s = in[t];
+  const uint64_t nlen = nend[d] - nbegin[d];
+  const uint32_t rawlen = (uint32_t)(raw_off[d + 1] - raw_off[d]);
+  const uint32_t* __restrict__ o = own + nbegin[d];
+  auto next = [&](uint64_t n) {
+    const uint32_t me = o[n];
+    for (n++; n < nlen; n++) { const uint32_t v = o[n]; if (v != me) return v; }
+    return rawlen;
+  };
+  span_t r;
+  if (s.y > s.x && s.y <= nlen) { r.x = o[s.x]; r.y = next((uint64_t)s.y - 1u); }
+  else { r.x = (s.x == 0u || s.x > nlen) ? 0u : next((uint64_t)s.x - 1u); r.y = r.x; }
+  out[t] = r;
+}
+
 // ---- host side ----------------------------------------------------------------------------------------------------------------------------------------
 int spans_ready(const tm_batch* b, const char* who) {
   if (!b->has_output || b->row_form < 0 || b->d_ctl)
@@ -273,6 +302,42 @@ int batch_spans_on(tm_batch* b, hipStream_t st, void* out, uint64_t total) {
   return launch_check();
 }
 
+// the raw pairs of the run into `out` (device or page-locked, 8-byte aligned): the normalized pairs into the batch's own buffer, the owners
+// (origin pass), then the map
+// ms (tm_batch_raw_spans_timed): the three parts between HIP events on `st` - normalized pairs, origin pass, map; synchronizes
+int batch_raw_spans_on(tm_batch* b, hipStream_t st, void* out, uint64_t total, uint32_t* host_docs, float* ms) {
+  if (host_docs) *host_docs = 0;
+  if (ms) ms[0] = ms[1] = ms[2] = 0.f;
+  if (total == 0 || b->nseg == 0) return TM_OK;
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  hipError_t e = hipSuccess;
+  if (ms) for (int k = 0; k < 4 && e == hipSuccess; k++) e = hipEventCreate(&ev[k]);
+  auto mark = [&](int k) { if (ms && e == hipSuccess) e = hipEventRecord(ev[k], st); };
+  int rc = TM_OK;
+  mark(0);
+  // capcode 0 without normalization flags: the normalizer is the identity and so is the map, byte for byte (no rounding to characters)
+  const bool identity = b->vocab->host.capcode == 0 && b->vocab->host.norm_flag == 0;
+  if (identity) rc = batch_spans_on(b, st, out, total);
+  else if ((rc = spans_reserve(b, total)) == TM_OK) rc = batch_spans_on(b, st, b->d_spans, total);
+  mark(1);
+  if (rc == TM_OK && !identity) rc = origin_pass_on(b, st, host_docs);
+  mark(2);
+  if (rc == TM_OK && !identity) {
+    (void)hipGetLastError();
+    TM_LAUNCH(k_raw_spans, grid_of(total), 256, 0, st, reinterpret_cast<const span_t*>(b->d_spans), b->d_tok_offsets, b->ndocs, b->d_doc_begin, b->d_doc_end,
+              b->d_raw_off, b->d_own, total, static_cast<span_t*>(out));
+    rc = launch_check();
+  }
+  mark(3);
+  if (ms) {
+    if (e == hipSuccess) e = hipEventSynchronize(ev[3]);
+    for (int k = 0; k < 3 && e == hipSuccess; k++) e = hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]);
+    for (int k = 0; k < 4; k++) if (ev[k]) (void)hipEventDestroy(ev[k]);
+    if (rc == TM_OK && e != hipSuccess) rc = hip_fail(e, "HIP events");
+  }
+  return rc;
+}
+
 template <typename T>
 static void launch_collate_spans(const CollateArgs& a, const uint32_t* spans, void* out, hipStream_t st) {
   const Flat f = flat_of(out, 2ull * a.rows * a.L, sizeof(T));
@@ -313,6 +378,45 @@ int tm_batch_collate_spans(tm_batch* b, const tm_collate* how, void* stream, voi
   if ((rc = spans_check_lengths(b, "tm_batch_collate_spans")) != TM_OK || (rc = spans_reserve(b, total)) != TM_OK) return rc;
   hipStream_t st = (hipStream_t)stream;
   if ((rc = batch_spans_on(b, st, b->d_spans, total)) != TM_OK) return rc;      // the ragged pairs first, into the batch's own buffer
+  (void)hipGetLastError();
+  const CollateArgs a{nullptr, b->d_tok_offsets + how->first_doc, how->ndocs, how->row_len, how->pad_id, how->bos_id, how->eos_id, how->flags};
+  if (span_bytes == 4) launch_collate_spans<uint32_t>(a, reinterpret_cast<const uint32_t*>(b->d_spans), spans_out, st);
+  else launch_collate_spans<uint64_t>(a, reinterpret_cast<const uint32_t*>(b->d_spans), spans_out, st);
+  return launch_check();
+}
+
+int tm_batch_raw_spans(tm_batch* b, void* stream, uint32_t* spans_out, uint64_t spans_cap, uint32_t* host_docs) {
+  return tm_batch_raw_spans_timed(b, stream, spans_out, spans_cap, host_docs, nullptr);
+}
+
+int tm_batch_raw_spans_timed(tm_batch* b, void* stream, uint32_t* spans_out, uint64_t spans_cap, uint32_t* host_docs, float* ms) {
+  if (!b) return set_error(TM_E_INVALID, "tm_batch_raw_spans: null argument");
+  if (host_docs) *host_docs = 0;
+  int rc = spans_ready(b, "tm_batch_raw_spans");
+  if (rc != TM_OK || (rc = origin_ready(b, "tm_batch_raw_spans")) != TM_OK) return rc;
+  if (reinterpret_cast<uintptr_t>(spans_out) % 8) return set_error(TM_E_INVALID, "tm_batch_raw_spans: spans_out not aligned to 8 bytes (a pair leaves in one store)");
+  if ((rc = enter_device(b->vocab)) != TM_OK || (rc = ensure_output(b)) != TM_OK) return rc;
+  const uint64_t total = b->ndocs ? b->last_totals[1] : 0;
+  if (total > spans_cap) return set_error(TM_E_NOSPACE, "tm_batch_raw_spans: spans_cap %llu < %llu ids", (unsigned long long)spans_cap, (unsigned long long)total);
+  if (total && !spans_out) return set_error(TM_E_INVALID, "tm_batch_raw_spans: null argument");
+  if ((rc = spans_check_lengths(b, "tm_batch_raw_spans")) != TM_OK) return rc;
+  return batch_raw_spans_on(b, (hipStream_t)stream, spans_out, total, host_docs, ms);
+}
+
+int tm_batch_collate_raw_spans(tm_batch* b, const tm_collate* how, void* stream, void* spans_out, uint32_t span_bytes) {
+  int rc = check_how(b, how, spans_out, "tm_batch_collate_raw_spans");
+  if (rc != TM_OK) return rc;
+  if (span_bytes != 4 && span_bytes != 8) return set_error(TM_E_INVALID, "tm_batch_collate_raw_spans: span_bytes %u (4 or 8)", span_bytes);
+  const uint32_t ns = (how->bos_id != TM_NONE ? 1u : 0u) + (how->eos_id != TM_NONE ? 1u : 0u);
+  if (how->row_len < ns) return set_error(TM_E_INVALID, "tm_batch_collate_raw_spans: row_len %u holds no %u specials", how->row_len, ns);
+  if ((uint64_t)how->ndocs * how->row_len > COLLATE_MAX_ELEMS) return set_error(TM_E_LIMIT, "tm_batch_collate_raw_spans: %u rows of %u ids in one call (split the documents)", how->ndocs, how->row_len);
+  if ((rc = spans_ready(b, "tm_batch_collate_raw_spans")) != TM_OK || (rc = origin_ready(b, "tm_batch_collate_raw_spans")) != TM_OK) return rc;
+  if ((rc = enter_device(b->vocab)) != TM_OK || (rc = ensure_output(b)) != TM_OK) return rc;
+  if (how->ndocs == 0) return TM_OK;
+  const uint64_t total = b->last_totals[1];
+  if ((rc = spans_check_lengths(b, "tm_batch_collate_raw_spans")) != TM_OK || (rc = spans_reserve(b, total)) != TM_OK) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  if ((rc = batch_raw_spans_on(b, st, b->d_spans, total, nullptr, nullptr)) != TM_OK) return rc;      // the ragged raw pairs, where the normalized ones lay
   (void)hipGetLastError();
   const CollateArgs a{nullptr, b->d_tok_offsets + how->first_doc, how->ndocs, how->row_len, how->pad_id, how->bos_id, how->eos_id, how->flags};
   if (span_bytes == 4) launch_collate_spans<uint32_t>(a, reinterpret_cast<const uint32_t*>(b->d_spans), spans_out, st);

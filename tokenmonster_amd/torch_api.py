@@ -150,7 +150,13 @@ def encode_batch(vocab, docs, max_length, *, pad_id, bos_id=None, eos_id=None, p
     [bos] ids [eos] pad...: the ids cut to max_length less the specials given (their head; keep_tail: their tail), the padding on the
     right (pad_left: on the left).  return_offsets=True adds "offset_mapping" [rows, max_length, 2] int64: (begin, end) of the bytes the id
     of a column came from, counted from the document's start in the normalized text the tokenizer walks (raw=True: what Vocab.normalize
-    makes of the document), and (0, 0) on BOS, EOS and padding (tm_batch_collate_spans)."""
+    makes of the document), and (0, 0) on BOS, EOS and padding (tm_batch_collate_spans).  return_offsets="raw" (with raw=True only): the same
+    pairs counted in the bytes of the document as it was passed in (tm_batch_collate_raw_spans)."""
+    if isinstance(return_offsets, str):
+        if return_offsets != "raw":
+            raise ValueError("return_offsets %r: False, True or \"raw\"" % (return_offsets,))
+        if not raw:
+            raise ValueError("return_offsets=\"raw\" needs raw=True: normalized documents have no raw text to point into")
     torch = _torch()
     dtype = dtype or torch.int64
     id_bytes = _check_dtype(torch, dtype)
@@ -169,7 +175,8 @@ def encode_batch(vocab, docs, max_length, *, pad_id, bos_id=None, eos_id=None, p
         res = {"input_ids": ids, "attention_mask": mask.view(torch.bool), "lengths": lengths}
         if return_offsets:
             spans = torch.empty((nd, max_length, 2), dtype=torch.int64, device=dev)
-            N.check(N.lib.tm_batch_collate_spans(b, C.byref(how), st, spans.data_ptr(), 8))
+            fn = N.lib.tm_batch_collate_raw_spans if return_offsets == "raw" else N.lib.tm_batch_collate_spans
+            N.check(fn(b, C.byref(how), st, spans.data_ptr(), 8))
             res["offset_mapping"] = spans
     return res
 

@@ -134,6 +134,18 @@ class Vocab:
     def normalize(self, data):
         return _synth.normalize(data, self.capcode(), self.normalization_code())
 
+    def normalize_origins(self, data):
+        """one raw document -> (normalized bytes - Vocab.normalize's -, own u32[n]): own[k] is the offset in `data` of the first byte of the
+        character (unit) that normalized byte k came from (tm_normalize_origins)"""
+        data = N.as_u8(data)
+        out, own, n = C.c_void_p(), C.c_void_p(), C.c_size_t()
+        N.check(N.lib.tm_normalize_origins(N.ptr(data), data.size, self.capcode(), self.normalization_code(), C.byref(out), C.byref(n), C.byref(own)))
+        try:
+            o = np.frombuffer(C.string_at(own.value, 4 * n.value), dtype=np.uint32).copy() if n.value else np.zeros(0, dtype=np.uint32)
+        finally:
+            N.lib.tm_free(own)
+        return N.take(out, n.value), o
+
     def normalize_packed_device(self, raw_text, raw_offsets):
         """norm.Normalize + capcode.Encode of packed raw documents ON THE GPU (tm_batch_normalize; documents with
         other non-ASCII content fall back to the host normalizer inside the library)
@@ -192,6 +204,33 @@ class Vocab:
             N.check(rc)
             n = int(tok_off[nd])
             return out[:n], tok_off, spans[:n], missing[:nd]
+
+    def tokenize_raw_spans_packed(self, raw_text, raw_offsets):
+        """RAW packed documents -> (ids u32[T], tok_offsets u64[D+1], spans u32[T, 2], number of documents mapped on the host): spans[k] =
+        (begin, end) of the bytes id k came from, counted from its document's start in the raw text (tm_batch_upload_raw,
+        tm_batch_normalize, tm_batch_run, tm_batch_raw_spans)"""
+        raw_text = N.as_u8(raw_text)
+        raw_offsets = np.ascontiguousarray(raw_offsets, dtype=np.uint64)
+        nd = raw_offsets.size - 1
+        b = C.c_void_p()
+        N.check(N.lib.tm_batch_create(self._h, int(raw_text.size * 4 + 16 * nd + 1024), max(nd, 1), C.byref(b)))
+        try:
+            N.check(N.lib.tm_batch_upload_raw(b, N.ptr(raw_text), N.ptr(raw_offsets), nd))
+            N.check(N.lib.tm_batch_normalize(b, None))
+            N.check(N.lib.tm_batch_run(b, None))
+            n = C.c_uint64()
+            N.check(N.lib.tm_batch_totals(b, C.byref(n), None))
+            n = int(n.value)
+            ids = np.zeros(max(n, 1), dtype=np.uint32)
+            tok_off = np.zeros(nd + 1, dtype=np.uint64)
+            N.check(N.lib.tm_batch_download(b, N.ptr(ids), n, N.ptr(tok_off), None))
+            spans = PinnedBuffer(8 * max(n, 1))
+            host_docs = C.c_uint32()
+            N.check(N.lib.tm_batch_raw_spans(b, None, spans.array.ctypes.data, n, C.byref(host_docs)))
+            N.check(N.lib.tm_batch_totals(b, None, None))                     # (waits for the NULL stream)
+            return ids[:n], tok_off, spans.array[:8 * n].view(np.uint32).reshape(n, 2).copy(), int(host_docs.value)
+        finally:
+            N.lib.tm_batch_free(b)
 
     def tokenize_normalized(self, docs):
         """list of already-normalized documents -> list of uint32 arrays (Vocab.tokenize, go :1017)"""
