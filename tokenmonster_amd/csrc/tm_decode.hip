@@ -473,6 +473,47 @@ int launch_decode_capcode(const tm_vocab* v, const uint8_t* d_out, const uint64_
   }
   return TM_OK;
 }
+
+int decode_assemble(const tm_vocab* v, bool raw, uint32_t ndocs, const uint64_t* doff, uint64_t total, const uint8_t* gathered, const uint8_t* decoded, const uint64_t* declen,
+                    uint8_t* out, uint64_t out_cap, uint64_t* out_offsets, uint32_t* host_docs) {
+  if (host_docs) *host_docs = 0;
+  out_offsets[0] = 0;
+  if (ndocs == 0) return TM_OK;
+  // (the offsets come from the device: a decode that failed half way, or a fault of this library, must not become a copy from anywhere)
+  for (uint32_t d = 0; d < ndocs; d++)
+    if (doff[d + 1] < doff[d] || doff[d + 1] > total || (declen && declen[d] != DEC_HOST && declen[d] > total - doff[d]))
+      return set_error(TM_E_INTERNAL, "the decode left offsets that do not lie in its %llu bytes (document %u)", (unsigned long long)total, d);
+  if (raw || v->host.capcode == 0) {      // no capcode to undo: the gathered bytes are the text
+    const uint64_t n = doff[ndocs] - doff[0];
+    for (uint32_t d = 1; d <= ndocs; d++) out_offsets[d] = doff[d] - doff[0];
+    if (n > out_cap) return set_error(TM_E_NOSPACE, "out_cap %llu < %llu required", (unsigned long long)out_cap, (unsigned long long)n);
+    if (n) std::memcpy(out, gathered + doff[0], n);
+    return TM_OK;
+  }
+  // the documents the device left to the host decoder (DEC_HOST; all of them when its decoder did not run), gathered into one batch for it
+  std::vector<uint32_t> todo;
+  for (uint32_t d = 0; d < ndocs; d++) if (!declen || declen[d] == DEC_HOST) todo.push_back(d);
+  if (host_docs) *host_docs = (uint32_t)todo.size();
+  std::vector<std::vector<uint8_t>> touts;
+  if (!todo.empty()) {
+    std::vector<uint64_t> toff(todo.size() + 1, 0);
+    std::vector<uint8_t> tbytes;
+    for (size_t k = 0; k < todo.size(); k++) { tbytes.insert(tbytes.end(), gathered + doff[todo[k]], gathered + doff[todo[k] + 1]); toff[k + 1] = tbytes.size(); }
+    capcode_decode_batch(tbytes.data(), toff.data(), (uint32_t)todo.size(), v->host.capcode, 0, touts);
+  }
+  // ... and the two sources interleaved in document order
+  std::vector<uint64_t> slot((size_t)ndocs, DEC_HOST);
+  for (size_t k = 0; k < todo.size(); k++) slot[todo[k]] = k;
+  uint64_t o = 0;
+  for (uint32_t d = 0; d < ndocs; d++) { out_offsets[d] = o; o += slot[d] != DEC_HOST ? touts[slot[d]].size() : declen[d]; }
+  out_offsets[ndocs] = o;
+  if (o > out_cap) return set_error(TM_E_NOSPACE, "out_cap %llu < %llu required", (unsigned long long)out_cap, (unsigned long long)o);
+  for (uint32_t d = 0; d < ndocs; d++) {
+    const uint64_t len = out_offsets[d + 1] - out_offsets[d];
+    if (len) std::memcpy(out + out_offsets[d], slot[d] != DEC_HOST ? touts[slot[d]].data() : decoded + doff[d], len);
+  }
+  return TM_OK;
+}
 }  // namespace tmh
 
 // ---- device-resident decode of the ids a batch holds -------------------------------------------------------------------------------------------
@@ -482,6 +523,7 @@ int launch_decode_capcode(const tm_vocab* v, const uint8_t* d_out, const uint64_
 extern "C" {
 
 static int batch_decode(tm_batch* b, int raw, void* stream, uint64_t* decoded_bytes, uint32_t* host_docs, float* ms);
+static uint64_t arena_room(uint64_t need) { return need + need / 8 + 4096; }      // the arenas' headroom (grow-only, not counted in tm_batch_device_bytes)
 int tm_batch_decode(tm_batch* b, int raw, void* stream, uint64_t* decoded_bytes, uint32_t* host_docs) { return batch_decode(b, raw, stream, decoded_bytes, host_docs, nullptr); }
 int tm_batch_decode_timed(tm_batch* b, int raw, void* stream, uint64_t* decoded_bytes, uint32_t* host_docs, float* ms) {
   if (!ms) return set_error(TM_E_INVALID, "null argument");
@@ -490,13 +532,14 @@ int tm_batch_decode_timed(tm_batch* b, int raw, void* stream, uint64_t* decoded_
 // ms (may be null): HIP events on `stream` around [0] lengths + scan + document offsets, [1] the gather (k_dec_copy), [2] capcode decoding (k_dec_capcode)
 static int batch_decode(tm_batch* b, int raw, void* stream, uint64_t* decoded_bytes, uint32_t* host_docs, float* ms) {
   if (!b) return set_error(TM_E_INVALID, "null argument");
+  // (what tm_batch_decoded_download goes by is set when the last step has succeeded: a decode that fails leaves an empty one behind, not offsets of another)
+  b->dec_ndocs = 0; b->dec_total = b->dec_o_doff = b->dec_o_declen = b->dec_o_dec = 0; b->dec_capcode = b->dec_raw = false;
   const tm_vocab* v = b->vocab;
   { int rc = enter_device(v); if (rc != TM_OK) return rc; }
   { int rc = ensure_output(b); if (rc != TM_OK) return rc; }          // (the ids are all there: the emit stage is repeated if its buffer was too small)
   hipStream_t st = (hipStream_t)stream;
   const uint32_t nd = b->ndocs;
   const uint64_t n = nd ? b->last_totals[1] : 0;
-  b->dec_ndocs = nd; b->dec_total = 0; b->dec_capcode = false; b->dec_raw = raw != 0;
   if (decoded_bytes) *decoded_bytes = 0;
   if (host_docs) *host_docs = 0;
   if (ms) ms[0] = ms[1] = ms[2] = 0.f;
@@ -507,17 +550,8 @@ static int batch_decode(tm_batch* b, int raw, void* stream, uint64_t* decoded_by
     b->have_events = true;
   }
   auto mark = [&](int k) { if (ms) (void)hipEventRecord(b->ev[k], st); };
-  auto up = [](uint64_t x) { return (x + 255) & ~(uint64_t)255; };
-  auto grow = [&](uint8_t** p, uint64_t* cap, uint64_t need) -> hipError_t {
-    if (*cap >= need) return hipSuccess;
-    if (*cap) trace_grow("decode arena", need);
-    (void)hipFree(*p);
-    *p = nullptr;
-    *cap = need + need / 8 + 4096;
-    return hipMalloc((void**)p, *cap);
-  };
   const DecArena a = dec_arena(0, n, nd);
-  if ((e = grow(&b->d_dec_a, &b->dec_a_cap, a.bytes)) != hipSuccess) { b->dec_a_cap = 0; return hip_fail(e, "hipMalloc (decode)"); }
+  { int rc = grow_device(&b->d_dec_a, &b->dec_a_cap, a.bytes, arena_room(a.bytes), "decode arena"); if (rc != TM_OK) return rc; }
   uint8_t* A = b->d_dec_a;
   uint64_t* d_total = (uint64_t*)(A + a.o_total); uint64_t* d_doff = (uint64_t*)(A + a.o_doff); uint64_t* d_declen = (uint64_t*)(A + a.o_declen);
   mark(0);
@@ -525,8 +559,8 @@ static int batch_decode(tm_batch* b, int raw, void* stream, uint64_t* decoded_by
   mark(1);
   uint64_t total = 0;
   { int rc = small_d2h(b, &total, d_total, 8, st); if (rc == TM_OK) rc = small_sync(b, st); if (rc != TM_OK) return rc; }
-  const uint64_t o_dec = up(total + 16);
-  if ((e = grow(&b->d_dec_b, &b->dec_b_cap, o_dec + up(total + 16))) != hipSuccess) { b->dec_b_cap = 0; return hip_fail(e, "hipMalloc (decode output)"); }
+  const uint64_t o_dec = dec_up(total + 16);
+  { int rc = grow_device(&b->d_dec_b, &b->dec_b_cap, 2 * o_dec, arena_room(2 * o_dec), "decode arena"); if (rc != TM_OK) return rc; }
   mark(2);
   launch_decode_copy(v, b->d_out, n, b->d_tok_offsets, nd, a, A, b->d_dec_b, st);
   mark(3);
@@ -544,7 +578,7 @@ static int batch_decode(tm_batch* b, int raw, void* stream, uint64_t* decoded_by
     (void)hipEventElapsedTime(&ms[1], b->ev[2], b->ev[3]);
     if (dev_capcode) (void)hipEventElapsedTime(&ms[2], b->ev[3], b->ev[4]);
   }
-  b->dec_total = total; b->dec_o_doff = a.o_doff; b->dec_o_declen = a.o_declen; b->dec_o_dec = o_dec; b->dec_capcode = dev_capcode;
+  b->dec_ndocs = nd; b->dec_raw = raw != 0; b->dec_total = total; b->dec_o_doff = a.o_doff; b->dec_o_declen = a.o_declen; b->dec_o_dec = o_dec; b->dec_capcode = dev_capcode;
   // (a capcode-1 or UTF-16 vocabulary, or one without capcode that was not asked for the raw form: every document is the host decoder's)
   const bool all_host = !raw && v->host.capcode != 0 && !dev_capcode;
   if (decoded_bytes) *decoded_bytes = all_host ? 0 : sum[0];
@@ -567,30 +601,7 @@ int tm_batch_decoded_download(tm_batch* b, uint8_t* out, uint64_t out_cap, uint6
       (total && (e = hipMemcpy(enc.data(), b->d_dec_b, total, hipMemcpyDeviceToHost)) != hipSuccess)) return hip_fail(e, "D2H decoded bytes");
   if (b->dec_capcode && ((e = hipMemcpy(declen.data(), b->d_dec_a + b->dec_o_declen, (size_t)nd * 8, hipMemcpyDeviceToHost)) != hipSuccess ||
                          (total && (e = hipMemcpy(dec.data(), b->d_dec_b + b->dec_o_dec, total, hipMemcpyDeviceToHost)) != hipSuccess))) return hip_fail(e, "D2H decoded text");
-  const bool plain = b->dec_raw || v->host.capcode == 0;      // no capcode to undo: the gathered bytes are the text
-  // the documents the device left alone go through the host decoder, as in tm_decode_batch
-  std::vector<uint32_t> todo;
-  if (!plain) for (uint32_t d = 0; d < nd; d++) if (!b->dec_capcode || declen[d] == DEC_HOST) todo.push_back(d);
-  std::vector<std::vector<uint8_t>> touts;
-  if (!todo.empty()) {
-    std::vector<uint64_t> toff(todo.size() + 1, 0);
-    std::vector<uint8_t> tbytes;
-    for (size_t k = 0; k < todo.size(); k++) { tbytes.insert(tbytes.end(), enc.begin() + doff[todo[k]], enc.begin() + doff[todo[k] + 1]); toff[k + 1] = tbytes.size(); }
-    capcode_decode_batch(tbytes.data(), toff.data(), (uint32_t)todo.size(), v->host.capcode, 0, touts);
-  }
-  std::vector<uint64_t> slot((size_t)nd, DEC_HOST);
-  for (size_t k = 0; k < todo.size(); k++) slot[todo[k]] = k;
-  uint64_t o = 0;
-  for (uint32_t d = 0; d < nd; d++) { out_offsets[d] = o; o += slot[d] != DEC_HOST ? touts[slot[d]].size() : (plain ? doff[d + 1] - doff[d] : declen[d]); }
-  out_offsets[nd] = o;
-  if (o > out_cap) return set_error(TM_E_NOSPACE, "out_cap %llu < %llu required", (unsigned long long)out_cap, (unsigned long long)o);
-  for (uint32_t d = 0; d < nd; d++) {
-    const uint64_t len = out_offsets[d + 1] - out_offsets[d];
-    if (!len) continue;
-    if (slot[d] != DEC_HOST) std::memcpy(out + out_offsets[d], touts[slot[d]].data(), len);
-    else std::memcpy(out + out_offsets[d], (plain ? enc.data() : dec.data()) + doff[d], len);
-  }
-  return TM_OK;
+  return decode_assemble(v, b->dec_raw, nd, doff.data(), total, enc.data(), b->dec_capcode ? dec.data() : nullptr, b->dec_capcode ? declen.data() : nullptr, out, out_cap, out_offsets, nullptr);
 }
 
 }  // extern "C"

@@ -129,23 +129,8 @@ uint64_t slot_device_bytes(const DocSlot& s) {
   return s.ws->device_bytes + SMALL_BYTES + s.d_bytes_cap + (s.nws ? s.nws->device_bytes + piece_device_bytes(s.nws) : 0);
 }
 
-int stage_grow(uint8_t** buf, uint64_t* cap, uint64_t bytes) {
-  if (*cap >= bytes) return TM_OK;
-  if (*cap) trace_grow("document staging (pinned)", bytes);
-  (void)hipHostFree(*buf);
-  *buf = nullptr;
-  *cap = bytes;
-  hipError_t e = hipHostMalloc((void**)buf, *cap, hipHostMallocDefault);
-  if (e != hipSuccess) { *cap = 0; return hip_fail(e, "hipHostMalloc (document staging)"); }
-  return TM_OK;
-}
-
-bool is_pinned(const void* p) {
-  if (!p) return false;
-  hipPointerAttribute_t a;
-  if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
-  return a.type == hipMemoryTypeHost;
-}
+// (exact sizes: a slot's buffers are sized for its piece once)
+int stage_grow(uint8_t** buf, uint64_t* cap, uint64_t bytes) { return grow_pinned(buf, cap, bytes, bytes, "document staging (pinned)"); }
 
 }  // namespace
 
@@ -262,13 +247,7 @@ int harvest(DocCall& c, DocSlot& s) {
     if (rc != TM_OK) return rc;
     ntok = b->last_totals[1];
     if (c.enc != 4) {
-      if (s.d_bytes_cap < ntok * 3 + 64) {
-        trace_grow("document ids", ntok * 3 + 64);
-        (void)hipFree(s.d_bytes);
-        s.d_bytes = nullptr; s.d_bytes_cap = 0;
-        if ((e = hipMalloc((void**)&s.d_bytes, b->out_cap * 3 + 64)) != hipSuccess) return hip_fail(e, "hipMalloc (document ids)");
-        s.d_bytes_cap = b->out_cap * 3 + 64;
-      }
+      if ((rc = grow_device(&s.d_bytes, &s.d_bytes_cap, ntok * 3 + 64, b->out_cap * 3 + 64, "document ids")) != TM_OK) return rc;
       launch_serialize(b->d_out, ntok, c.enc, s.d_bytes, s.comp);
       s.ids_at = s.d_bytes;
     } else s.ids_at = reinterpret_cast<const uint8_t*>(b->d_out);

@@ -7,6 +7,18 @@
 // different lanes and overlap on the device.  tm_tokenize_pipeline is the large-batch form: the corpus is cut into chunks that
 // run H2D | normalize + tokenize (+ serialize) | D2H on several lanes at once, so that PCIe moves chunk k+1 in and chunk k-1 out
 // while chunk k computes — the host-to-host number of bench.py.
+//
+// How the file is laid out.  A lane goes back to the pool with nothing in flight on its stream and nothing pending in its workspace's mailbox
+// (small_d2h's destinations are the caller's buffers and stack locals); that rule is kept in three places, once each:
+//   one_shot       the body of tm_tokenize_batch, _spans, _raw_spans and _serialized: lane, run, offsets and missing counts, the span pass, the
+//                  ids, small_sync on every path, lane back (tm_count_batch reads other arrays and keeps its own few lines);
+//   chunk_deliver  the second half of a chunk of tm_tokenize_pipeline on a lane - its place in the chain of counts, offsets, packed ids out,
+//                  one wait - for the lanes' worker loop (pipeline_lanes) and for the ring's exact path (chunk_exact), each of which waits
+//                  for the lane's stream itself when it fails;
+//   tm_decode_batch, whose host part (which documents the device left to the host decoder, the two sources interleaved) is decode_assemble
+//                  of tm_decode.hip, shared with tm_batch_decoded_download.
+// PipeCall::chunk(k) is the one place that turns a chunk number into documents, bytes and chunk-relative offsets.  Buffers grow through
+// grow_device / grow_pinned / grow_workspace (tm_pipeline.h); this file only says how much headroom a lane or a ring slot takes.
 #include <hip/hip_runtime.h>
 #include <sched.h>
 
@@ -227,57 +239,14 @@ static void lane_release(const tm_vocab* v, Lane* l) {
   p->cv.notify_one();
 }
 
-// grow-only: a workspace that is too small is replaced by one with headroom, so that a server converges to zero allocations
+// grow-only, with the lanes' headroom, so that a server converges to zero allocations (grow_workspace / grow_pinned / grow_device, tm_pipeline.h)
+static uint64_t lane_room(uint64_t bytes) { return bytes + bytes / 4 + 4096; }
 static int lane_workspace(Lane* l, const tm_vocab* v, uint64_t bytes, uint32_t docs) {
-  if (l->ws && l->ws->vocab == v && l->ws->max_bytes >= bytes && l->ws->max_docs >= docs) return TM_OK;
-  uint64_t want_b = std::max<uint64_t>(bytes + bytes / 4 + (1u << 20), l->ws ? l->ws->max_bytes : 0);
-  uint64_t want_d = std::max<uint64_t>((uint64_t)docs + docs / 4 + 64, l->ws ? l->ws->max_docs : 0);
-  if (l->ws) trace_grow("lane workspace", want_b);
-  tm_batch_free(l->ws);
-  l->ws = nullptr;
-  return tm_batch_create(v, want_b, (uint32_t)std::min<uint64_t>(want_d, 0xFFFFFFF0ull), &l->ws);
+  return grow_workspace(&l->ws, v, bytes, docs, bytes + bytes / 4 + (1u << 20), "lane workspace");
 }
-
-static int stage_grow(uint8_t** buf, uint64_t* cap, uint64_t bytes) {
-  if (*cap >= bytes) return TM_OK;
-  if (*cap) trace_grow("lane staging (pinned)", bytes);
-  (void)hipHostFree(*buf);
-  *buf = nullptr;
-  *cap = bytes + bytes / 4 + 4096;
-  hipError_t e = hipHostMalloc((void**)buf, *cap, hipHostMallocDefault);
-  if (e != hipSuccess) { *cap = 0; return hip_fail(e, "hipHostMalloc (lane staging)"); }
-  return TM_OK;
-}
-static int lane_stage(Lane* l, uint64_t bytes) { return stage_grow(&l->h_stage, &l->h_cap, bytes); }
-
-static int lane_dbytes(Lane* l, uint64_t bytes) {
-  if (l->d_bytes_cap >= bytes) return TM_OK;
-  if (l->d_bytes_cap) trace_grow("lane serialized ids", bytes);
-  (void)hipFree(l->d_bytes);
-  l->d_bytes = nullptr;
-  l->d_bytes_cap = bytes + bytes / 4 + 4096;
-  hipError_t e = hipMalloc((void**)&l->d_bytes, l->d_bytes_cap);
-  if (e != hipSuccess) { l->d_bytes_cap = 0; return hip_fail(e, "hipMalloc (serialized ids)"); }
-  return TM_OK;
-}
-
-static int dev_grow(uint8_t** buf, uint64_t* cap, uint64_t bytes, const char* what) {
-  if (*cap >= bytes) return TM_OK;
-  if (*cap) trace_grow(what, bytes);
-  (void)hipFree(*buf);
-  *buf = nullptr;
-  *cap = bytes + bytes / 4 + 4096;
-  hipError_t e = hipMalloc((void**)buf, *cap);
-  if (e != hipSuccess) { *cap = 0; return hip_fail(e, what); }
-  return TM_OK;
-}
-
-static bool is_pinned(const void* p) {
-  if (!p) return false;
-  hipPointerAttribute_t a;
-  if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
-  return a.type == hipMemoryTypeHost;
-}
+static int lane_pinned(uint8_t** buf, uint64_t* cap, uint64_t bytes) { return grow_pinned(buf, cap, bytes, lane_room(bytes), "lane staging (pinned)"); }
+static int lane_device(uint8_t** buf, uint64_t* cap, uint64_t bytes, const char* what) { return grow_device(buf, cap, bytes, lane_room(bytes), what); }
+static int lane_dbytes(Lane* l, uint64_t bytes) { return lane_device(&l->d_bytes, &l->d_bytes_cap, bytes, "lane serialized ids"); }
 
 struct RunOut { uint64_t total_tokens = 0; };
 
@@ -368,89 +337,76 @@ int tm_host_unregister(void* p) {
   return e == hipSuccess ? TM_OK : hip_fail(e, "hipHostUnregister");
 }
 
-int tm_tokenize_batch(const tm_vocab* v, const uint8_t* text, const uint64_t* offsets, uint32_t ndocs, uint32_t* tokens_out,
-                      uint64_t tokens_cap, uint64_t* tok_offsets, uint32_t* missing) {
+// The one body of the one-shot calls: a lane, the run, the documents' id offsets and missing counts, the span pass where one is asked for,
+// the ids - as u32, or packed to `enc` bytes -, and the lane back with nothing in flight and nothing pending in the mailbox.  small_sync runs
+// on every path behind a completed run: it is what fills tok_offsets and missing, also for a call that is refused.
+enum class SpanStep { none, normalized, raw };
+struct OneShot {
+  bool raw;                 // the text is raw: the normalizer runs in front
+  SpanStep spans;
+  uint32_t enc;             // 0: ids_out takes u32 ids and `cap` counts ids; 2 .. 4: the serialized form, `cap` counts bytes and offsets_out takes byte offsets
+  const char* who;
+  void* ids_out; uint64_t cap; uint64_t* offsets_out; uint32_t* spans_out; uint32_t* missing;
+};
+static int one_shot(const tm_vocab* v, const uint8_t* text, const uint64_t* offsets, uint32_t ndocs, const OneShot& o) {
   if (!v || (ndocs && !offsets)) return set_error(TM_E_INVALID, "null argument");
   Lane* l = nullptr;
   int rc = lane_acquire(v, &l);
   if (rc != TM_OK) return rc;
   RunOut ro;
-  rc = lane_run(l, v, text, offsets, ndocs, false, true, &ro);
+  rc = lane_run(l, v, text, offsets, ndocs, o.raw, true, &ro);
   if (rc == TM_OK) {
     tm_batch* b = l->ws;
-    if (tok_offsets) rc = small_d2h(b, tok_offsets, b->d_tok_offsets, ((uint64_t)ndocs + 1) * 8, l->stream);
-    if (rc == TM_OK && missing && ndocs) rc = small_d2h(b, missing, b->d_doc_missing, (uint64_t)ndocs * 4, l->stream);
-    if (rc == TM_OK && ro.total_tokens > tokens_cap) {
-      (void)small_sync(b, l->stream);
-      rc = set_error(TM_E_NOSPACE, "tokens_cap %llu < %llu required", (unsigned long long)tokens_cap, (unsigned long long)ro.total_tokens);
+    const uint64_t total = ro.total_tokens, need = o.enc ? total * o.enc : total;
+    const bool fits = need <= o.cap;
+    // the serialized form reads the id offsets into an array of its own: the caller's array takes BYTE offsets, made from them behind the wait
+    std::vector<uint64_t> id_offs(o.enc ? (size_t)ndocs + 1 : 0, 0);
+    uint64_t* const toff = o.enc ? id_offs.data() : o.offsets_out;
+    if (toff && ndocs) rc = small_d2h(b, toff, b->d_tok_offsets, ((uint64_t)ndocs + 1) * 8, l->stream);
+    if (rc == TM_OK && o.missing && ndocs) rc = small_d2h(b, o.missing, b->d_doc_missing, (uint64_t)ndocs * 4, l->stream);
+    if (rc == TM_OK && fits && o.spans != SpanStep::none) {
+      if (total && (!o.ids_out || !o.spans_out)) rc = set_error(TM_E_INVALID, "null argument");
+      // the pairs behind the run on the lane's stream, into the workspace's own grow-only buffer (lane_run has waited for the run: ensure_output)
+      if (rc == TM_OK) rc = spans_ready(b, o.who);
+      if (rc == TM_OK && o.spans == SpanStep::raw) rc = origin_ready(b, o.who);
+      if (rc == TM_OK) rc = spans_reserve(b, total);
+      if (rc == TM_OK) rc = o.spans == SpanStep::raw ? batch_raw_spans_on(b, l->stream, b->d_spans, total, nullptr) : batch_spans_on(b, l->stream, b->d_spans, total);
     }
-    if (rc == TM_OK) rc = small_d2h(b, tokens_out, b->d_out, ro.total_tokens * 4, l->stream);
-    if (rc == TM_OK) rc = small_sync(b, l->stream); else (void)small_sync(b, l->stream);
-    if (ndocs == 0 && tok_offsets) tok_offsets[0] = 0;
+    if (rc == TM_OK && fits && total) {
+      if (!o.enc) rc = small_d2h(b, o.ids_out, b->d_out, total * 4, l->stream);
+      else if ((rc = lane_dbytes(l, need)) == TM_OK) {
+        launch_serialize(b->d_out, total, o.enc, l->d_bytes, l->stream);
+        rc = small_d2h(b, o.ids_out, l->d_bytes, need, l->stream);
+      }
+    }
+    if (rc == TM_OK && fits && o.spans != SpanStep::none) rc = small_d2h(b, o.spans_out, b->d_spans, total * 8, l->stream);
+    { const int rs = small_sync(b, l->stream); if (rc == TM_OK) rc = rs; }
+    if (ndocs == 0 && toff) toff[0] = 0;
+    if (rc == TM_OK && o.enc && o.offsets_out) for (size_t d = 0; d <= ndocs; d++) o.offsets_out[d] = id_offs[d] * o.enc;
+    // TM_E_NOSPACE is answered last on every form: tok_offsets is complete once small_sync has run, byte_offsets once the line above has - and
+    // both say what capacity the call needs
+    if (rc == TM_OK && !fits) {
+      rc = o.enc ? set_error(TM_E_NOSPACE, "bytes_cap too small")
+                 : set_error(TM_E_NOSPACE, "tokens_cap %llu < %llu required", (unsigned long long)o.cap, (unsigned long long)total);
+    }
   }
   lane_release(v, l);
   return rc;
+}
+
+int tm_tokenize_batch(const tm_vocab* v, const uint8_t* text, const uint64_t* offsets, uint32_t ndocs, uint32_t* tokens_out,
+                      uint64_t tokens_cap, uint64_t* tok_offsets, uint32_t* missing) {
+  return one_shot(v, text, offsets, ndocs, OneShot{false, SpanStep::none, 0, "tm_tokenize_batch", tokens_out, tokens_cap, tok_offsets, nullptr, missing});
 }
 
 int tm_tokenize_batch_spans(const tm_vocab* v, const uint8_t* text, const uint64_t* offsets, uint32_t ndocs, uint32_t* tokens_out,
                             uint64_t tokens_cap, uint64_t* tok_offsets, uint32_t* spans_out, uint32_t* missing) {
-  if (!v || (ndocs && !offsets)) return set_error(TM_E_INVALID, "null argument");
-  Lane* l = nullptr;
-  int rc = lane_acquire(v, &l);
-  if (rc != TM_OK) return rc;
-  RunOut ro;
-  rc = lane_run(l, v, text, offsets, ndocs, false, true, &ro);
-  if (rc == TM_OK) {
-    tm_batch* b = l->ws;
-    if (tok_offsets) rc = small_d2h(b, tok_offsets, b->d_tok_offsets, ((uint64_t)ndocs + 1) * 8, l->stream);
-    if (rc == TM_OK && missing && ndocs) rc = small_d2h(b, missing, b->d_doc_missing, (uint64_t)ndocs * 4, l->stream);
-    if (rc == TM_OK && ro.total_tokens > tokens_cap) {
-      (void)small_sync(b, l->stream);
-      rc = set_error(TM_E_NOSPACE, "tokens_cap %llu < %llu required", (unsigned long long)tokens_cap, (unsigned long long)ro.total_tokens);
-    }
-    if (rc == TM_OK && ro.total_tokens && (!tokens_out || !spans_out)) rc = set_error(TM_E_INVALID, "null argument");
-    // the span pass behind the run on the lane's stream, into the workspace's own grow-only buffer (lane_run has waited for the run: ensure_output)
-    if (rc == TM_OK) rc = spans_ready(b, "tm_tokenize_batch_spans");
-    if (rc == TM_OK) rc = spans_reserve(b, ro.total_tokens);
-    if (rc == TM_OK) rc = batch_spans_on(b, l->stream, b->d_spans, ro.total_tokens);
-    if (rc == TM_OK) rc = small_d2h(b, tokens_out, b->d_out, ro.total_tokens * 4, l->stream);
-    if (rc == TM_OK) rc = small_d2h(b, spans_out, b->d_spans, ro.total_tokens * 8, l->stream);
-    if (rc == TM_OK) rc = small_sync(b, l->stream); else (void)small_sync(b, l->stream);
-    if (ndocs == 0 && tok_offsets) tok_offsets[0] = 0;
-  }
-  lane_release(v, l);
-  return rc;
+  return one_shot(v, text, offsets, ndocs, OneShot{false, SpanStep::normalized, 0, "tm_tokenize_batch_spans", tokens_out, tokens_cap, tok_offsets, spans_out, missing});
 }
 
 int tm_tokenize_batch_raw_spans(const tm_vocab* v, const uint8_t* raw, const uint64_t* offsets, uint32_t ndocs, uint32_t* tokens_out,
                                 uint64_t tokens_cap, uint64_t* tok_offsets, uint32_t* spans_out, uint32_t* missing) {
-  if (!v || (ndocs && !offsets)) return set_error(TM_E_INVALID, "null argument");
-  Lane* l = nullptr;
-  int rc = lane_acquire(v, &l);
-  if (rc != TM_OK) return rc;
-  RunOut ro;
-  rc = lane_run(l, v, raw, offsets, ndocs, true, true, &ro);
-  if (rc == TM_OK) {
-    tm_batch* b = l->ws;
-    if (tok_offsets) rc = small_d2h(b, tok_offsets, b->d_tok_offsets, ((uint64_t)ndocs + 1) * 8, l->stream);
-    if (rc == TM_OK && missing && ndocs) rc = small_d2h(b, missing, b->d_doc_missing, (uint64_t)ndocs * 4, l->stream);
-    if (rc == TM_OK && ro.total_tokens > tokens_cap) {
-      (void)small_sync(b, l->stream);
-      rc = set_error(TM_E_NOSPACE, "tokens_cap %llu < %llu required", (unsigned long long)tokens_cap, (unsigned long long)ro.total_tokens);
-    }
-    if (rc == TM_OK && ro.total_tokens && (!tokens_out || !spans_out)) rc = set_error(TM_E_INVALID, "null argument");
-    // the raw pairs behind the run on the lane's stream, in place in the workspace's own buffer
-    if (rc == TM_OK) rc = spans_ready(b, "tm_tokenize_batch_raw_spans");
-    if (rc == TM_OK) rc = origin_ready(b, "tm_tokenize_batch_raw_spans");
-    if (rc == TM_OK) rc = spans_reserve(b, ro.total_tokens);
-    if (rc == TM_OK) rc = batch_raw_spans_on(b, l->stream, b->d_spans, ro.total_tokens, nullptr);
-    if (rc == TM_OK) rc = small_d2h(b, tokens_out, b->d_out, ro.total_tokens * 4, l->stream);
-    if (rc == TM_OK) rc = small_d2h(b, spans_out, b->d_spans, ro.total_tokens * 8, l->stream);
-    if (rc == TM_OK) rc = small_sync(b, l->stream); else (void)small_sync(b, l->stream);
-    if (ndocs == 0 && tok_offsets) tok_offsets[0] = 0;
-  }
-  lane_release(v, l);
-  return rc;
+  return one_shot(v, raw, offsets, ndocs, OneShot{true, SpanStep::raw, 0, "tm_tokenize_batch_raw_spans", tokens_out, tokens_cap, tok_offsets, spans_out, missing});
 }
 
 static int count_batch(const tm_vocab* v, const uint8_t* text, const uint64_t* offsets, uint32_t ndocs, bool raw, uint64_t* counts, uint32_t* missing) {
@@ -487,29 +443,7 @@ int tm_tokenize_batch_serialized(const tm_vocab* v, const uint8_t* text, const u
   if (encoding_length <= 1) encoding_length = v->host.n_ids <= 65536 ? 2 : 3;          // go :990-996
   if (encoding_length < 2 || encoding_length > 4) return set_error(TM_E_INVALID, "Invalid encoding length");   // go :1012
   if (encoding_length_used) *encoding_length_used = encoding_length;
-  Lane* l = nullptr;
-  int rc = lane_acquire(v, &l);
-  if (rc != TM_OK) return rc;
-  RunOut ro;
-  rc = lane_run(l, v, text, offsets, ndocs, false, true, &ro);
-  if (rc == TM_OK) {
-    tm_batch* b = l->ws;
-    const uint64_t nb = ro.total_tokens * encoding_length;
-    std::vector<uint64_t> offs((size_t)ndocs + 1, 0);
-    if (ndocs) rc = small_d2h(b, offs.data(), b->d_tok_offsets, offs.size() * 8, l->stream);
-    if (rc == TM_OK && missing && ndocs) rc = small_d2h(b, missing, b->d_doc_missing, (uint64_t)ndocs * 4, l->stream);
-    if (rc == TM_OK && nb <= bytes_cap && nb) {
-      if ((rc = lane_dbytes(l, nb)) == TM_OK) {
-        launch_serialize(b->d_out, ro.total_tokens, encoding_length, l->d_bytes, l->stream);
-        rc = small_d2h(b, bytes_out, l->d_bytes, nb, l->stream);
-      }
-    }
-    { int rs = small_sync(b, l->stream); if (rc == TM_OK) rc = rs; }
-    if (rc == TM_OK && byte_offsets) for (size_t d = 0; d <= ndocs; d++) byte_offsets[d] = offs[d] * encoding_length;
-    if (rc == TM_OK && nb > bytes_cap) rc = set_error(TM_E_NOSPACE, "bytes_cap too small");
-  }
-  lane_release(v, l);
-  return rc;
+  return one_shot(v, text, offsets, ndocs, OneShot{false, SpanStep::none, encoding_length, "tm_tokenize_batch_serialized", bytes_out, bytes_cap, byte_offsets, nullptr, missing});
 }
 
 // ---- large batches, host to host -------------------------------------------------------------------------------------------------
@@ -541,6 +475,13 @@ struct PipeCall {
   std::string first_msg;
   std::atomic<size_t> next{0};
   double t0 = 0;
+  // chunk k: its documents [d0, d0 + nd) and its bytes [b0, b0 + nb) of the call's text
+  struct Chunk {
+    const uint64_t* off;      // = offsets + d0
+    uint32_t d0, nd; uint64_t b0, nb;
+    void local_offsets(uint64_t* lo) const { for (uint32_t d = 0; d <= nd; d++) lo[d] = off[d] - b0; }      // lo[nd + 1]: the documents' offsets counted from the chunk's first byte
+  };
+  Chunk chunk(size_t k) const { const uint32_t d0 = first[k], nd = first[k + 1] - d0; return Chunk{offsets + d0, d0, nd, offsets[d0], offsets[d0 + nd] - offsets[d0]}; }
   // test hook 24 (tm_debug_flags, TM_TEST_FAIL="<place>:<chunk>[:<chunks>]"): ONE chunk of this call fails with TM_E_INPUT at a place of the
   // host code - an error return like any other, nothing on the device differs.  hook_place stays 0 in every call of a process without the hook.
   enum { HOOK_FINISHER = 1, HOOK_EXACT, HOOK_ISSUER, HOOK_DOWNLOAD };
@@ -578,44 +519,64 @@ struct PipeCall {
   }
 };
 
+// The second half of a chunk on a lane: its ids lie in l->ws and their number is known.  The chunk takes its place in the chain of counts; id
+// offsets and missing counts come through the mailbox, the packed ids through l->d_bytes into the caller's buffer (directly, or through
+// h_stage when that buffer is pageable); one wait; offsets and statistics.  *delivered stays false with TM_OK when another chunk has failed.
+// `toff` is the caller's scratch: a failure may leave a small transfer into it pending, which the caller's clean-up waits for.
+// download_hook: test hook place HOOK_DOWNLOAD lies between the enqueued download and the wait (the lanes' form; the ring has its own).
+static int chunk_deliver(PipeCall& c, Lane* l, size_t k, uint64_t ntok, bool download_hook, std::vector<uint64_t>& toff, bool* delivered, double* t_ordered = nullptr) {
+  *delivered = false;
+  const PipeCall::Chunk ch = c.chunk(k);
+  uint64_t base = 0;
+  if (!c.order(k, ntok, &base)) return TM_OK;          // publish this chunk's count, learn where its ids go
+  if (t_ordered) *t_ordered = now_ms();
+  tm_batch* b = l->ws;
+  const uint64_t out_b = ntok * c.enc;
+  int rc = TM_OK;
+  toff.resize((size_t)ch.nd + 1);
+  if ((rc = small_d2h(b, toff.data(), b->d_tok_offsets, toff.size() * 8, l->stream)) != TM_OK) return rc;
+  if (c.missing && ch.nd && (rc = small_d2h(b, c.missing + ch.d0, b->d_doc_missing, (uint64_t)ch.nd * 4, l->stream)) != TM_OK) return rc;
+  const bool fits = (base + ntok) * c.enc <= c.bytes_cap && c.bytes_out;
+  if (fits && out_b) {
+    // (Writing the ids straight into the caller's page-locked buffer from the serialize kernel - no device staging, no copy command - was
+    // built and timed in round 5: 42 - 45 ms per GiB call against 32 - 36 with the copy engine, profiles/r05_h2h.txt: stores of a kernel to
+    // fine-grained host memory cross PCIe far below the engine's rate.  Removed.)
+    if ((rc = lane_dbytes(l, out_b)) != TM_OK) return rc;
+    launch_serialize(b->d_out, ntok, c.enc, l->d_bytes, l->stream);
+    if (c.out_pinned) rc = d2h(c.bytes_out + base * c.enc, l->d_bytes, out_b, l->stream, "D2H ids");
+    else if ((rc = lane_pinned(&l->h_stage, &l->h_cap, out_b)) == TM_OK) rc = d2h(l->h_stage, l->d_bytes, out_b, l->stream, "D2H ids");
+    if (rc != TM_OK) return rc;
+  }
+  if (download_hook && c.hook(PipeCall::HOOK_DOWNLOAD, k)) return PipeCall::hook_fail("download", k);
+  if ((rc = small_sync(b, l->stream)) != TM_OK) return rc;
+  if (fits && out_b && !c.out_pinned) std::memcpy(c.bytes_out + base * c.enc, l->h_stage, out_b);
+  for (uint32_t d = 1; d <= ch.nd; d++) c.byte_offsets[ch.d0 + d] = (base + toff[d]) * c.enc;
+  if (c.stats) { std::lock_guard<std::mutex> g(c.mu); c.stats->host_fallback_docs += c.raw ? b->host_fallback_docs : 0; c.stats->normalized_bytes += b->nbytes; }
+  *delivered = true;
+  return TM_OK;
+}
+
 // One chunk through the exact path on a borrowed lane, start to finish (the ring's way out for a chunk its one-pass form does not take; no
 // prefetching, every wait in line)
 static int chunk_exact(PipeCall& c, const tm_vocab* v, size_t k) {
-  const uint32_t d0 = c.first[k], nd = c.first[k + 1] - d0;
-  const uint64_t b0 = c.offsets[d0];
+  const PipeCall::Chunk ch = c.chunk(k);
   Lane* l = nullptr;
   int rc = lane_acquire(v, &l);
   if (rc != TM_OK) return rc;
-  std::vector<uint64_t> lo((size_t)nd + 1), toff((size_t)nd + 1);
-  for (uint32_t d = 0; d <= nd; d++) lo[d] = c.offsets[d0 + d] - b0;
-  const uint8_t* src = c.text + b0;
+  std::vector<uint64_t> lo((size_t)ch.nd + 1), toff;
+  ch.local_offsets(lo.data());
+  const uint8_t* src = c.text + ch.b0;
   do {
     if (!c.in_pinned) {
-      if ((rc = stage_grow(&l->h_stage_in, &l->h_in_cap, lo[nd])) != TM_OK) break;
-      std::memcpy(l->h_stage_in, src, lo[nd]);
+      if ((rc = lane_pinned(&l->h_stage_in, &l->h_in_cap, ch.nb)) != TM_OK) break;
+      std::memcpy(l->h_stage_in, src, ch.nb);
       src = l->h_stage_in;
     }
     RunOut ro;
-    if ((rc = lane_run(l, v, src, lo.data(), nd, c.raw != 0, true, &ro)) != TM_OK) break;
+    if ((rc = lane_run(l, v, src, lo.data(), ch.nd, c.raw != 0, true, &ro)) != TM_OK) break;
     if (c.hook(PipeCall::HOOK_EXACT, k)) { rc = PipeCall::hook_fail("exact", k); break; }
-    uint64_t base = 0;
-    if (!c.order(k, ro.total_tokens, &base)) break;
-    tm_batch* b = l->ws;
-    const uint64_t out_b = ro.total_tokens * c.enc;
-    if ((rc = small_d2h(b, toff.data(), b->d_tok_offsets, toff.size() * 8, l->stream)) != TM_OK) break;
-    if (c.missing && nd && (rc = small_d2h(b, c.missing + d0, b->d_doc_missing, (uint64_t)nd * 4, l->stream)) != TM_OK) break;
-    const bool fits = (base + ro.total_tokens) * c.enc <= c.bytes_cap && c.bytes_out;
-    if (fits && out_b) {
-      if ((rc = lane_dbytes(l, out_b)) != TM_OK) break;
-      launch_serialize(b->d_out, ro.total_tokens, c.enc, l->d_bytes, l->stream);
-      if (c.out_pinned) rc = d2h(c.bytes_out + base * c.enc, l->d_bytes, out_b, l->stream, "D2H ids");
-      else if ((rc = lane_stage(l, out_b)) == TM_OK) rc = d2h(l->h_stage, l->d_bytes, out_b, l->stream, "D2H ids");
-      if (rc != TM_OK) break;
-    }
-    if ((rc = small_sync(b, l->stream)) != TM_OK) break;
-    if (fits && out_b && !c.out_pinned) std::memcpy(c.bytes_out + base * c.enc, l->h_stage, out_b);
-    for (uint32_t d = 1; d <= nd; d++) c.byte_offsets[d0 + d] = (base + toff[d]) * c.enc;
-    if (c.stats) { std::lock_guard<std::mutex> g(c.mu); c.stats->host_fallback_docs += c.raw ? b->host_fallback_docs : 0; c.stats->normalized_bytes += b->nbytes; }
+    bool delivered = false;
+    rc = chunk_deliver(c, l, k, ro.total_tokens, false, toff, &delivered);
   } while (false);
   if (rc != TM_OK) {          // (nothing of the chunk in flight when the lane goes back, and no small transfer left that would land in `toff` later)
     const std::string msg = last_error();
@@ -637,34 +598,16 @@ static int chunk_exact(PipeCall& c, const tm_vocab* v, size_t k) {
 // place in the output from the chain of counts, and enqueues the download on the copy stream `down`.  A chunk the one-pass form does not
 // take (documents for the host normalizer, a long document, a piece whose margins could not tell ...) costs its kernels nothing behind the
 // normalizer pass (ctl[0] == 0) and is run through the exact path by the finisher (chunk_exact).
-static int ring_slot_size(RingSlot& s, const tm_vocab* v, uint64_t need_bytes, uint32_t need_docs, uint32_t enc) {
-  hipError_t e;
-  if (!s.ws || s.ws->vocab != v || s.ws->max_bytes < need_bytes || s.ws->max_docs < need_docs) {
-    const uint64_t wb = std::max<uint64_t>(need_bytes + need_bytes / 8 + (1u << 20), s.ws ? s.ws->max_bytes : 0);
-    const uint64_t wd = std::max<uint64_t>((uint64_t)need_docs + need_docs / 4 + 64, s.ws ? s.ws->max_docs : 0);
-    if (s.ws) trace_grow("ring workspace", wb);
-    tm_batch_free(s.ws);
-    s.ws = nullptr;
-    int rc = tm_batch_create(v, wb, (uint32_t)std::min<uint64_t>(wd, 0xFFFFFFF0ull), &s.ws);
-    if (rc != TM_OK) return rc;
-  }
+static int ring_slot_size(RingSlot& s, const tm_vocab* v, uint64_t need_bytes, uint32_t need_docs) {
+  int rc = grow_workspace(&s.ws, v, need_bytes, need_docs, need_bytes + need_bytes / 8 + (1u << 20), "ring workspace");
+  if (rc != TM_OK) return rc;
   const uint64_t nb = s.ws->out_cap * 4;          // (room for the widest form: the slot outlives the call)
-  (void)enc;
-  if (s.d_bytes_cap < nb) {
-    (void)hipFree(s.d_bytes);
-    s.d_bytes = nullptr;
-    if ((e = hipMalloc((void**)&s.d_bytes, nb)) != hipSuccess) { s.d_bytes_cap = 0; return hip_fail(e, "hipMalloc (ring ids)"); }
-    s.d_bytes_cap = nb;
-  }
+  if ((rc = grow_device(&s.d_bytes, &s.d_bytes_cap, nb, nb, "ring ids")) != TM_OK) return rc;
+  // (the block's layout hangs on the workspace's document count, which only grows - and the block's size with it)
   const uint64_t dc = s.ws->max_docs;
-  const uint64_t hp = 64 + 2 * (dc + 2) * 8 + (dc + 2) * 4;
-  if (s.h_pin_cap < hp || s.docs_cap != dc) {
-    (void)hipHostFree(s.h_pin);
-    s.h_pin = nullptr;
-    if ((e = hipHostMalloc((void**)&s.h_pin, hp, hipHostMallocDefault)) != hipSuccess) { s.h_pin_cap = 0; return hip_fail(e, "hipHostMalloc (ring slot)"); }
-    s.h_pin_cap = hp;
-    s.docs_cap = dc;
-  }
+  if ((rc = grow_pinned(&s.h_pin, &s.h_pin_cap, 64 + 2 * (dc + 2) * 8 + (dc + 2) * 4, 64 + 2 * (dc + 2) * 8 + (dc + 2) * 4, "ring slot (pinned)")) != TM_OK) return rc;
+  s.docs_cap = dc;
+  hipError_t e;
   for (hipEvent_t* ev : {&s.up_done, &s.comp_done, &s.dl_done})
     if (!*ev && (e = hipEventCreateWithFlags(ev, hipEventDisableTiming)) != hipSuccess) return hip_fail(e, "hipEventCreate (ring)");
   return TM_OK;
@@ -702,8 +645,9 @@ static int pipeline_ring(PipeCall& c, const std::vector<Ring*>& rings) {
     while (rc == TM_OK && !c.failed()) {
       const size_t k = c.next.fetch_add(1);
       if (k >= c.nchunks) break;
-      const uint32_t d0 = c.first[k], nd = c.first[k + 1] - d0;
-      const uint64_t b0 = c.offsets[d0], nb = c.offsets[d0 + nd] - b0;
+      const PipeCall::Chunk ch = c.chunk(k);
+      const uint32_t nd = ch.nd;
+      const uint64_t b0 = ch.b0, nb = ch.nb;
       int si = -1;
       if (nb > 0) {
         // a free slot (the finisher hands them back in order)
@@ -718,9 +662,9 @@ static int pipeline_ring(PipeCall& c, const std::vector<Ring*>& rings) {
         tm_batch* b = s.ws;
         uint64_t* lo = s.h_roff();
         uint64_t npieces = 0;
-        for (uint32_t d = 0; d <= nd; d++) lo[d] = c.offsets[d0 + d] - b0;
+        ch.local_offsets(lo);
         const uint64_t grows = (v->host.norm_flag & 64u) ? 1u : 0u;       // (leadingspace: as batch_upload_raw_on counts them)
-        for (uint32_t d = 0; d < nd; d++) npieces += (lo[d + 1] - lo[d] + grows + 1023) / 1024;
+        for (uint32_t d = 0; d < nd; d++) npieces += (lo[d + 1] - lo[d] + grows + RAW_PIECE - 1) / RAW_PIECE;
         hipStream_t cs = r.comp[issued % r.comp.size()];
         hipError_t e = hipSuccess;
         const double ti0 = trace ? now_ms() : 0;
@@ -888,7 +832,7 @@ static int rings_acquire(PipeCall& c, uint32_t nslots, uint32_t nstreams, std::v
     }
     if (rc != TM_OK) break;
     if (r.slots.size() < nslots) r.slots.resize(nslots);
-    for (RingSlot& s : r.slots) if ((rc = ring_slot_size(s, c.vs[i], lane_need(true, max_nb), max_nd, c.enc)) != TM_OK) break;
+    for (RingSlot& s : r.slots) if ((rc = ring_slot_size(s, c.vs[i], lane_need(true, max_nb), max_nd)) != TM_OK) break;
   }
   if (rc != TM_OK) { for (Ring* r : rings) r->busy = false; rings.clear(); return rc; }
   *got = true;
@@ -995,20 +939,13 @@ int tokenize_pipeline_on(const tm_vocab* const* vs, uint32_t nv, const uint8_t* 
 // tokenizer (one wait for the id count), the download (one wait).  For pageable buffers, already-normalized text, vocabularies whose
 // normalizer is not the one-pass form, and callers that find the ring taken.
 static int pipeline_lanes(PipeCall& c) {
-  const tm_vocab* const* vs = c.vs; const uint32_t nv = c.nv; const uint8_t* text = c.text; const uint64_t* offsets = c.offsets; const int raw = c.raw;
-  const uint32_t encoding_length = c.enc; uint8_t* bytes_out = c.bytes_out; const uint64_t bytes_cap = c.bytes_cap; uint64_t* byte_offsets = c.byte_offsets;
-  uint32_t* missing = c.missing; tm_pipeline_stats* stats = c.stats;
-  const std::vector<uint32_t>& first = c.first;
-  const size_t nchunks = c.nchunks;
-  const bool in_pinned = c.in_pinned, out_pinned = c.out_pinned;
-  std::atomic<size_t>& next = c.next;
-  const uint32_t nworkers = (uint32_t)std::min<size_t>((size_t)c.lanes * nv, nchunks);
+  const uint32_t nworkers = (uint32_t)std::min<size_t>((size_t)c.lanes * c.nv, c.nchunks);
+  const bool raw = c.raw != 0;
   // A lane works on one chunk at a time, but the raw text of its NEXT chunk is uploaded (on the lane's second stream) as soon as the
   // normalizer pass of the current one is through with the raw buffer: the H2D of chunk k+1 hides behind the tokenizer kernels of chunk k.
   static const bool trace = getenv("TM_TRACE") != nullptr;
-  const double t_pipe0 = c.t0;
   auto worker = [&](uint32_t wi) {
-    const tm_vocab* const v = vs[wi % nv];
+    const tm_vocab* const v = c.vs[wi % c.nv];
     NearDevice near_gpu(v->device);             // (worker 0 is the calling thread: it gets its affinity back when the call returns)
     Lane* l = nullptr;
     int rc = lane_acquire(v, &l);
@@ -1018,49 +955,48 @@ static int pipeline_lanes(PipeCall& c) {
       if (e == hipSuccess) e = hipEventCreateWithFlags(&l->up_done, hipEventDisableTiming);
       if (e != hipSuccess) rc = hip_fail(e, "hipStreamCreate (lane upload)");
     }
-    // chunk k: offsets relative to its first byte into `lo`; uploads it on `st` (through the pinned input staging when the caller's
-    // buffer is pageable, so that the H2D runs at link speed); *srcp = where the text was read from (for a retry)
-    auto upload = [&](size_t k, std::vector<uint64_t>& lo, hipStream_t st, const uint8_t** srcp) -> int {
-      const uint32_t d0 = first[k], nd = first[k + 1] - d0;
-      const uint64_t b0 = offsets[d0], nb = offsets[d0 + nd] - b0;
-      lo.resize((size_t)nd + 1);
-      for (uint32_t d = 0; d <= nd; d++) lo[d] = offsets[d0 + d] - b0;
-      const uint8_t* src = text + b0;
-      if (!in_pinned) {
-        int r = stage_grow(&l->h_stage_in, &l->h_in_cap, nb);
+    // the chunk with its offsets `lo` uploaded on `st` (through the pinned input staging when the caller's buffer is pageable, so that the
+    // H2D runs at link speed); *srcp = where the text was read from (for a retry)
+    auto upload = [&](const PipeCall::Chunk& ch, const std::vector<uint64_t>& lo, hipStream_t st, const uint8_t** srcp) -> int {
+      const uint8_t* src = c.text + ch.b0;
+      if (!c.in_pinned) {
+        int r = lane_pinned(&l->h_stage_in, &l->h_in_cap, ch.nb);
         if (r != TM_OK) return r;
-        std::memcpy(l->h_stage_in, src, nb);
+        std::memcpy(l->h_stage_in, src, ch.nb);
         src = l->h_stage_in;
       }
       *srcp = src;
-      return lane_upload(l, v, src, lo.data(), nd, raw != 0, st);
+      return lane_upload(l, v, src, lo.data(), ch.nd, raw, st);
     };
-    size_t k = rc == TM_OK ? next.fetch_add(1) : nchunks;
+    size_t k = rc == TM_OK ? c.next.fetch_add(1) : c.nchunks;
     bool prefetched = false;
     const uint8_t* src = nullptr;
-    while (rc == TM_OK && k < nchunks) {
+    while (rc == TM_OK && k < c.nchunks) {
       if (c.failed()) break;
-      const uint32_t d0 = first[k], d1 = first[k + 1], nd = d1 - d0;
+      const PipeCall::Chunk ch = c.chunk(k);
       const double tr0 = trace ? now_ms() : 0;
       double tr1 = 0, tr2 = 0, tr3 = 0;
       if (prefetched) {
         hipError_t e = hipStreamWaitEvent(l->stream, l->up_done, 0);
         if (e != hipSuccess) { rc = hip_fail(e, "hipStreamWaitEvent"); break; }
-      } else if ((rc = upload(k, loc, l->stream, &src)) != TM_OK) break;
-      size_t k_next = nchunks;
+      } else {
+        loc.resize((size_t)ch.nd + 1);
+        ch.local_offsets(loc.data());
+        if ((rc = upload(ch, loc, l->stream, &src)) != TM_OK) break;
+      }
+      size_t k_next = c.nchunks;
       bool next_up = false;
       const uint8_t* src_next = nullptr;
       auto prefetch = [&]() -> int {
-        k_next = next.fetch_add(1);
-        if (k_next >= nchunks || !raw) return TM_OK;
-        const uint32_t n0 = first[k_next], nn = first[k_next + 1] - n0;
-        const uint64_t need = lane_need(true, offsets[n0 + nn] - offsets[n0]);
+        k_next = c.next.fetch_add(1);
+        if (k_next >= c.nchunks || !raw) return TM_OK;
+        const PipeCall::Chunk nx = c.chunk(k_next);
         // (a chunk that would replace the workspace, or the per-document arrays the current chunk still reads, is uploaded later)
-        if (!l->ws || l->ws->max_bytes < need || l->ws->max_docs < nn || (uint64_t)nn + 2 > l->ws->raw_docs_cap) return TM_OK;
-        loc_next.resize((size_t)nn + 1);
-        for (uint32_t d = 0; d <= nn; d++) loc_next[d] = offsets[n0 + d] - offsets[n0];
-        if (raw_upload_replaces_buffers(l->ws, loc_next.data(), nn)) return TM_OK;       // (the slabs and piece offsets of the current chunk are read by its match kernel)
-        int r = upload(k_next, loc_next, l->up_stream, &src_next);
+        if (!l->ws || l->ws->max_bytes < lane_need(true, nx.nb) || l->ws->max_docs < nx.nd || (uint64_t)nx.nd + 2 > l->ws->raw_docs_cap) return TM_OK;
+        loc_next.resize((size_t)nx.nd + 1);
+        nx.local_offsets(loc_next.data());
+        if (raw_upload_replaces_buffers(l->ws, loc_next.data(), nx.nd)) return TM_OK;       // (the slabs and piece offsets of the current chunk are read by its match kernel)
+        int r = upload(nx, loc_next, l->up_stream, &src_next);
         if (r != TM_OK) return r;
         hipError_t e = hipEventRecord(l->up_done, l->up_stream);
         if (e != hipSuccess) return hip_fail(e, "hipEventRecord");
@@ -1069,40 +1005,14 @@ static int pipeline_lanes(PipeCall& c) {
       };
       RunOut ro;
       if (trace) tr1 = now_ms();
-      if ((rc = lane_compute(l, v, src, loc.data(), nd, raw != 0, true, &ro, prefetch)) != TM_OK) break;
+      if ((rc = lane_compute(l, v, src, loc.data(), ch.nd, raw, true, &ro, prefetch)) != TM_OK) break;
       if (c.hook(PipeCall::HOOK_EXACT, k)) { rc = PipeCall::hook_fail("exact", k); break; }
       if (trace) tr2 = now_ms();
-      if (k_next == nchunks && !next_up) k_next = next.fetch_add(1);          // (already-normalized input: nothing was prefetched)
-      uint64_t base = 0;
-      if (!c.order(k, ro.total_tokens, &base)) break;          // publish this chunk's count, learn where its ids go
-      if (trace) tr3 = now_ms();
-      tm_batch* b = l->ws;
-      const uint64_t out_b = ro.total_tokens * encoding_length;
-      toff.resize((size_t)nd + 1);
-      if ((rc = small_d2h(b, toff.data(), b->d_tok_offsets, toff.size() * 8, l->stream)) != TM_OK) break;
-      if (missing && nd && (rc = small_d2h(b, missing + d0, b->d_doc_missing, (uint64_t)nd * 4, l->stream)) != TM_OK) break;
-      const bool fits = (base + ro.total_tokens) * encoding_length <= bytes_cap && bytes_out;
-      if (fits && out_b) {
-        uint8_t* dst = bytes_out + base * encoding_length;
-        // (Writing the ids straight into the caller's page-locked buffer from the serialize kernel - no device staging, no copy command - was
-        // built and timed in round 5: 42 - 45 ms per GiB call against 32 - 36 with the copy engine, profiles/r05_h2h.txt: stores of a kernel to
-        // fine-grained host memory cross PCIe far below the engine's rate.  Removed.)
-        if ((rc = lane_dbytes(l, out_b)) != TM_OK) break;
-        launch_serialize(b->d_out, ro.total_tokens, encoding_length, l->d_bytes, l->stream);
-        if (out_pinned) rc = d2h(dst, l->d_bytes, out_b, l->stream, "D2H ids");
-        else {
-          if ((rc = lane_stage(l, out_b)) != TM_OK) break;
-          rc = d2h(l->h_stage, l->d_bytes, out_b, l->stream, "D2H ids");
-        }
-        if (rc != TM_OK) break;
-      }
-      if (c.hook(PipeCall::HOOK_DOWNLOAD, k)) { rc = PipeCall::hook_fail("download", k); break; }
-      if ((rc = small_sync(b, l->stream)) != TM_OK) break;
-      if (fits && out_b && !out_pinned) std::memcpy(bytes_out + base * encoding_length, l->h_stage, out_b);
+      if (k_next == c.nchunks && !next_up) k_next = c.next.fetch_add(1);          // (already-normalized input: nothing was prefetched)
+      bool delivered = false;
+      if ((rc = chunk_deliver(c, l, k, ro.total_tokens, true, toff, &delivered, trace ? &tr3 : nullptr)) != TM_OK || !delivered) break;
       if (trace) fprintf(stderr, "[pipe] worker %u chunk %3zu (%5.1f MiB): start %7.2f  upload/wait %5.2f  compute %5.2f  order-wait %5.2f  download %5.2f  -> end %7.2f ms\n", wi, k,
-                         (offsets[d1] - offsets[d0]) / 1048576.0, tr0 - t_pipe0, tr1 - tr0, tr2 - tr1, tr3 - tr2, now_ms() - tr3, now_ms() - t_pipe0);
-      for (uint32_t d = 1; d <= nd; d++) byte_offsets[d0 + d] = (base + toff[d]) * encoding_length;
-      if (stats) { std::lock_guard<std::mutex> g(c.mu); stats->host_fallback_docs += raw ? b->host_fallback_docs : 0; stats->normalized_bytes += b->nbytes; }
+                         ch.nb / 1048576.0, tr0 - c.t0, tr1 - tr0, tr2 - tr1, tr3 - tr2, now_ms() - tr3, now_ms() - c.t0);
       k = k_next;
       prefetched = next_up;
       if (next_up) { loc.swap(loc_next); src = src_next; }
@@ -1143,7 +1053,7 @@ int tm_decode_batch(const tm_vocab* v, const uint32_t* tokens, const uint64_t* t
   hipError_t e = hipSuccess;
   const bool dev_capcode = !raw && v->host.capcode == 2 && v->host.charset == 1 && ndocs > 0;
   // arena A: ids | document offsets | the decode's own words (dec_arena: tiles of ids, byte offset / decoded length of every document)
-  auto up = [](uint64_t x) { return (x + 255) & ~(uint64_t)255; };
+  const auto up = dec_up;
   const uint64_t o_tok = 0, o_toff = o_tok + up((n + 1) * 4);
   const DecArena a = dec_arena(o_toff + up(((uint64_t)ndocs + 1) * 8), n, ndocs);
   const uint64_t a_bytes = a.bytes;
@@ -1152,25 +1062,25 @@ int tm_decode_batch(const tm_vocab* v, const uint32_t* tokens, const uint64_t* t
   bool need_raw = !dev_capcode;
   const uint8_t *h_dec = nullptr, *h_raw = nullptr;          // decoded / raw bytes in the lane's pinned staging
   do {
-    if ((rc = dev_grow(&l->d_dec_a, &l->d_dec_a_cap, a_bytes, "hipMalloc (decode)")) != TM_OK) break;
+    if ((rc = lane_device(&l->d_dec_a, &l->d_dec_a_cap, a_bytes, "hipMalloc (decode)")) != TM_OK) break;
     uint8_t* A = l->d_dec_a;
     uint32_t* d_tok = (uint32_t*)(A + o_tok); uint64_t* d_toff = (uint64_t*)(A + o_toff);
     uint64_t* d_total = (uint64_t*)(A + a.o_total); uint64_t* d_doff = (uint64_t*)(A + a.o_doff); uint64_t* d_declen = (uint64_t*)(A + a.o_declen);
     // ids and offsets through pinned staging (the caller's buffers are pageable Go / Python memory)
     const uint64_t in_bytes = n * 4 + ((uint64_t)ndocs + 1) * 8;
-    if ((rc = stage_grow(&l->h_stage_in, &l->h_in_cap, in_bytes)) != TM_OK) break;
+    if ((rc = lane_pinned(&l->h_stage_in, &l->h_in_cap, in_bytes)) != TM_OK) break;
     std::memcpy(l->h_stage_in, tok_offsets, ((uint64_t)ndocs + 1) * 8);
     if (n) std::memcpy(l->h_stage_in + ((uint64_t)ndocs + 1) * 8, tokens, n * 4);
     if ((e = hipMemcpyAsync(d_toff, l->h_stage_in, ((uint64_t)ndocs + 1) * 8, hipMemcpyHostToDevice, st)) != hipSuccess ||
         (n && (e = hipMemcpyAsync(d_tok, l->h_stage_in + ((uint64_t)ndocs + 1) * 8, n * 4, hipMemcpyHostToDevice, st)) != hipSuccess)) { rc = hip_fail(e, "H2D tokens"); break; }
     launch_decode_lengths(v, d_tok, n, d_toff, ndocs, a, A, st);
-    if ((rc = lane_stage(l, 8)) != TM_OK) break;
+    if ((rc = lane_pinned(&l->h_stage, &l->h_cap, 8)) != TM_OK) break;
     if ((rc = d2h(l->h_stage, d_total, 8, st, "decode lengths")) != TM_OK) break;
     if ((e = hipStreamSynchronize(st)) != hipSuccess) { rc = hip_fail(e, "hipStreamSynchronize"); break; }
     std::memcpy(&total, l->h_stage, 8);
     // arena B: the gathered bytes | the same after capcode decoding (out of place: the host decoder needs the others as they were)
     const uint64_t o_dec = up(total + 16);
-    if ((rc = dev_grow(&l->d_dec_b, &l->d_dec_b_cap, o_dec + up(total + 16), "hipMalloc (decode output)")) != TM_OK) break;
+    if ((rc = lane_device(&l->d_dec_b, &l->d_dec_b_cap, o_dec + up(total + 16), "hipMalloc (decode output)")) != TM_OK) break;
     uint8_t* d_out = l->d_dec_b; uint8_t* d_dec = l->d_dec_b + o_dec;
     launch_decode_copy(v, d_tok, n, d_toff, ndocs, a, A, d_out, st);
     if (dev_capcode) {
@@ -1179,7 +1089,7 @@ int tm_decode_batch(const tm_vocab* v, const uint32_t* tokens, const uint64_t* t
     }
     // staging: the documents' byte offsets (they come out of the gather) | decoded lengths | decoded text | gathered bytes
     const uint64_t s_doff = 0, s_declen = up(((uint64_t)ndocs + 1) * 8), s_text = s_declen + up((uint64_t)ndocs * 8 + 8), s_raw = s_text + up(total + 16);
-    if ((rc = lane_stage(l, s_raw + up(total + 16))) != TM_OK) break;
+    if ((rc = lane_pinned(&l->h_stage, &l->h_cap, s_raw + up(total + 16))) != TM_OK) break;
     if ((rc = d2h(l->h_stage + s_doff, d_doff, ((uint64_t)ndocs + 1) * 8, st, "decode offsets")) != TM_OK) break;
     if (dev_capcode) {
       uint8_t* hp = l->h_stage + s_text;
@@ -1202,38 +1112,8 @@ int tm_decode_batch(const tm_vocab* v, const uint32_t* tokens, const uint64_t* t
     std::memcpy(doff.data(), l->h_stage + s_doff, doff.size() * 8);
   } while (false);
   if (rc != TM_OK) (void)hipStreamSynchronize(st);      // nothing of this call may still be in flight when the lane goes back
-  if (rc == TM_OK) {
-    if (raw || v->host.capcode == 0) {
-      std::memcpy(out_offsets, doff.data(), doff.size() * 8);
-      if (total > out_cap) rc = set_error(TM_E_NOSPACE, "out_cap %llu < %llu required", (unsigned long long)out_cap, (unsigned long long)total);
-      else if (total) std::memcpy(out, h_raw, total);
-    } else {
-      // the documents the device left alone (anything beyond ASCII; every document of a capcode-1 or UTF-16 vocabulary) go through the host decoder
-      std::vector<uint32_t> todo;
-      for (uint32_t d = 0; d < ndocs; d++) if (!dev_capcode || declen[d] == DEC_HOST) todo.push_back(d);
-      g_decode_host_docs = (uint32_t)todo.size();
-      std::vector<std::vector<uint8_t>> touts;
-      if (!todo.empty()) {
-        std::vector<uint64_t> toff(todo.size() + 1, 0);
-        std::vector<uint8_t> tbytes;
-        for (size_t k = 0; k < todo.size(); k++) {
-          tbytes.insert(tbytes.end(), h_raw + doff[todo[k]], h_raw + doff[todo[k] + 1]);
-          toff[k + 1] = tbytes.size();
-        }
-        capcode_decode_batch(tbytes.data(), toff.data(), (uint32_t)todo.size(), v->host.capcode, 0, touts);
-      }
-      std::vector<uint64_t> hostlen((size_t)ndocs, DEC_HOST);
-      for (size_t k = 0; k < todo.size(); k++) hostlen[todo[k]] = k;
-      uint64_t o = 0;
-      for (uint32_t d = 0; d < ndocs; d++) { out_offsets[d] = o; o += hostlen[d] != DEC_HOST ? touts[hostlen[d]].size() : declen[d]; }
-      out_offsets[ndocs] = o;
-      if (o > out_cap) rc = set_error(TM_E_NOSPACE, "out_cap %llu < %llu required", (unsigned long long)out_cap, (unsigned long long)o);
-      else for (uint32_t d = 0; d < ndocs; d++) {
-        if (hostlen[d] != DEC_HOST) { const auto& t = touts[hostlen[d]]; if (!t.empty()) std::memcpy(out + out_offsets[d], t.data(), t.size()); }
-        else if (declen[d]) std::memcpy(out + out_offsets[d], h_dec + doff[d], declen[d]);
-      }
-    }
-  }
+  // (the documents the device left alone - anything it does not decode; every document of a capcode-1 or UTF-16 vocabulary - go through the host decoder there)
+  if (rc == TM_OK) rc = decode_assemble(v, raw != 0, ndocs, doff.data(), total, h_raw, h_dec, dev_capcode ? declen.data() : nullptr, out, out_cap, out_offsets, &g_decode_host_docs);
   lane_release(v, l);
   return rc;
 }

@@ -2514,18 +2514,57 @@ int small_h2d(tm_batch* b, void* dev_dst, const void* host_src, uint64_t bytes, 
   return TM_OK;
 }
 int small_sync(tm_batch* b, hipStream_t st) {
-  hipError_t e = hipStreamSynchronize(st);
-  if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
+  const hipError_t e = hipStreamSynchronize(st);
+  // The stream's transfers leave the list either way.  Behind a failed wait nothing is copied: the destinations are the caller's buffers or its
+  // stack locals, and an entry left here would have the lane's NEXT small_sync write through them.
   size_t keep = 0;
   for (auto& m : b->mail_pending) {
-    if (m.st == st) std::memcpy(m.dst, m.slot, m.n);
-    else b->mail_pending[keep++] = m;
+    if (m.st != st) b->mail_pending[keep++] = m;
+    else if (e == hipSuccess) std::memcpy(m.dst, m.slot, m.n);
   }
   b->mail_pending.resize(keep);
-  // every copy kernel of this stream is done: the stream no longer has to be waited for when the mailbox wraps (and a caller's
+  // every copy kernel of this stream is done (or lost): the stream no longer has to be waited for when the mailbox wraps (and a caller's
   // stream that is destroyed later is not kept here)
   b->mail_streams.erase(std::remove(b->mail_streams.begin(), b->mail_streams.end(), st), b->mail_streams.end());
+  return e == hipSuccess ? TM_OK : hip_fail(e, "hipStreamSynchronize");
+}
+
+// ---- grow-only buffers (tm_pipeline.h) ------------------------------------------------------------------------------------------------------
+bool is_pinned(const void* p) {
+  if (!p) return false;
+  hipPointerAttribute_t a;
+  if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
+  return a.type == hipMemoryTypeHost;
+}
+int grow_device(uint8_t** buf, uint64_t* cap, uint64_t need, uint64_t alloc, const char* what) {
+  if (*cap >= need) return TM_OK;
+  if (*cap) trace_grow(what, need);
+  (void)hipFree(*buf);
+  *buf = nullptr; *cap = 0;
+  const hipError_t e = hipMalloc((void**)buf, alloc);
+  if (e != hipSuccess) { *buf = nullptr; return hip_fail(e, what); }
+  *cap = alloc;
   return TM_OK;
+}
+int grow_pinned(uint8_t** buf, uint64_t* cap, uint64_t need, uint64_t alloc, const char* what) {
+  if (*cap >= need) return TM_OK;
+  if (*cap) trace_grow(what, need);
+  (void)hipHostFree(*buf);
+  *buf = nullptr; *cap = 0;
+  const hipError_t e = hipHostMalloc((void**)buf, alloc, hipHostMallocDefault);
+  if (e != hipSuccess) { *buf = nullptr; return hip_fail(e, what); }
+  *cap = alloc;
+  return TM_OK;
+}
+int grow_workspace(tm_batch** ws, const tm_vocab* v, uint64_t bytes, uint32_t docs, uint64_t alloc_bytes, const char* what) {
+  tm_batch* const w = *ws;
+  if (w && w->vocab == v && w->max_bytes >= bytes && w->max_docs >= docs) return TM_OK;
+  const uint64_t want_b = std::max<uint64_t>(alloc_bytes, w ? w->max_bytes : 0);
+  const uint64_t want_d = std::max<uint64_t>((uint64_t)docs + docs / 4 + 64, w ? w->max_docs : 0);
+  if (w) trace_grow(what, want_b);
+  tm_batch_free(w);
+  *ws = nullptr;
+  return tm_batch_create(v, want_b, (uint32_t)std::min<uint64_t>(want_d, 0xFFFFFFF0ull), ws);
 }
 
 int error_from_flag(uint32_t err) {

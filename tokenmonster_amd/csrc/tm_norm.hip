@@ -322,6 +322,7 @@ __device__ __forceinline__ uint32_t norm_lead_back(const uint8_t* raw_x) {
   return back;
 }
 static_assert(SLAB == SLAB_BYTES, "k_match_branch stages the text from these slabs");
+static_assert(PIECE == RAW_PIECE, "the ring's issuer counts the pieces of a chunk (tm_host.hip)");
 template <int MODE>
 __global__ __launch_bounds__(256) void k_norm_emit(const uint8_t* __restrict__ raw, const uint64_t* __restrict__ rbegin,
                                                    const uint64_t* __restrict__ rend, const uint32_t* __restrict__ piece_doc,

@@ -16,6 +16,7 @@ constexpr int SEG = 256;                 // bytes of one document segment (one w
 constexpr int NPOS = SEG + 40;           // positions whose descriptors a segment needs (look-ahead <= 40)
 constexpr int NPOS_PAD = (NPOS + 63) / 64 * 64;
 constexpr int TEXT_LEN = SEG + 96;       // staged text: position i may read up to i + 40
+constexpr int RAW_PIECE = 1024;          // bytes of raw text in one piece of the device normalizer (tm_norm.hip)
 constexpr int SLAB_BYTES = 2048;         // the device normalizer's slab for one 1 KiB piece of raw text (tm_norm.hip); K1 can stage the text from there
 constexpr int ENT = 80;                  // entry states of a segment: 40 offsets x fd{0,1}
 #ifndef TM_K1_WAVES
@@ -344,6 +345,14 @@ constexpr uint64_t MAIL_BYTES = 4ull << 20, MAIL_MAX = 1ull << 20;
 int small_d2h(tm_batch* b, void* host_dst, const void* dev_src, uint64_t bytes, hipStream_t st);
 int small_h2d(tm_batch* b, void* dev_dst, const void* host_src, uint64_t bytes, hipStream_t st);
 int small_sync(tm_batch* b, hipStream_t st);
+// Grow-only buffers outside tm_batch::device_bytes (tm_kernels.hip): lanes, ring slots, document slots, the decode arenas.  A buffer of at least `need` bytes
+// stays; a smaller one is replaced by one of `alloc` bytes (the caller's headroom), and `what` names it in the [grow] line of TM_TRACE and in the
+// error message.  On failure the pointer is null and the capacity 0.
+bool is_pinned(const void* p);      // page-locked host memory (hipHostMalloc / hipHostRegister)
+int grow_device(uint8_t** buf, uint64_t* cap, uint64_t need, uint64_t alloc, const char* what);
+int grow_pinned(uint8_t** buf, uint64_t* cap, uint64_t need, uint64_t alloc, const char* what);
+// ... and a workspace of `v` for `bytes` of text in `docs` documents: a smaller one (or another vocabulary's) is replaced by one of alloc_bytes and docs + 25 %
+int grow_workspace(tm_batch** ws, const tm_vocab* v, uint64_t bytes, uint32_t docs, uint64_t alloc_bytes, const char* what);
 int batch_upload_on(tm_batch* b, const uint8_t* text, const uint64_t* offsets, uint32_t ndocs, hipStream_t st);
 void launch_serialize(const uint32_t* ids, uint64_t n, uint32_t enc, uint8_t* out, hipStream_t st);
 // the host-to-host ring: a chunk's stages behind the upload enqueued on `st` without a host round trip (tm_norm.hip / tm_kernels.hip)
@@ -363,8 +372,9 @@ constexpr uint64_t DEC_HOST = ~0ull;      // k_dec_capcode's length of a documen
 // tile | scan block sums | total | byte offset of every document | decoded length of every document
 struct DecArena { uint64_t ntiles, o_len, o_first, o_off, o_sums, o_total, o_doff, o_declen, bytes; };
 constexpr uint32_t DEC_TILE_IDS = 2048;
+inline uint64_t dec_up(uint64_t x) { return (x + 255) & ~(uint64_t)255; }      // the parts of the decode's arenas begin on 256-byte boundaries
 inline DecArena dec_arena(uint64_t base, uint64_t n, uint32_t ndocs) {
-  auto up = [](uint64_t x) { return (x + 255) & ~(uint64_t)255; };
+  const auto up = dec_up;
   DecArena a;
   a.ntiles = (n + DEC_TILE_IDS - 1) / DEC_TILE_IDS;
   const uint64_t sblocks = (a.ntiles + 1 + SCAN_CH - 1) / SCAN_CH + 2;
@@ -377,6 +387,13 @@ void launch_decode_lengths(const tm_vocab* v, const uint32_t* d_tok, uint64_t n,
 void launch_decode_copy(const tm_vocab* v, const uint32_t* d_tok, uint64_t n, const uint64_t* d_toff, uint32_t ndocs, const DecArena& a, uint8_t* A, uint8_t* d_out, hipStream_t st);
 // d_sums: two words the kernel adds up - bytes the device decoded, documents it left to the host decoder
 int launch_decode_capcode(const tm_vocab* v, const uint8_t* d_out, const uint64_t* d_doff, uint32_t ndocs, uint8_t* d_dec, uint64_t* d_declen, uint64_t* d_sums, hipStream_t st);
+// The host's part of a decode, once everything is in host memory: doff[ndocs + 1] the documents' offsets in the `total` gathered bytes, `decoded` the
+// same after the device's capcode decoder with declen[ndocs] its lengths (both null: the decoder did not run; DEC_HOST: a document it left alone).
+// Documents without a device-decoded form go through capcode_decode_batch - none when `raw` or the vocabulary has no capcode: the gathered bytes are
+// the text then.  out_offsets[ndocs + 1] is always filled; TM_E_NOSPACE (nothing written to out) if out_cap is too small; TM_E_INTERNAL for offsets
+// that are not monotone or reach beyond `total`.  *host_docs (may be null): documents decoded on the host.
+int decode_assemble(const tm_vocab* v, bool raw, uint32_t ndocs, const uint64_t* doff, uint64_t total, const uint8_t* gathered, const uint8_t* decoded, const uint64_t* declen,
+                    uint8_t* out, uint64_t out_cap, uint64_t* out_offsets, uint32_t* host_docs);
 // tm_host.hip: tm_tokenize_pipeline over the lanes of one vocabulary or of its replicas on several devices
 int tokenize_pipeline_on(const tm_vocab* const* vs, uint32_t nv, const uint8_t* text, const uint64_t* offsets, uint32_t ndocs, int raw, uint32_t encoding_length,
                          uint64_t chunk_bytes, uint32_t lanes, uint8_t* bytes_out, uint64_t bytes_cap, uint64_t* byte_offsets, uint32_t* missing,

@@ -60,6 +60,20 @@ int main() {
     if (tm_tokenize_pipeline(v, raw.data(), roff.data(), nd, 1, 2, 96 << 10, 2, s2.data(), s2.size(), so.data(), ms.data(), &e2, nullptr) != TM_OK) { bad++; return; }
     if (so[nd] != soff[nd] || std::memcmp(s2.data(), ser.data(), so[nd]) != 0) bad++;
   });
+  // the other forms of the one-shot body beside them: the spans of already-normalized and of raw text, the serialized ids, and a call that is refused
+  th.emplace_back([&] {
+    for (int round = 0; round < 2; round++) {
+      std::vector<uint32_t> out(toff[nd] + 64), sp(2 * (toff[nd] + 64)), ms(nd + 1); std::vector<uint64_t> to(nd + 1);
+      if (tm_tokenize_batch_spans(v, text, off.data(), nd, out.data(), toff[nd], to.data(), sp.data(), ms.data()) != TM_OK) { bad++; return; }
+      if (to[nd] != toff[nd] || std::memcmp(out.data(), ids.data(), toff[nd] * 4) != 0) { bad++; return; }
+      if (tm_tokenize_batch_raw_spans(v, raw.data(), roff.data(), nd, out.data(), toff[nd], to.data(), sp.data(), ms.data()) != TM_OK) { bad++; return; }
+      if (to[nd] != toff[nd] || std::memcmp(out.data(), ids.data(), toff[nd] * 4) != 0) { bad++; return; }
+      if (tm_tokenize_batch_spans(v, text, off.data(), nd, out.data(), toff[nd] - 1, to.data(), sp.data(), ms.data()) != TM_E_NOSPACE || to[nd] != toff[nd]) { bad++; return; }
+      std::vector<uint8_t> s2(ser.size()); std::vector<uint64_t> so(nd + 1); uint32_t e2 = 0;
+      if (tm_tokenize_batch_serialized(v, text, off.data(), nd, 2, s2.data(), s2.size(), so.data(), ms.data(), &e2) != TM_OK) { bad++; return; }
+      if (so[nd] != soff[nd] || std::memcmp(s2.data(), ser.data(), so[nd]) != 0) bad++;
+    }
+  });
   // decode jobs beside the tokenize jobs (tokenmonsterserver jobs 2-9): same lanes, same answers as a single-threaded decode
   std::vector<uint8_t> dec(off[nd] * 2 + 4096); std::vector<uint64_t> doff(nd + 1);
   CHECK(tm_decode_batch(v, ids.data(), toff.data(), nd, 0, dec.data(), dec.size(), doff.data()));
@@ -107,6 +121,6 @@ int main() {
   tm_vocab_free(v);
   tm_free(text); tm_free(img);
   if (bad.load()) { std::fprintf(stderr, "%d caller(s) got a wrong result\n", bad.load()); return 1; }
-  std::printf("tsan_host ok: %u documents, %llu ids, 13 concurrent callers (two of them through the multi-device driver)\n", nd, (unsigned long long)toff[nd]);
+  std::printf("tsan_host ok: %u documents, %llu ids, 14 concurrent callers (two of them through the multi-device driver)\n", nd, (unsigned long long)toff[nd]);
   return 0;
 }
