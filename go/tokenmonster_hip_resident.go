@@ -410,6 +410,55 @@ func (b *HipBatch) Pack(how HipCollate, stream unsafe.Pointer, rowsCap uint64, i
 	return 0, err
 }
 
+// WindowRows is the number of rows Windows writes for these documents: a document longer than a row takes several rows, consecutive rows of a
+// document share `overlap` ids (tm_batch_window_rows).  KeepTail has no meaning here and is an error.
+func (b *HipBatch) WindowRows(how HipCollate, overlap uint32) (uint64, error) {
+	h := how.c()
+	var rows C.uint64_t
+	_, err := locked(func() C.int { return C.tm_batch_window_rows(b.h, &h, C.uint32_t(overlap), &rows) })
+	return uint64(rows), err
+}
+
+// Windows lays the documents out as overlapping rows of RowLen: ids[rows * RowLen] of IdBytes each; mask (may be nil) a byte per id; lengths,
+// rowDoc - the row's document, counted from FirstDoc - and rowStart - the index inside the document of the row's first id - (each may be nil)
+// a uint32 per row (tm_batch_windows).  With rowsCap too small nothing is written and the rows needed are returned.
+func (b *HipBatch) Windows(how HipCollate, overlap uint32, stream unsafe.Pointer, rowsCap uint64, ids, mask, lengths, rowDoc, rowStart unsafe.Pointer) (uint64, error) {
+	h := how.c()
+	rc, err := locked(func() C.int {
+		return C.tm_batch_windows(b.h, &h, C.uint32_t(overlap), stream, C.uint64_t(rowsCap), ids, (*C.uint8_t)(mask), (*C.uint32_t)(lengths),
+			(*C.uint32_t)(rowDoc), (*C.uint32_t)(rowStart))
+	})
+	if err == nil && rc == C.TM_E_NOSPACE {
+		return b.WindowRows(how, overlap)
+	}
+	return 0, err
+}
+
+// WindowsSpans is the companion of Windows: spans [rows, RowLen, 2] elements of spanBytes 4 or 8, the pair of every column that holds an id of
+// the document, counted from the document's start in the normalized text, (0, 0) on BOS, EOS and padding (tm_batch_windows_spans).
+func (b *HipBatch) WindowsSpans(how HipCollate, overlap uint32, stream unsafe.Pointer, rowsCap uint64, spans unsafe.Pointer, spanBytes uint32) (uint64, error) {
+	h := how.c()
+	rc, err := locked(func() C.int {
+		return C.tm_batch_windows_spans(b.h, &h, C.uint32_t(overlap), stream, C.uint64_t(rowsCap), spans, C.uint32_t(spanBytes))
+	})
+	if err == nil && rc == C.TM_E_NOSPACE {
+		return b.WindowRows(how, overlap)
+	}
+	return 0, err
+}
+
+// WindowsRawSpans is WindowsSpans counted in the raw text (tm_batch_windows_raw_spans).
+func (b *HipBatch) WindowsRawSpans(how HipCollate, overlap uint32, stream unsafe.Pointer, rowsCap uint64, spans unsafe.Pointer, spanBytes uint32) (uint64, error) {
+	h := how.c()
+	rc, err := locked(func() C.int {
+		return C.tm_batch_windows_raw_spans(b.h, &h, C.uint32_t(overlap), stream, C.uint64_t(rowsCap), spans, C.uint32_t(spanBytes))
+	})
+	if err == nil && rc == C.TM_E_NOSPACE {
+		return b.WindowRows(how, overlap)
+	}
+	return 0, err
+}
+
 // LoadIds makes the rows of a [nrows, rowLen] tensor of ids the documents of the batch, as a run would have left them (Decode, Download follow).
 func (b *HipBatch) LoadIds(rows unsafe.Pointer, nrows, rowLen, idBytes int, lengths unsafe.Pointer, pad, bos, eos uint32, stream unsafe.Pointer) error {
 	_, err := locked(func() C.int {

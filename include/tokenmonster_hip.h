@@ -365,6 +365,44 @@ int tm_batch_collate_raw_spans(tm_batch* b, const tm_collate* how, void* stream,
 int tm_tokenize_batch_raw_spans(const tm_vocab* v, const uint8_t* raw, const uint64_t* offsets, uint32_t ndocs,
                                 uint32_t* tokens_out, uint64_t tokens_cap, uint64_t* tok_offsets, uint32_t* spans_out, uint32_t* missing);
 
+/* ---- sliding windows: a long document as several rows that overlap (stride / return_overflowing_tokens / overflow_to_sample_mapping) ------- */
+/* The third layout beside tm_batch_collate (which drops what does not fit a row) and tm_batch_pack (which cuts where the stream crosses a row
+ * end): every id of every document is kept, a document longer than a row becomes several rows, and consecutive rows of a document share
+ * `overlap` ids.  The same tm_collate; the overlap travels beside it.  With ns the number of specials given (bos_id, eos_id):
+ * room = row_len - ns content ids per row, step = room - overlap.  room < 1 or overlap >= room: TM_E_INVALID.  A document of n ids yields
+ * w(n) = 1 rows if n <= room (an empty document too: its specials and padding), else 1 + ceil((n - room) / step).  Row k of the document is
+ * [bos] ids[k * step .. min(k * step + room, n)) [eos], then pad_id up to row_len - on the left under TM_COLLATE_PAD_LEFT: every row of a
+ * document but its last is full, and the last holds at least one id the one before did not.  Rows stand in the order of the documents, then
+ * of k.  TM_COLLATE_KEEP_TAIL has no meaning here: TM_E_INVALID.  The ids are those of the ONE walk over the whole document: tokenizing the
+ * text of a window by itself gives other ids at the cuts.
+ * tm_batch_window_rows: the rows that takes, sum of w(n) over the documents - counted on the device (a count per document, a scan of them
+ * into a grow-only buffer of the batch, counted in tm_batch_device_bytes), one number read back; synchronizes like tm_batch_pack_rows.
+ * tm_batch_windows does the same and then, on `stream`, finds the document of every row (4 bytes per row in a second such buffer) and writes
+ * the rows: ids_out[rows * row_len] elements of id_bytes; mask_out (may be NULL)
+ * [rows * row_len] bytes, 1 on an entry and 0 on padding; lengths_out (may be NULL) [rows]: entries of a row, specials included; row_doc_out
+ * (may be NULL) [rows]: the row's document, counted from first_doc (overflow_to_sample_mapping); row_start_out (may be NULL) [rows]: k * step,
+ * the index inside the document of the row's first content id.  rows_cap smaller than the rows needed: TM_E_NOSPACE, nothing is written,
+ * tm_last_error names the number (tm_batch_window_rows returns it); more than 2^36 elements in one output: TM_E_LIMIT.  Otherwise outputs,
+ * alignment, stores and errors are those of tm_batch_collate (not its freedom of streams: below).
+ * tm_batch_windows_spans / tm_batch_windows_raw_spans: spans_out[rows * row_len * 2] elements of span_bytes 4 or 8, (begin, end) per column
+ * - a content column gets exactly the pair tm_batch_spans / tm_batch_raw_spans give for its id, so a document's offsets keep counting from
+ * the DOCUMENT's start in every one of its rows; BOS, EOS and padding get (0, 0).  The ragged pairs are produced first, on `stream`, into the
+ * batch's own buffer as for tm_batch_collate_spans / tm_batch_collate_raw_spans, whose errors apply: ids from tm_batch_load_ids, or for the
+ * raw form a text that did not come from tm_batch_upload_raw + tm_batch_normalize, are TM_E_INVALID.
+ * The calls change nothing a later call reads - ids, offsets, totals, missing stay as they are.
+ * Streams - stricter than for tm_batch_collate: EVERY one of the four calls, tm_batch_window_rows included, rewrites the rows per document
+ * and their offsets in the batch's buffer on the stream of the batch's last run, and the fill calls rewrite the document of every row (and
+ * the span forms the ragged pairs) on `stream`, while a fill reads all of them on `stream`.  So before the next window call of any kind on
+ * the batch, the last fill must have completed or have run on the stream of the batch's last run - passing that stream to every call is
+ * the simple way. */
+int tm_batch_window_rows(tm_batch* b, const tm_collate* how, uint32_t overlap, uint64_t* rows_needed);   /* synchronizes like tm_batch_pack_rows */
+int tm_batch_windows(tm_batch* b, const tm_collate* how, uint32_t overlap, void* stream, uint64_t rows_cap,
+                     void* ids_out, uint8_t* mask_out, uint32_t* lengths_out, uint32_t* row_doc_out, uint32_t* row_start_out);
+int tm_batch_windows_spans(tm_batch* b, const tm_collate* how, uint32_t overlap, void* stream, uint64_t rows_cap,
+                           void* spans_out, uint32_t span_bytes);
+int tm_batch_windows_raw_spans(tm_batch* b, const tm_collate* how, uint32_t overlap, void* stream, uint64_t rows_cap,
+                               void* spans_out, uint32_t span_bytes);
+
 /* Streaming Decoder (go/tokenmonster.go:552-700 NewDecoder / Decode / DecodeSerialized / Flush; server jobs 5-9): ids arrive a few
  * at a time, a call returns the text that is COMPLETE so far; the bytes of a character that is not (a token may end in the middle of a
  * UTF-8 sequence) and the state of the capcode decoder are carried to the next call.  Per-connection host state: the gather of a

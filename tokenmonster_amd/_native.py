@@ -89,6 +89,10 @@ SIGNATURES = {
     "tm_batch_raw_spans_timed": (C.c_int, [vp, vp, vp, C.c_uint64, u32p, f32p]),
     "tm_batch_collate_raw_spans": (C.c_int, [vp, vp, vp, vp, C.c_uint32]),
     "tm_tokenize_batch_raw_spans": (C.c_int, [vp, vp, vp, C.c_uint32, vp, C.c_uint64, vp, vp, vp]),
+    "tm_batch_window_rows": (C.c_int, [vp, vp, C.c_uint32, u64p]),
+    "tm_batch_windows": (C.c_int, [vp, vp, C.c_uint32, vp, C.c_uint64, vp, vp, vp, vp, vp]),
+    "tm_batch_windows_spans": (C.c_int, [vp, vp, C.c_uint32, vp, C.c_uint64, vp, C.c_uint32]),
+    "tm_batch_windows_raw_spans": (C.c_int, [vp, vp, C.c_uint32, vp, C.c_uint64, vp, C.c_uint32]),
     "tm_decoder_new":(C.c_int, [vp, C.POINTER(vp)]),
     "tm_decoder_free": (None, [vp]),
     "tm_decoder_decode": (C.c_int, [vp, vp, C.c_uint64, vp, C.c_uint64, u64p]),

@@ -65,6 +65,57 @@ __device__ __forceinline__ RowPlan row_plan(const CollateArgs& a, uint64_t r) {
   return p;
 }
 
+// ---- a position of a stream of documents -> its document ---------------------------------------------------------------------------------------------
+// key(d) = toff[d] - toff[0] + d * sep: where document d begins in the stream (sep = 1: every document is followed by a separator).  The
+// cursor holds the document d with key(d) <= p < key(d + 1) - for an empty document without separator there is no such p, it vanishes.
+struct DocCursor {
+  const uint64_t* toff;
+  uint32_t nd, sep, d;
+  uint64_t base, next;        // key(d), key(d + 1)
+  __device__ __forceinline__ uint64_t key(uint32_t k) const { return toff[k] - toff[0] + (uint64_t)k * sep; }
+  // p < key(nd) and key(from) <= p
+  __device__ __forceinline__ void seek(uint64_t p, uint32_t from) {
+    uint32_t lo = from, hi = nd;      // invariant: key(lo) <= p < key(hi)
+    while (hi - lo > 1) {
+      const uint32_t mid = lo + (hi - lo) / 2;
+      if (key(mid) <= p) lo = mid; else hi = mid;
+    }
+    d = lo; base = key(lo); next = key(lo + 1);
+  }
+  // the next position asked for is >= the last one: stay, or search the documents behind (never a walk: a run of empty documents is legal)
+  __device__ __forceinline__ void advance(uint64_t p) { if (p >= next) seek(p, d + 1); }
+};
+
+// ---- overlapping windows of a document as rows (tm_batch_windows, tm_batch_windows_spans: tm_windows.hip) -------------------------------------
+// room = L - specials content ids per row, consecutive rows of a document step = room - overlap ids apart.  win_off[d]: the first row of
+// document d (a scan of the windows per document); row_doc[r]: the document of row r (a search over win_off, once per row).
+struct WindowArgs {
+  const uint32_t* ids;        // the batch's ids
+  const uint64_t* toff;       // tok_offsets + first_doc
+  const uint64_t* win_off;    // [nd + 1]
+  const uint32_t* row_doc;    // [rows]
+  uint64_t rows;              // win_off[nd]
+  uint32_t nd, L, room, step, pad, bos, eos, flags;      // bos / eos: TM_NONE = none
+};
+// windows of a document of n ids: one if it fits (an empty document too), else one more for every `step` ids, or part of them, beyond `room`
+__host__ __device__ __forceinline__ uint64_t window_count(uint64_t n, uint32_t room, uint32_t step) {
+  return n <= room ? 1u : 1u + (n - room + step - 1) / step;
+}
+// what row r holds: RowPlan as above, its document and the index of its first content id inside the document
+struct WinPlan { RowPlan p; uint64_t start; uint32_t d; };
+__device__ __forceinline__ WinPlan win_plan(const WindowArgs& a, uint64_t r) {
+  WinPlan w;
+  w.d = a.row_doc[r];
+  const uint64_t b0 = a.toff[w.d], n = a.toff[w.d + 1] - b0;
+  const uint32_t ns = (a.bos != TM_NONE ? 1u : 0u) + (a.eos != TM_NONE ? 1u : 0u);
+  w.start = (r - a.win_off[w.d]) * a.step;           // (<= n - 1 for every window but an empty document's only one)
+  const uint32_t m = (uint32_t)std::min<uint64_t>(n - w.start, a.room);
+  w.p.src = b0 + w.start;
+  w.p.len = m + ns;
+  w.p.lo = (a.flags & TM_COLLATE_PAD_LEFT) ? a.L - w.p.len : 0u;
+  return w;
+}
+
 constexpr uint64_t COLLATE_MAX_ELEMS = 1ull << 36;       // elements of one output: keeps every grid below 2^31 workgroups
 
 inline uint32_t grid_of(uint64_t items) { return (uint32_t)((items + 255) / 256); }
@@ -75,5 +126,7 @@ inline int launch_check() {
 
 // the arguments every layout shares (ids_out: only that it is there)
 int check_how(const tm_batch* b, const tm_collate* how, const void* ids_out, const char* who);
+// tm_spans.hip: no document of the run is 2^32 bytes or longer (offsets are 32 bits)
+int spans_check_lengths(tm_batch* b, const char* who);
 
 }  // namespace tmh

@@ -54,27 +54,6 @@ __global__ __launch_bounds__(256) void k_collate_rows(CollateArgs a, Flat f, T* 
   flat_store<T>(out, e0, cnt, vals);
 }
 
-// ---- a position of a stream of documents -> its document ---------------------------------------------------------------------------------------------
-// key(d) = toff[d] - toff[0] + d * sep: where document d begins in the stream (sep = 1: every document is followed by a separator).  The
-// cursor holds the document d with key(d) <= p < key(d + 1) - for an empty document without separator there is no such p, it vanishes.
-struct DocCursor {
-  const uint64_t* toff;
-  uint32_t nd, sep, d;
-  uint64_t base, next;        // key(d), key(d + 1)
-  __device__ __forceinline__ uint64_t key(uint32_t k) const { return toff[k] - toff[0] + (uint64_t)k * sep; }
-  // p < key(nd) and key(from) <= p
-  __device__ __forceinline__ void seek(uint64_t p, uint32_t from) {
-    uint32_t lo = from, hi = nd;      // invariant: key(lo) <= p < key(hi)
-    while (hi - lo > 1) {
-      const uint32_t mid = lo + (hi - lo) / 2;
-      if (key(mid) <= p) lo = mid; else hi = mid;
-    }
-    d = lo; base = key(lo); next = key(lo + 1);
-  }
-  // the next position asked for is >= the last one: stay, or search the documents behind (never a walk: a run of empty documents is legal)
-  __device__ __forceinline__ void advance(uint64_t p) { if (p >= next) seek(p, d + 1); }
-};
-
 // ---- k_pack_stream: ids(doc0) [eos] ids(doc1) [eos] ... cut into rows -------------------------------------------------------------------------------------
 struct PackArgs {
   const uint32_t* ids;

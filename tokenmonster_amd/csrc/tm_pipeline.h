@@ -251,6 +251,10 @@ struct tm_batch {
   uint64_t own_cap = 0;
   uint8_t* d_own_tmp = nullptr;         // ... and what k_norm_carry writes on the side when the origin pass runs it again
   uint64_t own_tmp_cap = 0;
+  uint8_t* d_win = nullptr;             // tm_batch_windows: win_off[cap + 1] (u64) | the scan's block sums and total (u64) | windows per document (u32), grow-only (tm_windows.hip)
+  uint32_t win_cap = 0;                 // ... in documents
+  uint32_t* d_win_rows = nullptr;       // ... and the document of every row of the last window call, grow-only
+  uint64_t win_rows_cap = 0;
   uint16_t* d_out16 = nullptr;          // set for the length of a launch: K4 writes two-byte ids here instead (a chunk of the ring, launch_emit)
   uint64_t out16_cap = 0;
   // a chunk of the host-to-host ring (tm_host.hip): what the host would have read back between the stages - the number of segments the normalizer

@@ -278,7 +278,7 @@ int spans_reserve(tm_batch* b, uint64_t n) {
 
 // offsets are 32 bits: no document of the run may be 2^32 bytes or longer.  Only a run of 2^24 segments or more can hold one; then the
 // documents' ranges are fetched and looked at (the stream of the run has been waited for).
-static int spans_check_lengths(tm_batch* b, const char* who) {
+int spans_check_lengths(tm_batch* b, const char* who) {
   if (b->nseg < (1ull << 32) / SEG) return TM_OK;
   std::vector<uint64_t> lo(b->ndocs), hi(b->ndocs);
   hipError_t e;

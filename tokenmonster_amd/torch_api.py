@@ -1,7 +1,8 @@
 """Fixed-shape id tensors for code that lives beside this library in one PyTorch-ROCm process: text -> [rows, L] CUDA tensors and back,
-without an id crossing the host link (tm_batch_collate / tm_batch_pack / tm_batch_load_ids, include/tokenmonster_hip.h).
+without an id crossing the host link (tm_batch_collate / tm_batch_windows / tm_batch_pack / tm_batch_load_ids, include/tokenmonster_hip.h).
 
     encode_batch   one document per row: padded or truncated, BOS / EOS, attention mask, lengths
+    encode_windows every id kept: a long document as several rows that overlap, with the row -> document map
     pack_batch     the pre-training form: one EOS-separated id stream cut into rows, with document numbers and positions
     decode_batch   a [rows, L] tensor of ids -> list of bytes
 
@@ -177,6 +178,51 @@ def encode_batch(vocab, docs, max_length, *, pad_id, bos_id=None, eos_id=None, p
             spans = torch.empty((nd, max_length, 2), dtype=torch.int64, device=dev)
             fn = N.lib.tm_batch_collate_raw_spans if return_offsets == "raw" else N.lib.tm_batch_collate_spans
             N.check(fn(b, C.byref(how), st, spans.data_ptr(), 8))
+            res["offset_mapping"] = spans
+    return res
+
+
+def encode_windows(vocab, docs, max_length, overlap, *, pad_id, bos_id=None, eos_id=None, pad_left=False, dtype=None, raw=True, device=None, return_offsets=False):
+    """documents -> overlapping rows, every id kept: a document with more ids than a row holds takes several rows, consecutive rows of a
+    document share `overlap` ids (the stride / return_overflowing_tokens of other tokenizers; tm_batch_windows).  {"input_ids" [rows,
+    max_length] of `dtype` (default int64), "attention_mask" [rows, max_length] bool, "lengths" [rows] int32, "overflow_to_sample_mapping"
+    [rows] int32 - the document of a row -, "window_start" [rows] int32 - the index inside the document of the row's first id}.  Row k of a
+    document is [bos] ids[k * step : k * step + room] [eos] pad..., room = max_length less the specials given, step = room - overlap; the
+    ids are those of the one walk over the whole document.  return_offsets as for encode_batch: "offset_mapping" [rows, max_length, 2]
+    int64 counts from the DOCUMENT's start in every row (tm_batch_windows_spans / tm_batch_windows_raw_spans)."""
+    if isinstance(return_offsets, str):
+        if return_offsets != "raw":
+            raise ValueError("return_offsets %r: False, True or \"raw\"" % (return_offsets,))
+        if not raw:
+            raise ValueError("return_offsets=\"raw\" needs raw=True: normalized documents have no raw text to point into")
+    torch = _torch()
+    dtype = dtype or torch.int64
+    id_bytes = _check_dtype(torch, dtype)
+    max_length, overlap = int(max_length), int(overlap)
+    room = max_length - (bos_id is not None) - (eos_id is not None)
+    if room < 1:
+        raise ValueError("max_length %d holds no id beside the specials" % max_length)
+    if not 0 <= overlap < room:
+        raise ValueError("overlap %d: 0 .. %d (rows of %d ids beside the specials)" % (overlap, room - 1, room))
+    dev = _device(vocab, device)
+    with torch.cuda.device(dev):
+        st = _stream(dev)
+        b, nd = _tokenize(vocab, docs, raw, st)
+        how = _Collate(0, nd, max_length, id_bytes, int(pad_id), _special(bos_id), _special(eos_id), PAD_LEFT if pad_left else 0)
+        rows = C.c_uint64()
+        N.check(N.lib.tm_batch_window_rows(b, C.byref(how), overlap, C.byref(rows)))
+        rows = int(rows.value)
+        ids = torch.empty((rows, max_length), dtype=dtype, device=dev)
+        mask = torch.empty((rows, max_length), dtype=torch.uint8, device=dev)
+        lengths, row_doc, row_start = (torch.empty((rows,), dtype=torch.int32, device=dev) for _ in range(3))
+        if rows:
+            N.check(N.lib.tm_batch_windows(b, C.byref(how), overlap, st, rows, ids.data_ptr(), mask.data_ptr(), lengths.data_ptr(), row_doc.data_ptr(), row_start.data_ptr()))
+        res = {"input_ids": ids, "attention_mask": mask.view(torch.bool), "lengths": lengths, "overflow_to_sample_mapping": row_doc, "window_start": row_start}
+        if return_offsets:
+            spans = torch.empty((rows, max_length, 2), dtype=torch.int64, device=dev)
+            fn = N.lib.tm_batch_windows_raw_spans if return_offsets == "raw" else N.lib.tm_batch_windows_spans
+            if rows:
+                N.check(fn(b, C.byref(how), overlap, st, rows, spans.data_ptr(), 8))
             res["offset_mapping"] = spans
     return res
 

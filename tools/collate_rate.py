@@ -2,7 +2,8 @@
 
     python tools/collate_rate.py [--mib 256] [--out profiles/collate.txt]
 
-collate at int64 and pack at uint16 (both L = 2048) and load_ids of the int64 rows, on the ids of a --mib MiB batch of the benchmark's
+collate at int64 and pack at uint16 (both L = 2048), windows at int64 beside a collate of the same output element count (L = 256 and L = 2048) and load_ids
+of the int64 rows, on the ids of a --mib MiB batch of the benchmark's
 englishcode-32000 shape.  HIP events (torch's) around the launches on ONE stream; GB/s counts the bytes a call reads plus the bytes it writes;
 the yardstick is hipMemcpyAsync device to device of that many bytes (half read, half written), timed the same way.  Three warm-up calls, then
 the median of 20.  (tm_batch_collate / tm_batch_pack wait for the batch's last run before they launch and tm_batch_pack_rows fetches two
@@ -90,6 +91,44 @@ def main():
         ppo = torch.empty((r, L), dtype=torch.int32, device="cuda")
         med, lo, hi = timed(lambda: N.check(N.lib.tm_batch_pack(b, C.byref(howp), st, r, pids.data_ptr(), pdi.data_ptr(), ppo.data_ptr())), stream)
         report("pack uint16 + doc_index + position", n_ids * 4 + r * L * 10, med, lo, hi)
+        # windows, int64, beside a collate of the SAME output element count: rows of LW ids with OV shared, over the first documents whose
+        # windows make at most nd rows (bisection over tm_batch_window_rows), and a collate of that many documents at LW.  In front of the fill
+        # kernels a windows call finds the document of every row (k_window_row_docs: one binary search per row); the fill then differs from
+        # the collate's by one load of that map per row it touches, and reads every id (the collate only what a row keeps)
+        def windows_pair(LW, OV):
+            need = C.c_uint64()
+
+            def window_rows(k):
+                hw = torch_api._Collate(0, k, LW, 8, pad, N.TM_NONE, N.TM_NONE, 0)
+                N.check(N.lib.tm_batch_window_rows(b, C.byref(hw), OV, C.byref(need)))
+                return int(need.value)
+
+            lo_d, hi_d = 1, nd
+            while lo_d < hi_d:
+                mid = (lo_d + hi_d + 1) // 2
+                lo_d, hi_d = (mid, hi_d) if window_rows(mid) <= nd else (lo_d, mid - 1)
+            ndw, rw = lo_d, window_rows(lo_d)
+            howw = torch_api._Collate(0, ndw, LW, 8, pad, N.TM_NONE, N.TM_NONE, 0)
+            howc = torch_api._Collate(0, rw, LW, 8, pad, N.TM_NONE, N.TM_NONE, 0)
+            wids = torch.empty((rw, LW), dtype=torch.int64, device="cuda")
+            wmask = torch.empty((rw, LW), dtype=torch.uint8, device="cuda")
+            wlens = torch.empty((rw,), dtype=torch.int32, device="cuda")
+            for rep in range(3):                                         # (repeated: the spread of the collate runs is the noise to read the pair against)
+                med, lo, hi = timed(lambda: N.check(N.lib.tm_batch_collate(b, C.byref(howc), st, wids.data_ptr(), wmask.data_ptr(), wlens.data_ptr())), stream)
+                keptc = int(wlens.to(torch.int64).sum().item())
+                report("collate int64, %d rows of %d [%d]" % (rw, LW, rep), keptc * 4 + rw * LW * 9 + rw * 4, med, lo, hi)
+                med, lo, hi = timed(lambda: N.check(N.lib.tm_batch_windows(b, C.byref(howw), OV, st, rw, wids.data_ptr(), wmask.data_ptr(), wlens.data_ptr(), None, None)), stream)
+                keptw = int(wlens.to(torch.int64).sum().item())
+                report("windows int64, %d rows of %d [%d]" % (rw, LW, rep), keptw * 4 + rw * LW * 9 + rw * 4, med, lo, hi)
+                # the part of a windows call in front of k_window_row_docs and the fill - count, scan, one 8-byte read-back, a wait for the stream - is
+                # tm_batch_window_rows; what is left holds the row-docs kernel too
+                rmed, rlo, rhi = timed(lambda: window_rows(ndw), stream)
+                lines.append("window_rows alone [%d]                 %8.3f ms (%.3f .. %.3f)  -> row docs + fill: windows less window_rows = %.3f ms" % (rep, rmed, rlo, rhi, med - rmed))
+                print(lines[-1], flush=True)
+            lines.append("(windows: %d documents -> %d rows, overlap %d; a call = tm_batch_window_rows' work, then the row docs and the fill)" % (ndw, rw, OV))
+
+        windows_pair(256, 32)          # 19 M elements: the outputs stay in the cache, latency shows
+        windows_pair(2048, 256)        # 154 M elements: bound by HBM bytes like the collate line above
         # load_ids of the int64 rows: the extents pass reads every element once, the gather reads the kept ones again and writes them as uint32
         b2 = C.c_void_p()
         N.check(N.lib.tm_batch_create(v.handle, 4096, nd, C.byref(b2)))
