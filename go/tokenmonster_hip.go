@@ -266,6 +266,104 @@ func (hv *HipVocab) TokenizeBatchRawSpans(raw [][]byte) ([][]uint32, [][]uint32,
 	}
 }
 
+// Character offsets (include/tokenmonster_hip.h): what a pair counts, and which text it points into.
+const (
+	UnitBytes      uint32 = 0 // TM_UNIT_BYTES
+	UnitCodepoints uint32 = 1 // TM_UNIT_CODEPOINTS: the index into a []rune
+	UnitUTF16      uint32 = 2 // TM_UNIT_UTF16: the index into a []uint16 (utf16.Encode), a Java or JS string
+	TextNormalized uint32 = 0 // TM_TEXT_NORMALIZED
+	TextRaw        uint32 = 1 // TM_TEXT_RAW
+)
+
+// TokenizeBatchSpansIn is TokenizeBatchSpans (text TextNormalized: docs are normalized) or TokenizeBatchRawSpans (text TextRaw: docs are raw)
+// with the pairs counted in `unit` (tm_tokenize_batch_spans_in).
+func (hv *HipVocab) TokenizeBatchSpansIn(docs [][]byte, text, unit uint32) ([][]uint32, [][]uint32, []int, error) {
+	n := len(docs)
+	packed, offsets := pack(docs)
+	capTok := uint64(2*len(packed) + 2*n + 64)
+	tokOff := make([]uint64, n+1)
+	missing := make([]uint32, n+1)
+	for {
+		out := make([]uint32, capTok+1)
+		spans := make([]uint32, 2*capTok+2)
+		rc, err := locked(func() C.int {
+			return C.tm_tokenize_batch_spans_in(hv.h, (*C.uint8_t)(unsafe.Pointer(&packed[0])), (*C.uint64_t)(unsafe.Pointer(&offsets[0])),
+				C.uint32_t(n), C.uint32_t(text), C.uint32_t(unit), (*C.uint32_t)(unsafe.Pointer(&out[0])), C.uint64_t(capTok),
+				(*C.uint64_t)(unsafe.Pointer(&tokOff[0])), (*C.uint32_t)(unsafe.Pointer(&spans[0])), (*C.uint32_t)(unsafe.Pointer(&missing[0])))
+		})
+		if err != nil {
+			return nil, nil, nil, err
+		}
+		if rc == C.TM_E_NOSPACE {
+			capTok = tokOff[n]
+			continue
+		}
+		res := make([][]uint32, n)
+		sp := make([][]uint32, n)
+		miss := make([]int, n)
+		for i := range docs {
+			res[i] = out[tokOff[i]:tokOff[i+1]]
+			sp[i] = spans[2*tokOff[i] : 2*tokOff[i+1]]
+			miss[i] = int(missing[i])
+		}
+		return res, sp, miss, nil
+	}
+}
+
+// SpansIn is Spans (TextNormalized) / RawSpans (TextRaw) counted in `unit` (tm_batch_spans_in).  ms, when not nil, receives the milliseconds
+// of the four parts - normalized pairs, origin pass, map, unit work - and the call synchronizes.  Returns the documents mapped on the host.
+func (b *HipBatch) SpansIn(stream unsafe.Pointer, text, unit uint32, spans unsafe.Pointer, capIds uint64, ms *[4]float32) (uint32, error) {
+	var hostDocs C.uint32_t
+	var cms [4]C.float
+	var pms *C.float
+	if ms != nil {
+		pms = &cms[0]
+	}
+	_, err := locked(func() C.int {
+		return C.tm_batch_spans_in(b.h, stream, C.uint32_t(text), C.uint32_t(unit), (*C.uint32_t)(spans), C.uint64_t(capIds), &hostDocs, pms)
+	})
+	if ms != nil {
+		for k := range cms {
+			ms[k] = float32(cms[k])
+		}
+	}
+	return uint32(hostDocs), err
+}
+
+// CollateSpansIn is CollateSpans / CollateRawSpans counted in `unit` (tm_batch_collate_spans_in).
+func (b *HipBatch) CollateSpansIn(how HipCollate, stream unsafe.Pointer, text, unit uint32, spans unsafe.Pointer, spanBytes uint32) error {
+	h := how.c()
+	_, err := locked(func() C.int {
+		return C.tm_batch_collate_spans_in(b.h, &h, stream, C.uint32_t(text), C.uint32_t(unit), spans, C.uint32_t(spanBytes))
+	})
+	return err
+}
+
+// WindowsSpansIn is WindowsSpans / WindowsRawSpans counted in `unit` (tm_batch_windows_spans_in).
+func (b *HipBatch) WindowsSpansIn(how HipCollate, overlap uint32, stream unsafe.Pointer, rowsCap uint64, text, unit uint32, spans unsafe.Pointer, spanBytes uint32) (uint64, error) {
+	h := how.c()
+	rc, err := locked(func() C.int {
+		return C.tm_batch_windows_spans_in(b.h, &h, C.uint32_t(overlap), stream, C.uint64_t(rowsCap), C.uint32_t(text), C.uint32_t(unit), spans, C.uint32_t(spanBytes))
+	})
+	if err == nil && rc == C.TM_E_NOSPACE {
+		return b.WindowRows(how, overlap)
+	}
+	return 0, err
+}
+
+// HipUtf8Units is the unit rule on the host (tm_utf8_units): U(x), or D(x) with roundDown, of the byte offset x of doc in `unit`.
+func HipUtf8Units(doc []byte, unit uint32, x uint64, roundDown bool) uint64 {
+	var p *C.uint8_t
+	if len(doc) > 0 {
+		p = (*C.uint8_t)(unsafe.Pointer(&doc[0]))
+	}
+	rd := C.int(0)
+	if roundDown {
+		rd = 1
+	}
+	return uint64(C.tm_utf8_units(p, C.uint64_t(len(doc)), C.uint32_t(unit), C.uint64_t(x), rd))
+}
+
 // CountBatch is Count (go :971) over many RAW documents: server job 20.
 func (hv *HipVocab) CountBatch(docs [][]byte) ([]int, error) {
 	n := len(docs)

@@ -54,6 +54,11 @@ int tm_normalize(const uint8_t* data, size_t n, uint32_t capcode, uint32_t norm_
  * is the map tm_batch_raw_spans (tokenmonster_hip.h) applies, and the reference for the device's own.  Every flag set tm_normalize takes;
  * n < 2^32. */
 int tm_normalize_origins(const uint8_t* data, size_t n, uint32_t capcode, uint32_t norm_flag, uint8_t** out, size_t* out_n, uint32_t** own_out);
+/* The host statement of the unit rule of tokenmonster_hip.h (character offsets): for the document doc[0 .. len) and a byte offset x in
+ * 0..len, U(x) (round_down 0) or D(x) = U(char_start(x)) (round_down not 0) in `unit` - 0 bytes (x itself), 1 code points, 2 UTF-16 units.
+ * A byte pair (b, e) becomes (D(b), U(e)) if e > b and (D(b), D(b)) otherwise.  Plain host code, no device work; x > len counts as len; an
+ * unknown unit returns UINT64_MAX. */
+uint64_t tm_utf8_units(const uint8_t* doc, uint64_t len, uint32_t unit, uint64_t x, int round_down);
 /* The way back for ONE byte string (a token, a decoded fragment): capcode decoding as Vocab.Denormalize does it (go/tokenmonster.go:445-462;
  * tokenmonster-cpp/src/tokenmonster.cpp:3248-3253) - level 2 by the decoder of javascript/tokenmonster.js:1007-1065, level 1 drops the 0x7F
  * marker and the character behind it, level 0 copies.  Host code (token lists are small); documents go through tm_decode_batch.  Returns a

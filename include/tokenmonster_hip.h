@@ -403,6 +403,63 @@ int tm_batch_windows_spans(tm_batch* b, const tm_collate* how, uint32_t overlap,
 int tm_batch_windows_raw_spans(tm_batch* b, const tm_collate* how, uint32_t overlap, void* stream, uint64_t rows_cap,
                                void* spans_out, uint32_t span_bytes);
 
+/* ---- character offsets: the same pairs counted in code points or UTF-16 units ----------------------------------------------------------- */
+/* Two units are added beside bytes: */
+#define TM_UNIT_BYTES 0u
+#define TM_UNIT_CODEPOINTS 1u
+#define TM_UNIT_UTF16 2u
+/* A byte is a *continuation byte* if (b & 0xC0) == 0x80.
+ * For a document of `len` bytes and a byte offset x in 0..len:
+ *  - U(x) under TM_UNIT_CODEPOINTS is the number of non-continuation bytes in [0, x).
+ *  - U(x) under TM_UNIT_UTF16 is that number plus the number of bytes >= 0xF0 in [0, x).
+ *  - char_start(x) is x if x == len or byte x is not a continuation byte.
+ *  - Otherwise char_start(x) is the nearest of x-1, x-2, x-3 that lies inside the document and holds a non-continuation byte.
+ *  - If there is no such byte, char_start(x) is x.
+ *  - D(x) = U(char_start(x)).
+ * A byte pair (b, e) becomes:
+ *  - (D(b), U(e)) if e > b;
+ *  - (D(b), D(b)) if the span is empty.
+ * Consequences:
+ *  - On well-formed UTF-8 with both ends on character boundaries, this is the index into the decoded string: Python str for code points, a
+ *    UTF-16 string for TM_UNIT_UTF16.
+ *  - An end inside a character rounds outward.
+ *  - Malformed text follows the rule literally.  Every non-continuation byte is one unit.  This header makes no claim about any decoder.
+ *  - Pairs can end inside a character: TokenMonster tokens are byte strings, so normalized spans can; so can raw spans of a vocabulary with
+ *    capcode 0 and no normalization flags (the identity map of tm_batch_raw_spans, which does not round to characters).
+ *  - Begins never decrease.
+ *  - The end of an empty span inside a character may lie one unit before the end in front of it (the empty span rounds down, the end in
+ *    front of it rounded outward).
+ *  - Units never exceed bytes, so 32-bit offsets still hold.
+ *  - With TM_UNIT_BYTES every call below returns exactly what its existing counterpart returns.
+ * `text` says which text the offsets point into: */
+#define TM_TEXT_NORMALIZED 0u   /* offsets into the text the walk runs on (tm_batch_download_text) */
+#define TM_TEXT_RAW        1u   /* offsets into the documents as uploaded (tm_batch_upload_raw) */
+/* tm_batch_spans_in is tm_batch_spans (TM_TEXT_NORMALIZED) / tm_batch_raw_spans (TM_TEXT_RAW) in `unit`; tm_batch_collate_spans_in and
+ * tm_batch_windows_spans_in are tm_batch_collate_spans / tm_batch_collate_raw_spans and tm_batch_windows_spans / tm_batch_windows_raw_spans;
+ * tm_tokenize_batch_spans_in takes normalized input like tm_tokenize_batch_spans under TM_TEXT_NORMALIZED and raw input like
+ * tm_tokenize_batch_raw_spans under TM_TEXT_RAW.  Slot order, alignment, TM_E_NOSPACE (nothing written), host_docs, the stream rules (the
+ * stricter ones of the window calls included) and every error are those of the byte-span calls; BOS, EOS and padding columns stay (0, 0).
+ * An unknown `text` or `unit`, and TM_TEXT_RAW on a batch whose text did not come from tm_batch_upload_raw + tm_batch_normalize, are
+ * TM_E_INVALID before any device work.
+ * The units come from an index of the text, made on request only and kept until the batch's next upload, one per `text` kind: per 256 bytes
+ * of the text the number of non-continuation bytes (and, for TM_UNIT_UTF16 only, of bytes >= 0xF0) in front of them, counted in one streaming
+ * pass over the resident text - the raw text as uploaded, or the normalized text (packed first, on `stream`, where it still lies in the normalizer's
+ * buffers: a second tm_batch_run of the same upload wants that stream, or the pack completed) - and scanned.  It lives in a grow-only buffer of the batch of at most 1/8 of the text's bytes, counted in
+ * tm_batch_device_bytes; tm_batch_normalize and tm_batch_run do nothing for it.  The ragged byte pairs are then converted in place (a work-item
+ * per pair: the index entry plus a count over the part of a 256-byte block in front of the offset) and the collate and window fills run on
+ * the converted pairs.  With TM_UNIT_BYTES no index is made and nothing is converted.
+ * ms (may be NULL), when given, receives four parts and the call synchronizes as tm_batch_raw_spans_timed does: ms[0..2] are its parts
+ * (ms[1..2] are 0 for TM_TEXT_NORMALIZED), ms[3] is the unit work, index plus conversion. */
+int tm_batch_spans_in(tm_batch* b, void* stream, uint32_t text, uint32_t unit,
+                      uint32_t* spans_out, uint64_t spans_cap, uint32_t* host_docs, float* ms /* may be NULL */);
+int tm_batch_collate_spans_in(tm_batch* b, const tm_collate* how, void* stream, uint32_t text, uint32_t unit,
+                              void* spans_out, uint32_t span_bytes);
+int tm_batch_windows_spans_in(tm_batch* b, const tm_collate* how, uint32_t overlap, void* stream, uint64_t rows_cap,
+                              uint32_t text, uint32_t unit, void* spans_out, uint32_t span_bytes);
+int tm_tokenize_batch_spans_in(const tm_vocab* v, const uint8_t* docs, const uint64_t* offsets, uint32_t ndocs,
+                               uint32_t text, uint32_t unit, uint32_t* tokens_out, uint64_t tokens_cap,
+                               uint64_t* tok_offsets, uint32_t* spans_out, uint32_t* missing);
+
 /* Streaming Decoder (go/tokenmonster.go:552-700 NewDecoder / Decode / DecodeSerialized / Flush; server jobs 5-9): ids arrive a few
  * at a time, a call returns the text that is COMPLETE so far; the bytes of a character that is not (a token may end in the middle of a
  * UTF-8 sequence) and the state of the capcode decoder are carried to the next call.  Per-connection host state: the gather of a

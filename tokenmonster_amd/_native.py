@@ -14,6 +14,8 @@ TM_OK, TM_E_INVALID, TM_E_NODEVICE, TM_E_HIP, TM_E_NOSPACE, TM_E_LIMIT, TM_E_INP
 TM_NONE = 0xFFFFFF
 TM_NUM_KERNELS = 5
 KIND_ENGLISH, KIND_ENGLISHCODE, KIND_CODE = 0, 1, 2
+TM_UNIT_BYTES, TM_UNIT_CODEPOINTS, TM_UNIT_UTF16 = 0, 1, 2
+TM_TEXT_NORMALIZED, TM_TEXT_RAW = 0, 1
 
 u8p = C.POINTER(C.c_uint8)
 u32p = C.POINTER(C.c_uint32)
@@ -93,6 +95,10 @@ SIGNATURES = {
     "tm_batch_windows": (C.c_int, [vp, vp, C.c_uint32, vp, C.c_uint64, vp, vp, vp, vp, vp]),
     "tm_batch_windows_spans": (C.c_int, [vp, vp, C.c_uint32, vp, C.c_uint64, vp, C.c_uint32]),
     "tm_batch_windows_raw_spans": (C.c_int, [vp, vp, C.c_uint32, vp, C.c_uint64, vp, C.c_uint32]),
+    "tm_batch_spans_in": (C.c_int, [vp, vp, C.c_uint32, C.c_uint32, vp, C.c_uint64, u32p, f32p]),
+    "tm_batch_collate_spans_in": (C.c_int, [vp, vp, vp, C.c_uint32, C.c_uint32, vp, C.c_uint32]),
+    "tm_batch_windows_spans_in": (C.c_int, [vp, vp, C.c_uint32, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, C.c_uint32]),
+    "tm_tokenize_batch_spans_in": (C.c_int, [vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_uint64, vp, vp, vp]),
     "tm_decoder_new":(C.c_int, [vp, C.POINTER(vp)]),
     "tm_decoder_free": (None, [vp]),
     "tm_decoder_decode": (C.c_int, [vp, vp, C.c_uint64, vp, C.c_uint64, u64p]),
@@ -146,6 +152,7 @@ SIGNATURES = {
     "tm_tok_write": (C.c_int, [vp, vp, vp, C.c_uint32, vp, vp, vp, C.c_uint32, C.POINTER(vp), C.POINTER(C.c_size_t)]),
     "tm_normalize": (C.c_int, [vp, C.c_size_t, C.c_uint32, C.c_uint32, C.POINTER(vp), C.POINTER(C.c_size_t)]),
     "tm_normalize_origins": (C.c_int, [vp, C.c_size_t, C.c_uint32, C.c_uint32, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(vp)]),
+    "tm_utf8_units": (C.c_uint64, [vp, C.c_uint64, C.c_uint32, C.c_uint64, C.c_int]),
     "tm_denormalize": (C.c_int, [vp, C.c_size_t, C.c_uint32, C.POINTER(vp), C.POINTER(C.c_size_t)]),
     "tm_normalize_batch": (C.c_int, [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(vp), vp]),
 }

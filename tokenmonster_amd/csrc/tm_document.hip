@@ -328,6 +328,7 @@ int enqueue_pass(DocCall& c, uint64_t pass, uint64_t own, uint64_t have, uint32_
   b->d_ctl = nullptr;
   b->text_in_slabs = false;
   b->has_output = false;
+  units_forget(b, 3u);
   b->ndocs = 1;
   b->nbytes = have;
   b->nseg = (own + SEG - 1) / SEG;

@@ -92,6 +92,7 @@ int enc_pass(tm_encoder* e, bool last, uint64_t* total) {
   b->d_doc_vis = b->d_offsets + 2;
   b->d_doc_entry = e->d_entry();
   b->text_in_slabs = false;
+  units_forget(b, 3u);
   b->ndocs = 1;
   b->nbytes = e->have;
   b->nseg = (own + SEG - 1) / SEG;

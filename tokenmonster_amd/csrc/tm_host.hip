@@ -344,6 +344,7 @@ enum class SpanStep { none, normalized, raw };
 struct OneShot {
   bool raw;                 // the text is raw: the normalizer runs in front
   SpanStep spans;
+  uint32_t unit;            // TM_UNIT_*: what the pairs count (tm_units.hip)
   uint32_t enc;             // 0: ids_out takes u32 ids and `cap` counts ids; 2 .. 4: the serialized form, `cap` counts bytes and offsets_out takes byte offsets
   const char* who;
   void* ids_out; uint64_t cap; uint64_t* offsets_out; uint32_t* spans_out; uint32_t* missing;
@@ -371,6 +372,7 @@ static int one_shot(const tm_vocab* v, const uint8_t* text, const uint64_t* offs
       if (rc == TM_OK && o.spans == SpanStep::raw) rc = origin_ready(b, o.who);
       if (rc == TM_OK) rc = spans_reserve(b, total);
       if (rc == TM_OK) rc = o.spans == SpanStep::raw ? batch_raw_spans_on(b, l->stream, b->d_spans, total, nullptr) : batch_spans_on(b, l->stream, b->d_spans, total);
+      if (rc == TM_OK) rc = batch_units_on(b, l->stream, o.spans == SpanStep::raw ? TM_TEXT_RAW : TM_TEXT_NORMALIZED, o.unit, b->d_spans, total);
     }
     if (rc == TM_OK && fits && total) {
       if (!o.enc) rc = small_d2h(b, o.ids_out, b->d_out, total * 4, l->stream);
@@ -396,17 +398,25 @@ static int one_shot(const tm_vocab* v, const uint8_t* text, const uint64_t* offs
 
 int tm_tokenize_batch(const tm_vocab* v, const uint8_t* text, const uint64_t* offsets, uint32_t ndocs, uint32_t* tokens_out,
                       uint64_t tokens_cap, uint64_t* tok_offsets, uint32_t* missing) {
-  return one_shot(v, text, offsets, ndocs, OneShot{false, SpanStep::none, 0, "tm_tokenize_batch", tokens_out, tokens_cap, tok_offsets, nullptr, missing});
+  return one_shot(v, text, offsets, ndocs, OneShot{false, SpanStep::none, TM_UNIT_BYTES, 0, "tm_tokenize_batch", tokens_out, tokens_cap, tok_offsets, nullptr, missing});
 }
 
 int tm_tokenize_batch_spans(const tm_vocab* v, const uint8_t* text, const uint64_t* offsets, uint32_t ndocs, uint32_t* tokens_out,
                             uint64_t tokens_cap, uint64_t* tok_offsets, uint32_t* spans_out, uint32_t* missing) {
-  return one_shot(v, text, offsets, ndocs, OneShot{false, SpanStep::normalized, 0, "tm_tokenize_batch_spans", tokens_out, tokens_cap, tok_offsets, spans_out, missing});
+  return one_shot(v, text, offsets, ndocs, OneShot{false, SpanStep::normalized, TM_UNIT_BYTES, 0, "tm_tokenize_batch_spans", tokens_out, tokens_cap, tok_offsets, spans_out, missing});
 }
 
 int tm_tokenize_batch_raw_spans(const tm_vocab* v, const uint8_t* raw, const uint64_t* offsets, uint32_t ndocs, uint32_t* tokens_out,
                                 uint64_t tokens_cap, uint64_t* tok_offsets, uint32_t* spans_out, uint32_t* missing) {
-  return one_shot(v, raw, offsets, ndocs, OneShot{true, SpanStep::raw, 0, "tm_tokenize_batch_raw_spans", tokens_out, tokens_cap, tok_offsets, spans_out, missing});
+  return one_shot(v, raw, offsets, ndocs, OneShot{true, SpanStep::raw, TM_UNIT_BYTES, 0, "tm_tokenize_batch_raw_spans", tokens_out, tokens_cap, tok_offsets, spans_out, missing});
+}
+
+int tm_tokenize_batch_spans_in(const tm_vocab* v, const uint8_t* docs, const uint64_t* offsets, uint32_t ndocs, uint32_t text, uint32_t unit,
+                               uint32_t* tokens_out, uint64_t tokens_cap, uint64_t* tok_offsets, uint32_t* spans_out, uint32_t* missing) {
+  const int rc = units_args(text, unit, "tm_tokenize_batch_spans_in");
+  if (rc != TM_OK) return rc;
+  const bool raw = text == TM_TEXT_RAW;
+  return one_shot(v, docs, offsets, ndocs, OneShot{raw, raw ? SpanStep::raw : SpanStep::normalized, unit, 0, "tm_tokenize_batch_spans_in", tokens_out, tokens_cap, tok_offsets, spans_out, missing});
 }
 
 static int count_batch(const tm_vocab* v, const uint8_t* text, const uint64_t* offsets, uint32_t ndocs, bool raw, uint64_t* counts, uint32_t* missing) {
@@ -443,7 +453,7 @@ int tm_tokenize_batch_serialized(const tm_vocab* v, const uint8_t* text, const u
   if (encoding_length <= 1) encoding_length = v->host.n_ids <= 65536 ? 2 : 3;          // go :990-996
   if (encoding_length < 2 || encoding_length > 4) return set_error(TM_E_INVALID, "Invalid encoding length");   // go :1012
   if (encoding_length_used) *encoding_length_used = encoding_length;
-  return one_shot(v, text, offsets, ndocs, OneShot{false, SpanStep::none, encoding_length, "tm_tokenize_batch_serialized", bytes_out, bytes_cap, byte_offsets, nullptr, missing});
+  return one_shot(v, text, offsets, ndocs, OneShot{false, SpanStep::none, TM_UNIT_BYTES, encoding_length, "tm_tokenize_batch_serialized", bytes_out, bytes_cap, byte_offsets, nullptr, missing});
 }
 
 // ---- large batches, host to host -------------------------------------------------------------------------------------------------

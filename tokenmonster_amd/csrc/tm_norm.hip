@@ -1221,6 +1221,7 @@ int raw_prepare(tm_batch* b, uint64_t nbytes, uint32_t ndocs, uint64_t npieces, 
   b->raw_docs = ndocs;
   b->raw_pieces = npieces;
   b->has_output = false;
+  units_forget(b, 3u);
   return TM_OK;
 }
 
@@ -1366,6 +1367,7 @@ static int batch_normalize_impl(tm_batch* b, void* stream, bool one_piece) {
   b->d_doc_end = b->d_nend;
   b->ndocs = nd; b->nbytes = 0; b->nseg = 0; b->ngroups = 0; b->nlong = 0;
   b->text_in_slabs = false;
+  units_forget(b, 1u);
   b->slab_pieces = np;
   if (nd == 0) return TM_OK;
   static const bool trace = getenv("TM_TRACE") != nullptr;

@@ -1181,6 +1181,20 @@ int tm_normalize_origins(const uint8_t* data, size_t n, uint32_t capcode, uint32
   return TM_OK;
 }
 
+// the unit rule of tokenmonster_hip.h, stated on the host: what k_unit_spans (tm_units.hip) computes from the index
+uint64_t tm_utf8_units(const uint8_t* doc, uint64_t len, uint32_t unit, uint64_t x, int round_down) {
+  if (unit > 2u || (len && !doc)) return ~0ull;
+  if (x > len) x = len;
+  if (unit == 0u) return x;
+  auto cont = [&](uint64_t i) { return (doc[i] & 0xC0u) == 0x80u; };
+  if (round_down && x < len && cont(x)) {
+    for (uint64_t k = 1; k <= 3 && k <= x; k++) if (!cont(x - k)) { x -= k; break; }
+  }
+  uint64_t u = 0;
+  for (uint64_t i = 0; i < x; i++) u += (cont(i) ? 0u : 1u) + ((unit == 2u && doc[i] >= 0xF0u) ? 1u : 0u);
+  return u;
+}
+
 int tm_denormalize(const uint8_t* data, size_t n, uint32_t capcode, uint8_t** out, size_t* out_n) {
   if (!out || !out_n || (n && !data)) return tmh::set_error(TM_E_INVALID, "null argument");
   if (capcode > 2) return tmh::set_error(TM_E_INVALID, "capcode %u", capcode);

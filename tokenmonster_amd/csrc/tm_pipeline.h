@@ -251,6 +251,10 @@ struct tm_batch {
   uint64_t own_cap = 0;
   uint8_t* d_own_tmp = nullptr;         // ... and what k_norm_carry writes on the side when the origin pass runs it again
   uint64_t own_tmp_cap = 0;
+  uint8_t* d_units[2] = {nullptr, nullptr};   // tm_batch_spans_in: the unit index of the normalized [0] / the raw [1] text, grow-only (tm_units.hip: two planes of UnitPlane)
+  uint64_t units_cap[2] = {0, 0};       // ... in 256-byte blocks of text
+  uint64_t units_blocks[2] = {0, 0};    // ... and the blocks of the text the planes were made for
+  uint32_t units_have[2] = {0, 0};      // which planes hold the current text: bit 0 non-continuation bytes, bit 1 bytes >= 0xF0; 0 again wherever new text arrives (units_forget)
   uint8_t* d_win = nullptr;             // tm_batch_windows: win_off[cap + 1] (u64) | the scan's block sums and total (u64) | windows per document (u32), grow-only (tm_windows.hip)
   uint32_t win_cap = 0;                 // ... in documents
   uint32_t* d_win_rows = nullptr;       // ... and the document of every row of the last window call, grow-only
@@ -343,6 +347,17 @@ int batch_spans_on(tm_batch* b, hipStream_t st, void* out, uint64_t total);
 int origin_ready(const tm_batch* b, const char* who);
 int origin_pass_on(tm_batch* b, hipStream_t st, uint32_t* host_docs);
 int batch_raw_spans_on(tm_batch* b, hipStream_t st, void* out, uint64_t total, uint32_t* host_docs, float* ms = nullptr);      // tm_spans.hip: spans_reserve, batch_spans_on, origin_pass_on, k_raw_spans
+// tm_units.hip: the pairs counted in code points or UTF-16 units (tokenmonster_hip.h, character offsets).  units_args: `text` and `unit` are known
+// (TM_E_INVALID otherwise; the callers ask origin_ready for TM_TEXT_RAW themselves).  batch_units_on: the ragged BYTE pairs in `pairs` (device or
+// page-locked, as batch_spans_on / batch_raw_spans_on left them for this `text`) converted in place on `st` - the unit index of the text first where the
+// batch does not hold it yet; nothing at all for TM_UNIT_BYTES.  batch_spans_in_on: the byte pairs of `text` and their conversion, ms[4] (may be
+// null) as tm_batch_spans_in states.  units_forget: new text has arrived (kinds: bit 0 the normalized text, bit 1 the raw text).
+int units_args(uint32_t text, uint32_t unit, const char* who);
+int batch_units_on(tm_batch* b, hipStream_t st, uint32_t text, uint32_t unit, void* pairs, uint64_t total);
+int batch_spans_in_on(tm_batch* b, hipStream_t st, uint32_t text, uint32_t unit, void* out, uint64_t total, uint32_t* host_docs, float* ms);
+inline void units_forget(tm_batch* b, uint32_t kinds) { if (kinds & 1u) b->units_have[0] = 0; if (kinds & 2u) b->units_have[1] = 0; }
+// tm_spans.hip / tm_windows.hip: the bodies of the collate and window span calls (text: TM_TEXT_*, unit: TM_UNIT_*; `who` names the entry point)
+int collate_spans_impl(tm_batch* b, const tm_collate* how, void* stream, uint32_t text, uint32_t unit, void* spans_out, uint32_t span_bytes, const char* who);
 // small device <-> host transfers that bypass the copy engines (tm_kernels.hip).  small_d2h's destination is filled by small_sync
 // (which synchronizes the stream); small_h2d's source may be reused as soon as the call returns (pageable memory, or at most MAIL_MAX bytes).
 constexpr uint64_t MAIL_BYTES = 4ull << 20, MAIL_MAX = 1ull << 20;

@@ -90,6 +90,7 @@ static int score_prepare(const tm_vocab* v, tm_dataset* d, const uint64_t* strip
     if (rc != TM_OK) return rc; }
   b->d_doc_begin = b->d_offsets;
   b->text_in_slabs = false;
+  units_forget(b, 3u);
   b->d_doc_end = b->d_offsets + n_strips;
   b->d_doc_vis = d->d_vis;
   b->d_doc_entry = nullptr;

@@ -345,6 +345,32 @@ static void launch_collate_spans(const CollateArgs& a, const uint32_t* spans, vo
   TM_LAUNCH(kern, grid_of(flat_items(f, sizeof(T))), 256, 0, st, a, f, spans, static_cast<T*>(out));
 }
 
+// the one body of tm_batch_collate_spans, tm_batch_collate_raw_spans and tm_batch_collate_spans_in: the ragged pairs of `text` into the batch's own
+// buffer, counted in `unit` (tm_units.hip), then the fill
+int collate_spans_impl(tm_batch* b, const tm_collate* how, void* stream, uint32_t text, uint32_t unit, void* spans_out, uint32_t span_bytes, const char* who) {
+  int rc = check_how(b, how, spans_out, who);
+  if (rc != TM_OK) return rc;
+  const bool raw = text == TM_TEXT_RAW;
+  if (span_bytes != 4 && span_bytes != 8) return set_error(TM_E_INVALID, "%s: span_bytes %u (4 or 8)", who, span_bytes);
+  const uint32_t ns = (how->bos_id != TM_NONE ? 1u : 0u) + (how->eos_id != TM_NONE ? 1u : 0u);
+  if (how->row_len < ns) return set_error(TM_E_INVALID, "%s: row_len %u holds no %u specials", who, how->row_len, ns);
+  if ((uint64_t)how->ndocs * how->row_len > COLLATE_MAX_ELEMS) return set_error(TM_E_LIMIT, "%s: %u rows of %u ids in one call (split the documents)", who, how->ndocs, how->row_len);
+  if ((rc = spans_ready(b, who)) != TM_OK || (raw && (rc = origin_ready(b, who)) != TM_OK)) return rc;
+  if ((rc = enter_device(b->vocab)) != TM_OK || (rc = ensure_output(b)) != TM_OK) return rc;      // (waits for the run: the rows are all there)
+  if (how->ndocs == 0) return TM_OK;
+  const uint64_t total = b->last_totals[1];
+  if ((rc = spans_check_lengths(b, who)) != TM_OK || (rc = spans_reserve(b, total)) != TM_OK) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  // the ragged pairs first, into the batch's own buffer (the raw ones where the normalized ones lay)
+  if ((rc = raw ? batch_raw_spans_on(b, st, b->d_spans, total, nullptr, nullptr) : batch_spans_on(b, st, b->d_spans, total)) != TM_OK) return rc;
+  if ((rc = batch_units_on(b, st, text, unit, b->d_spans, total)) != TM_OK) return rc;
+  (void)hipGetLastError();
+  const CollateArgs a{nullptr, b->d_tok_offsets + how->first_doc, how->ndocs, how->row_len, how->pad_id, how->bos_id, how->eos_id, how->flags};
+  if (span_bytes == 4) launch_collate_spans<uint32_t>(a, reinterpret_cast<const uint32_t*>(b->d_spans), spans_out, st);
+  else launch_collate_spans<uint64_t>(a, reinterpret_cast<const uint32_t*>(b->d_spans), spans_out, st);
+  return launch_check();
+}
+
 }  // namespace tmh
 
 using namespace tmh;
@@ -365,24 +391,7 @@ int tm_batch_spans(tm_batch* b, void* stream, uint32_t* spans_out, uint64_t span
 }
 
 int tm_batch_collate_spans(tm_batch* b, const tm_collate* how, void* stream, void* spans_out, uint32_t span_bytes) {
-  int rc = check_how(b, how, spans_out, "tm_batch_collate_spans");
-  if (rc != TM_OK) return rc;
-  if (span_bytes != 4 && span_bytes != 8) return set_error(TM_E_INVALID, "tm_batch_collate_spans: span_bytes %u (4 or 8)", span_bytes);
-  const uint32_t ns = (how->bos_id != TM_NONE ? 1u : 0u) + (how->eos_id != TM_NONE ? 1u : 0u);
-  if (how->row_len < ns) return set_error(TM_E_INVALID, "tm_batch_collate_spans: row_len %u holds no %u specials", how->row_len, ns);
-  if ((uint64_t)how->ndocs * how->row_len > COLLATE_MAX_ELEMS) return set_error(TM_E_LIMIT, "tm_batch_collate_spans: %u rows of %u ids in one call (split the documents)", how->ndocs, how->row_len);
-  if ((rc = spans_ready(b, "tm_batch_collate_spans")) != TM_OK) return rc;
-  if ((rc = enter_device(b->vocab)) != TM_OK || (rc = ensure_output(b)) != TM_OK) return rc;
-  if (how->ndocs == 0) return TM_OK;
-  const uint64_t total = b->last_totals[1];
-  if ((rc = spans_check_lengths(b, "tm_batch_collate_spans")) != TM_OK || (rc = spans_reserve(b, total)) != TM_OK) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  if ((rc = batch_spans_on(b, st, b->d_spans, total)) != TM_OK) return rc;      // the ragged pairs first, into the batch's own buffer
-  (void)hipGetLastError();
-  const CollateArgs a{nullptr, b->d_tok_offsets + how->first_doc, how->ndocs, how->row_len, how->pad_id, how->bos_id, how->eos_id, how->flags};
-  if (span_bytes == 4) launch_collate_spans<uint32_t>(a, reinterpret_cast<const uint32_t*>(b->d_spans), spans_out, st);
-  else launch_collate_spans<uint64_t>(a, reinterpret_cast<const uint32_t*>(b->d_spans), spans_out, st);
-  return launch_check();
+  return collate_spans_impl(b, how, stream, TM_TEXT_NORMALIZED, TM_UNIT_BYTES, spans_out, span_bytes, "tm_batch_collate_spans");
 }
 
 int tm_batch_raw_spans(tm_batch* b, void* stream, uint32_t* spans_out, uint64_t spans_cap, uint32_t* host_docs) {
@@ -404,24 +413,7 @@ int tm_batch_raw_spans_timed(tm_batch* b, void* stream, uint32_t* spans_out, uin
 }
 
 int tm_batch_collate_raw_spans(tm_batch* b, const tm_collate* how, void* stream, void* spans_out, uint32_t span_bytes) {
-  int rc = check_how(b, how, spans_out, "tm_batch_collate_raw_spans");
-  if (rc != TM_OK) return rc;
-  if (span_bytes != 4 && span_bytes != 8) return set_error(TM_E_INVALID, "tm_batch_collate_raw_spans: span_bytes %u (4 or 8)", span_bytes);
-  const uint32_t ns = (how->bos_id != TM_NONE ? 1u : 0u) + (how->eos_id != TM_NONE ? 1u : 0u);
-  if (how->row_len < ns) return set_error(TM_E_INVALID, "tm_batch_collate_raw_spans: row_len %u holds no %u specials", how->row_len, ns);
-  if ((uint64_t)how->ndocs * how->row_len > COLLATE_MAX_ELEMS) return set_error(TM_E_LIMIT, "tm_batch_collate_raw_spans: %u rows of %u ids in one call (split the documents)", how->ndocs, how->row_len);
-  if ((rc = spans_ready(b, "tm_batch_collate_raw_spans")) != TM_OK || (rc = origin_ready(b, "tm_batch_collate_raw_spans")) != TM_OK) return rc;
-  if ((rc = enter_device(b->vocab)) != TM_OK || (rc = ensure_output(b)) != TM_OK) return rc;
-  if (how->ndocs == 0) return TM_OK;
-  const uint64_t total = b->last_totals[1];
-  if ((rc = spans_check_lengths(b, "tm_batch_collate_raw_spans")) != TM_OK || (rc = spans_reserve(b, total)) != TM_OK) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  if ((rc = batch_raw_spans_on(b, st, b->d_spans, total, nullptr, nullptr)) != TM_OK) return rc;      // the ragged raw pairs, where the normalized ones lay
-  (void)hipGetLastError();
-  const CollateArgs a{nullptr, b->d_tok_offsets + how->first_doc, how->ndocs, how->row_len, how->pad_id, how->bos_id, how->eos_id, how->flags};
-  if (span_bytes == 4) launch_collate_spans<uint32_t>(a, reinterpret_cast<const uint32_t*>(b->d_spans), spans_out, st);
-  else launch_collate_spans<uint64_t>(a, reinterpret_cast<const uint32_t*>(b->d_spans), spans_out, st);
-  return launch_check();
+  return collate_spans_impl(b, how, stream, TM_TEXT_RAW, TM_UNIT_BYTES, spans_out, span_bytes, "tm_batch_collate_raw_spans");
 }
 
 }  // extern "C"

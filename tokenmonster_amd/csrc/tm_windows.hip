@@ -206,7 +206,7 @@ static void launch_window_spans(const WindowArgs& a, const uint32_t* spans, void
 }
 
 static int windows_spans(tm_batch* b, const tm_collate* how, uint32_t overlap, void* stream, uint64_t rows_cap, void* spans_out, uint32_t span_bytes, bool raw,
-                         const char* who) {
+                         uint32_t unit, const char* who) {
   WindowArgs a{};
   int rc = window_plan(b, how, overlap, spans_out, who, raw ? 2 : 1, span_bytes, &a);
   if (rc != TM_OK) return rc;
@@ -217,6 +217,7 @@ static int windows_spans(tm_batch* b, const tm_collate* how, uint32_t overlap, v
   hipStream_t st = (hipStream_t)stream;
   // the ragged pairs first, into the batch's own buffer (the raw ones where the normalized ones lay)
   if ((rc = raw ? batch_raw_spans_on(b, st, b->d_spans, total, nullptr, nullptr) : batch_spans_on(b, st, b->d_spans, total)) != TM_OK) return rc;
+  if ((rc = batch_units_on(b, st, raw ? TM_TEXT_RAW : TM_TEXT_NORMALIZED, unit, b->d_spans, total)) != TM_OK) return rc;      // (tm_units.hip; nothing for TM_UNIT_BYTES)
   if ((rc = window_row_docs(b, &a, st)) != TM_OK) return rc;
   (void)hipGetLastError();
   a.ids = nullptr;
@@ -262,11 +263,18 @@ int tm_batch_windows(tm_batch* b, const tm_collate* how, uint32_t overlap, void*
 }
 
 int tm_batch_windows_spans(tm_batch* b, const tm_collate* how, uint32_t overlap, void* stream, uint64_t rows_cap, void* spans_out, uint32_t span_bytes) {
-  return windows_spans(b, how, overlap, stream, rows_cap, spans_out, span_bytes, false, "tm_batch_windows_spans");
+  return windows_spans(b, how, overlap, stream, rows_cap, spans_out, span_bytes, false, TM_UNIT_BYTES, "tm_batch_windows_spans");
 }
 
 int tm_batch_windows_raw_spans(tm_batch* b, const tm_collate* how, uint32_t overlap, void* stream, uint64_t rows_cap, void* spans_out, uint32_t span_bytes) {
-  return windows_spans(b, how, overlap, stream, rows_cap, spans_out, span_bytes, true, "tm_batch_windows_raw_spans");
+  return windows_spans(b, how, overlap, stream, rows_cap, spans_out, span_bytes, true, TM_UNIT_BYTES, "tm_batch_windows_raw_spans");
+}
+
+int tm_batch_windows_spans_in(tm_batch* b, const tm_collate* how, uint32_t overlap, void* stream, uint64_t rows_cap, uint32_t text, uint32_t unit,
+                              void* spans_out, uint32_t span_bytes) {
+  const int rc = units_args(text, unit, "tm_batch_windows_spans_in");
+  if (rc != TM_OK) return rc;
+  return windows_spans(b, how, overlap, stream, rows_cap, spans_out, span_bytes, text == TM_TEXT_RAW, unit, "tm_batch_windows_spans_in");
 }
 
 }  // extern "C"

@@ -17,7 +17,7 @@ import weakref
 import numpy as np
 
 from . import _native as N
-from .vocab import pack_documents
+from .vocab import pack_documents, span_unit
 
 PAD_LEFT, KEEP_TAIL = 1, 2
 
@@ -145,14 +145,18 @@ def _check_dtype(torch, dtype):
     return sizes[dtype]
 
 
-def encode_batch(vocab, docs, max_length, *, pad_id, bos_id=None, eos_id=None, pad_left=False, keep_tail=False, dtype=None, raw=True, device=None, return_offsets=False):
+def encode_batch(vocab, docs, max_length, *, pad_id, bos_id=None, eos_id=None, pad_left=False, keep_tail=False, dtype=None, raw=True, device=None, return_offsets=False,
+                 offset_unit="bytes"):
     """documents (bytes or str; raw=False: already normalized bytes) -> {"input_ids" [rows, max_length] of `dtype` (default int64),
     "attention_mask" [rows, max_length] bool, "lengths" [rows] int32}, CUDA tensors on the vocabulary's device.  Row r is
     [bos] ids [eos] pad...: the ids cut to max_length less the specials given (their head; keep_tail: their tail), the padding on the
     right (pad_left: on the left).  return_offsets=True adds "offset_mapping" [rows, max_length, 2] int64: (begin, end) of the bytes the id
     of a column came from, counted from the document's start in the normalized text the tokenizer walks (raw=True: what Vocab.normalize
     makes of the document), and (0, 0) on BOS, EOS and padding (tm_batch_collate_spans).  return_offsets="raw" (with raw=True only): the same
-    pairs counted in the bytes of the document as it was passed in (tm_batch_collate_raw_spans)."""
+    pairs counted in the bytes of the document as it was passed in (tm_batch_collate_raw_spans).  offset_unit "bytes" | "chars" | "utf16"
+    (any return_offsets): what the pairs count - bytes, code points or UTF-16 units, by the rule of include/tokenmonster_hip.h
+    (tm_batch_collate_spans_in).  With str documents, return_offsets="raw" and offset_unit="chars", doc[b:e] is the text of the id."""
+    unit = span_unit(offset_unit)
     if isinstance(return_offsets, str):
         if return_offsets != "raw":
             raise ValueError("return_offsets %r: False, True or \"raw\"" % (return_offsets,))
@@ -176,20 +180,24 @@ def encode_batch(vocab, docs, max_length, *, pad_id, bos_id=None, eos_id=None, p
         res = {"input_ids": ids, "attention_mask": mask.view(torch.bool), "lengths": lengths}
         if return_offsets:
             spans = torch.empty((nd, max_length, 2), dtype=torch.int64, device=dev)
-            fn = N.lib.tm_batch_collate_raw_spans if return_offsets == "raw" else N.lib.tm_batch_collate_spans
-            N.check(fn(b, C.byref(how), st, spans.data_ptr(), 8))
+            text = N.TM_TEXT_RAW if return_offsets == "raw" else N.TM_TEXT_NORMALIZED
+            N.check(N.lib.tm_batch_collate_spans_in(b, C.byref(how), st, text, unit, spans.data_ptr(), 8))
             res["offset_mapping"] = spans
     return res
 
 
-def encode_windows(vocab, docs, max_length, overlap, *, pad_id, bos_id=None, eos_id=None, pad_left=False, dtype=None, raw=True, device=None, return_offsets=False):
+def encode_windows(vocab, docs, max_length, overlap, *, pad_id, bos_id=None, eos_id=None, pad_left=False, dtype=None, raw=True, device=None, return_offsets=False,
+                   offset_unit="bytes"):
     """documents -> overlapping rows, every id kept: a document with more ids than a row holds takes several rows, consecutive rows of a
     document share `overlap` ids (the stride / return_overflowing_tokens of other tokenizers; tm_batch_windows).  {"input_ids" [rows,
     max_length] of `dtype` (default int64), "attention_mask" [rows, max_length] bool, "lengths" [rows] int32, "overflow_to_sample_mapping"
     [rows] int32 - the document of a row -, "window_start" [rows] int32 - the index inside the document of the row's first id}.  Row k of a
     document is [bos] ids[k * step : k * step + room] [eos] pad..., room = max_length less the specials given, step = room - overlap; the
     ids are those of the one walk over the whole document.  return_offsets as for encode_batch: "offset_mapping" [rows, max_length, 2]
-    int64 counts from the DOCUMENT's start in every row (tm_batch_windows_spans / tm_batch_windows_raw_spans)."""
+    int64 counts from the DOCUMENT's start in every row (tm_batch_windows_spans / tm_batch_windows_raw_spans); offset_unit "bytes" |
+    "chars" | "utf16" as for encode_batch (tm_batch_windows_spans_in): with str documents, return_offsets="raw" and offset_unit="chars",
+    doc[b:e] is the text of the id."""
+    unit = span_unit(offset_unit)
     if isinstance(return_offsets, str):
         if return_offsets != "raw":
             raise ValueError("return_offsets %r: False, True or \"raw\"" % (return_offsets,))
@@ -220,9 +228,9 @@ def encode_windows(vocab, docs, max_length, overlap, *, pad_id, bos_id=None, eos
         res = {"input_ids": ids, "attention_mask": mask.view(torch.bool), "lengths": lengths, "overflow_to_sample_mapping": row_doc, "window_start": row_start}
         if return_offsets:
             spans = torch.empty((rows, max_length, 2), dtype=torch.int64, device=dev)
-            fn = N.lib.tm_batch_windows_raw_spans if return_offsets == "raw" else N.lib.tm_batch_windows_spans
+            text = N.TM_TEXT_RAW if return_offsets == "raw" else N.TM_TEXT_NORMALIZED
             if rows:
-                N.check(fn(b, C.byref(how), overlap, st, rows, spans.data_ptr(), 8))
+                N.check(N.lib.tm_batch_windows_spans_in(b, C.byref(how), overlap, st, rows, text, unit, spans.data_ptr(), 8))
             res["offset_mapping"] = spans
     return res
 

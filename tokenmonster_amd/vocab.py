@@ -22,6 +22,16 @@ def pack_documents(docs):
     return text, offsets
 
 
+SPAN_UNITS = {"bytes": N.TM_UNIT_BYTES, "chars": N.TM_UNIT_CODEPOINTS, "utf16": N.TM_UNIT_UTF16}
+
+
+def span_unit(name):
+    """"bytes" | "chars" | "utf16" -> TM_UNIT_* (ValueError for anything else, before any device call)"""
+    if name not in SPAN_UNITS:
+        raise ValueError('offset unit %r: "bytes", "chars" or "utf16"' % (name,))
+    return SPAN_UNITS[name]
+
+
 class VocabBlock(C.Structure):
     """tm_vocab_block (include/tokenmonster_hip.h): what a process needs besides the bytes of a vocabulary's device block"""
     _fields_ = [("bytes", C.c_uint64), ("part_bytes", C.c_uint64 * 8)] + [(n, C.c_uint32) for n in (
@@ -185,9 +195,11 @@ class Vocab:
             N.check(rc)
             return out[: int(tok_off[nd])], tok_off, missing[:nd]
 
-    def tokenize_spans_packed(self, text, offsets):
+    def tokenize_spans_packed(self, text, offsets, unit="bytes"):
         """normalized packed documents -> (ids u32[T], tok_offsets u64[D+1], spans u32[T, 2], missing u32[D]): spans[k] = (begin, end) of the
-        bytes id k came from, counted from its document's start (tm_tokenize_batch_spans)"""
+        bytes id k came from, counted from its document's start (tm_tokenize_batch_spans_in, TM_TEXT_NORMALIZED).  unit: "bytes", or "chars"
+        (code points) / "utf16" (UTF-16 units) by the rule of include/tokenmonster_hip.h"""
+        unit = span_unit(unit)
         text = N.as_u8(text)
         offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
         nd = offsets.size - 1
@@ -197,7 +209,8 @@ class Vocab:
         while True:
             out = np.empty(cap, dtype=np.uint32)
             spans = np.empty((cap, 2), dtype=np.uint32)
-            rc = N.lib.tm_tokenize_batch_spans(self._h, N.ptr(text), N.ptr(offsets), nd, N.ptr(out), cap, N.ptr(tok_off), N.ptr(spans), N.ptr(missing))
+            rc = N.lib.tm_tokenize_batch_spans_in(self._h, N.ptr(text), N.ptr(offsets), nd, N.TM_TEXT_NORMALIZED, unit, N.ptr(out), cap, N.ptr(tok_off), N.ptr(spans),
+                                                  N.ptr(missing))
             if rc == N.TM_E_NOSPACE:
                 cap = int(tok_off[nd])
                 continue
@@ -205,10 +218,12 @@ class Vocab:
             n = int(tok_off[nd])
             return out[:n], tok_off, spans[:n], missing[:nd]
 
-    def tokenize_raw_spans_packed(self, raw_text, raw_offsets):
+    def tokenize_raw_spans_packed(self, raw_text, raw_offsets, unit="bytes"):
         """RAW packed documents -> (ids u32[T], tok_offsets u64[D+1], spans u32[T, 2], number of documents mapped on the host): spans[k] =
         (begin, end) of the bytes id k came from, counted from its document's start in the raw text (tm_batch_upload_raw,
-        tm_batch_normalize, tm_batch_run, tm_batch_raw_spans)"""
+        tm_batch_normalize, tm_batch_run, tm_batch_spans_in with TM_TEXT_RAW - the batch calls, which report the host's documents).  unit:
+        "bytes", or "chars" (code points: the index into the decoded str) / "utf16" (UTF-16 units) by the rule of include/tokenmonster_hip.h"""
+        unit = span_unit(unit)
         raw_text = N.as_u8(raw_text)
         raw_offsets = np.ascontiguousarray(raw_offsets, dtype=np.uint64)
         nd = raw_offsets.size - 1
@@ -226,7 +241,7 @@ class Vocab:
             N.check(N.lib.tm_batch_download(b, N.ptr(ids), n, N.ptr(tok_off), None))
             spans = PinnedBuffer(8 * max(n, 1))
             host_docs = C.c_uint32()
-            N.check(N.lib.tm_batch_raw_spans(b, None, spans.array.ctypes.data, n, C.byref(host_docs)))
+            N.check(N.lib.tm_batch_spans_in(b, None, N.TM_TEXT_RAW, unit, spans.array.ctypes.data, n, C.byref(host_docs), None))
             N.check(N.lib.tm_batch_totals(b, None, None))                     # (waits for the NULL stream)
             return ids[:n], tok_off, spans.array[:8 * n].view(np.uint32).reshape(n, 2).copy(), int(host_docs.value)
         finally:
