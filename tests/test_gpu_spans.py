@@ -15,47 +15,20 @@ import traceback
 import numpy as np
 import pytest
 
+from fixed_shape import Collate, Out, FILL, KEEP_TAIL, PAD_LEFT
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 pytestmark = pytest.mark.gpu
 
-PAD_LEFT, KEEP_TAIL = 1, 2
 HOOKS = {"plain": 0, "dense_side": 64, "direct": 1024, "deep_tree": 4096, "id_staging": 32768}      # test hooks 6, 10, 12, 15 (include/tokenmonster_hip.h)
 DOC_LENS = [0, 1, 2, 255, 256, 257, 511, 512, 513, 4095, 4096, 4097]
 SEG_BATCHES = [15, 16, 17, 33]
-FILL = 0xA5
 
 
 def _mods():
     import tokenmonster_amd as tm
     from tokenmonster_amd import _native as N, synth
     return tm, N, synth
-
-
-class Collate(C.Structure):
-    _fields_ = [(n, C.c_uint32) for n in ("first_doc", "ndocs", "row_len", "id_bytes", "pad_id", "bos_id", "eos_id", "flags")]
-
-
-class Out:
-    """n elements of `elem` bytes in page-locked memory, `shift` elements behind a 16-byte boundary, every byte around them a sentinel"""
-
-    def __init__(self, n, elem, shift=0):
-        from tokenmonster_amd.vocab import PinnedBuffer
-        self.n, self.elem = n, elem
-        self.buf = PinnedBuffer(n * elem + 64)
-        a = self.buf.array
-        a[:] = FILL
-        self.off = (-a.ctypes.data) % 16 + 16 + shift * elem
-        self.ptr = a.ctypes.data + self.off
-
-    def view(self, dtype):
-        return self.buf.array[self.off:self.off + self.n * self.elem].view(dtype)
-
-    def sentinels_intact(self):
-        a = self.buf.array
-        return bool((a[:self.off] == FILL).all() and (a[self.off + self.n * self.elem:] == FILL).all())
-
-    def untouched(self):
-        return bool((self.buf.array == FILL).all())
 
 
 @contextlib.contextmanager

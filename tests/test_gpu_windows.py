@@ -10,26 +10,14 @@ import pytest
 import tokenmonster_amd as tm
 from tokenmonster_amd import _native as N
 from tokenmonster_amd import synth
-from tokenmonster_amd.vocab import PinnedBuffer
+from fixed_shape import Collate, Out, spec, DT, FILL, KEEP_TAIL, NONE, PAD_LEFT
 
-NONE = N.TM_NONE
-PAD_LEFT, KEEP_TAIL = 1, 2
 ROW_LENS = [1, 2, 3, 7, 64, 65, 257]
 SPAN_LENS = [1, 3, 7, 65]
 FORMS = [("norm", 4), ("raw", 8), ("norm", 8), ("raw", 4)]
 SPECIALS = [(False, False), (True, False), (False, True), (True, True)]
-DT = {2: np.uint16, 4: np.uint32, 8: np.uint64}
-FILL = 0xA5
 EMPTY_RUN = 16          # (sixteen rows in a row hold a whole 16-byte vector of two-byte ids wherever the run begins)
 pytestmark = pytest.mark.gpu
-
-
-class Collate(C.Structure):
-    _fields_ = [(n, C.c_uint32) for n in ("first_doc", "ndocs", "row_len", "id_bytes", "pad_id", "bos_id", "eos_id", "flags")]
-
-
-def spec(x):
-    return NONE if x is None else x
 
 
 def shapes(L):
@@ -82,28 +70,6 @@ def np_windows(docs, L, pad, bos, eos, overlap, pad_left, spans=None):
 
 
 # ---- one vocabulary, one run for the whole file -----------------------------------------------------------------------------------------
-class Out:
-    """n elements of `elem` bytes in page-locked memory, `shift` elements behind a 16-byte boundary, every byte around them a sentinel"""
-
-    def __init__(self, n, elem, shift=0):
-        self.n, self.elem = n, elem
-        self.buf = PinnedBuffer(n * elem + 64)
-        a = self.buf.array
-        a[:] = FILL
-        self.off = (-a.ctypes.data) % 16 + 16 + shift * elem
-        self.ptr = a.ctypes.data + self.off
-
-    def view(self, dtype):
-        return self.buf.array[self.off:self.off + self.n * self.elem].view(dtype)
-
-    def sentinels_intact(self):
-        a = self.buf.array
-        return bool((a[:self.off] == FILL).all() and (a[self.off + self.n * self.elem:] == FILL).all())
-
-    def untouched(self):
-        return bool((self.buf.array == FILL).all())
-
-
 LETTERS = b"abcdefghijklmnopqrst"
 
 

@@ -1,5 +1,7 @@
-// tm_collate.h - what the fixed-shape outputs share (tm_collate.hip: ids, masks, streams; tm_spans.hip: the byte spans of the ids): an output as
-// one flat run of elements with 16-byte stores between an unaligned head and tail, and the plan of a row of tm_batch_collate.
+// tm_collate.h - what the fixed-shape outputs share (tm_collate.hip: ids, masks, streams; tm_windows.hip: overlapping windows; tm_spans.hip: the
+// spans of the ids in either layout): an output as one flat run of elements with 16-byte stores between an unaligned head and tail, the plan of a
+// row of tm_batch_collate and of tm_batch_windows, the ONE fill body each for ids / mask and for pairs that both layouts' kernels call with their
+// plan, and the searches from an id or a stream position to its document.
 #pragma once
 #include <algorithm>
 
@@ -63,6 +65,80 @@ __device__ __forceinline__ RowPlan row_plan(const CollateArgs& a, uint64_t r) {
   p.len = m + ns;
   p.lo = (a.flags & TM_COLLATE_PAD_LEFT) ? a.L - p.len : 0u;
   return p;
+}
+
+// ---- the fill of rows: what k_collate_rows / k_window_rows and k_collate_spans / k_window_spans do with work-item t ------------------------------
+// Args: CollateArgs or WindowArgs (L, pad, bos, eos, ids); plan(r): the RowPlan of row r - row_plan, or win_plan's.  The row of the work-item's
+// first element is a division; when its vector crosses a row end the next row's plan is asked for.
+// MASK: the element is 1 inside the row's entries and 0 on padding (T = uint8_t); else the id.
+template <typename T, bool MASK, typename Args, typename Plan>
+__device__ __forceinline__ void fill_rows(const Args& a, const Flat& f, T* __restrict__ out, uint64_t t, Plan plan) {
+  constexpr uint32_t PER = 16 / sizeof(T);
+  uint64_t e0;
+  uint32_t cnt;
+  if (!flat_span<T>(f, t, e0, cnt)) return;
+  uint64_t r;
+  uint32_t c;
+  if (f.n <= 0xFFFFFFFFull) { r = (uint32_t)e0 / a.L; c = (uint32_t)e0 - (uint32_t)r * a.L; }      // (a 64-bit division costs more than the store it is for)
+  else { r = e0 / a.L; c = (uint32_t)(e0 - r * a.L); }
+  RowPlan p = plan(r);                                 // (r is a row: e0 is an element of the output)
+  const uint32_t hb = a.bos != TM_NONE ? 1u : 0u;
+  T vals[PER];
+#pragma unroll
+  for (uint32_t k = 0; k < PER; k++) {
+    if (k < cnt) {
+      const uint32_t j = c - p.lo;                     // (wraps to a large number left of the entries)
+      uint32_t v;
+      if (MASK) v = j < p.len ? 1u : 0u;
+      else if (j >= p.len) v = a.pad;
+      else if (hb && j == 0) v = a.bos;
+      else if (a.eos != TM_NONE && j == p.len - 1) v = a.eos;
+      else v = a.ids[p.src + (j - hb)];
+      vals[k] = (T)v;
+      if (++c == a.L && k + 1 < cnt) { c = 0; r++; p = plan(r); }      // (another element follows: r is a row)
+    } else {
+      vals[k] = 0;
+    }
+  }
+  flat_store<T>(out, e0, cnt, vals);
+}
+// The pairs of the ids laid out like the rows: the output [rows, L, 2] is one flat run of 2 * rows * L elements of T, element e is component
+// e & 1 of column (e >> 1) % L of row (e >> 1) / L.  A column that holds a content id gets that id's pair; BOS, EOS and padding get (0, 0).
+template <typename T, typename Args, typename Plan>
+__device__ __forceinline__ void fill_spans(const Args& a, const Flat& f, const uint32_t* __restrict__ spans, T* __restrict__ out, uint64_t t, Plan plan) {
+  constexpr uint32_t PER = 16 / sizeof(T);
+  uint64_t e0;
+  uint32_t cnt;
+  if (!flat_span<T>(f, t, e0, cnt)) return;
+  const uint64_t L2 = 2ull * a.L;
+  uint64_t r;
+  uint64_t c;                                         // element of the row: 2 * column + component
+  if (f.n <= 0xFFFFFFFFull && L2 <= 0xFFFFFFFFull) { r = (uint32_t)e0 / (uint32_t)L2; c = (uint32_t)e0 - (uint32_t)r * (uint32_t)L2; }
+  else { r = e0 / L2; c = e0 - r * L2; }
+  RowPlan p = plan(r);
+  const uint32_t hb = a.bos != TM_NONE ? 1u : 0u;
+  T vals[PER];
+#pragma unroll
+  for (uint32_t k = 0; k < PER; k++) {
+    if (k < cnt) {
+      const uint32_t j = (uint32_t)(c >> 1) - p.lo;      // (wraps to a large number left of the entries)
+      uint32_t v = 0;
+      if (j < p.len && !(hb && j == 0) && !(a.eos != TM_NONE && j == p.len - 1)) v = spans[2 * (p.src + (j - hb)) + (c & 1u)];
+      vals[k] = (T)v;
+      if (++c == L2 && k + 1 < cnt) { c = 0; r++; p = plan(r); }
+    } else {
+      vals[k] = 0;
+    }
+  }
+  flat_store<T>(out, e0, cnt, vals);
+}
+
+// ---- an id of a run -> its document ----------------------------------------------------------------------------------------------------------------
+// the last document whose first id is not behind id t, over tok_offsets[0 .. ndocs) (documents without ids share their offset with the next)
+__device__ __forceinline__ uint32_t doc_of_id(const uint64_t* __restrict__ tok_offsets, uint32_t ndocs, uint64_t t) {
+  uint32_t lo = 0, hi = ndocs;
+  while (hi - lo > 1u) { const uint32_t mid = lo + (hi - lo) / 2u; if (tok_offsets[mid] <= t) lo = mid; else hi = mid; }
+  return lo;
 }
 
 // ---- a position of a stream of documents -> its document ---------------------------------------------------------------------------------------------

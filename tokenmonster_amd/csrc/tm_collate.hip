@@ -18,40 +18,13 @@
 namespace tmh {
 
 // ---- k_collate_rows: one document per row (the flat output and the plan of a row: tm_collate.h) ------------------------------------------------
-// MASK: the element is 1 inside the row's entries and 0 on padding (T = uint8_t); else the id.  lengths (ids launch only, may be null):
-// the first `rows` work-items write a row's length each.
+// The fill is fill_rows (tm_collate.h) with the plan of one document per row.  lengths (ids launch only, may be null): the first `rows`
+// work-items write a row's length each.
 template <typename T, bool MASK>
 __global__ __launch_bounds__(256) void k_collate_rows(CollateArgs a, Flat f, T* __restrict__ out, uint32_t* __restrict__ lengths) {
-  constexpr uint32_t PER = 16 / sizeof(T);
   const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (!MASK && lengths && t < a.rows) lengths[t] = row_plan(a, t).len;
-  uint64_t e0;
-  uint32_t cnt;
-  if (!flat_span<T>(f, t, e0, cnt)) return;
-  uint64_t r;
-  uint32_t c;
-  if (f.n <= 0xFFFFFFFFull) { r = (uint32_t)e0 / a.L; c = (uint32_t)e0 - (uint32_t)r * a.L; }      // (a 64-bit division costs more than the store it is for)
-  else { r = e0 / a.L; c = (uint32_t)(e0 - r * a.L); }
-  RowPlan p = row_plan(a, r);
-  const uint32_t hb = a.bos != TM_NONE ? 1u : 0u;
-  T vals[PER];
-#pragma unroll
-  for (uint32_t k = 0; k < PER; k++) {
-    if (k < cnt) {
-      const uint32_t j = c - p.lo;                     // (wraps to a large number left of the entries)
-      uint32_t v;
-      if (MASK) v = j < p.len ? 1u : 0u;
-      else if (j >= p.len) v = a.pad;
-      else if (hb && j == 0) v = a.bos;
-      else if (a.eos != TM_NONE && j == p.len - 1) v = a.eos;
-      else v = a.ids[p.src + (j - hb)];
-      vals[k] = (T)v;
-      if (++c == a.L && k + 1 < cnt) { c = 0; r++; p = row_plan(a, r); }
-    } else {
-      vals[k] = 0;
-    }
-  }
-  flat_store<T>(out, e0, cnt, vals);
+  fill_rows<T, MASK>(a, f, out, t, [&](uint64_t r) { return row_plan(a, r); });
 }
 
 // ---- k_pack_stream: ids(doc0) [eos] ids(doc1) [eos] ... cut into rows -------------------------------------------------------------------------------------
@@ -289,14 +262,8 @@ int tm_batch_load_ids(tm_batch* b, const void* rows, uint32_t nrows, uint32_t ro
   if (bound + 4 > b->out_cap) {          // (the gather stores whole 16 bytes)
     // what the last run left may still be read on its stream
     if ((e = hipStreamSynchronize(b->last_stream)) != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
-    trace_grow("ids", (bound + 4) * 4);
-    (void)hipFree(b->d_out);
-    b->device_bytes -= b->out_cap * 4;
-    b->d_out = nullptr;
-    b->out_cap = 0;
-    const uint64_t cap = bound + bound / 4 + 1024;
-    if ((e = batch_alloc_bytes(b, (void**)&b->d_out, cap * 4)) != hipSuccess) return hip_fail(e, "hipMalloc output");
-    b->out_cap = cap;
+    const int rc = grow_batch(b, (void**)&b->d_out, &b->out_cap, bound + 4, bound + bound / 4 + 1024, 4, "ids");
+    if (rc != TM_OK) return rc;
   }
   (void)hipGetLastError();
   b->has_output = false;

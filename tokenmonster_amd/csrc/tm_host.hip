@@ -370,9 +370,7 @@ static int one_shot(const tm_vocab* v, const uint8_t* text, const uint64_t* offs
       // the pairs behind the run on the lane's stream, into the workspace's own grow-only buffer (lane_run has waited for the run: ensure_output)
       if (rc == TM_OK) rc = spans_ready(b, o.who);
       if (rc == TM_OK && o.spans == SpanStep::raw) rc = origin_ready(b, o.who);
-      if (rc == TM_OK) rc = spans_reserve(b, total);
-      if (rc == TM_OK) rc = o.spans == SpanStep::raw ? batch_raw_spans_on(b, l->stream, b->d_spans, total, nullptr) : batch_spans_on(b, l->stream, b->d_spans, total);
-      if (rc == TM_OK) rc = batch_units_on(b, l->stream, o.spans == SpanStep::raw ? TM_TEXT_RAW : TM_TEXT_NORMALIZED, o.unit, b->d_spans, total);
+      if (rc == TM_OK) rc = batch_own_spans_on(b, l->stream, o.spans == SpanStep::raw ? TM_TEXT_RAW : TM_TEXT_NORMALIZED, o.unit, total);
     }
     if (rc == TM_OK && fits && total) {
       if (!o.enc) rc = small_d2h(b, o.ids_out, b->d_out, total * 4, l->stream);

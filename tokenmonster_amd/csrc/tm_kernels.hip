@@ -2174,7 +2174,7 @@ uint32_t long_segs() { return (debug_flags() & 4096) ? 8u : LONG_SEGS; }
 
 static const char* kKernelNames[TM_NUM_KERNELS] = {"segments", "match_branch", "resolve", "scan", "emit"};
 
-hipError_t batch_alloc_bytes(tm_batch* b, void** p, uint64_t bytes) {
+static hipError_t batch_alloc_bytes(tm_batch* b, void** p, uint64_t bytes) {
   hipError_t e = hipMalloc(p, bytes ? bytes : 16);
   if (e == hipSuccess) b->device_bytes += bytes;
   return e;
@@ -2546,6 +2546,23 @@ int grow_device(uint8_t** buf, uint64_t* cap, uint64_t need, uint64_t alloc, con
   *cap = alloc;
   return TM_OK;
 }
+int batch_replace(tm_batch* b, void** p, uint64_t old_bytes, uint64_t need_bytes, uint64_t alloc_bytes, const char* what) {
+  if (*p) trace_grow(what, need_bytes);
+  (void)hipFree(*p);                                   // (waits for the device: no kernel is still reading or writing the old buffer)
+  b->device_bytes -= old_bytes;
+  *p = nullptr;
+  const hipError_t e = batch_alloc_bytes(b, p, alloc_bytes);
+  if (e != hipSuccess) { *p = nullptr; return hip_fail(e, what); }
+  return TM_OK;
+}
+int grow_batch(tm_batch* b, void** p, uint64_t* cap, uint64_t need, uint64_t alloc, uint32_t elem_bytes, const char* what) {
+  if (*cap >= need) return TM_OK;
+  const uint64_t old_bytes = *cap * elem_bytes;
+  *cap = 0;
+  const int rc = batch_replace(b, p, old_bytes, need * elem_bytes, alloc * elem_bytes, what);
+  if (rc == TM_OK) *cap = alloc;
+  return rc;
+}
 int grow_pinned(uint8_t** buf, uint64_t* cap, uint64_t need, uint64_t alloc, const char* what) {
   if (*cap >= need) return TM_OK;
   if (*cap) trace_grow(what, need);
@@ -2588,12 +2605,8 @@ int ensure_output(tm_batch* b) {
   if (err != 0) return error_from_flag(err);
   uint64_t total = b->ndocs ? totals[1] : 0;
   if (total > b->out_cap) {
-    trace_grow("ids", total * 4);
-    (void)hipFree(b->d_out);
-    b->device_bytes -= b->out_cap * 4;
-    b->d_out = nullptr;
-    b->out_cap = total + total / 4 + 1024;
-    if ((e = dalloc(b, &b->d_out, b->out_cap)) != hipSuccess) return hip_fail(e, "hipMalloc output");
+    const int rc = grow_batch(b, (void**)&b->d_out, &b->out_cap, total, total + total / 4 + 1024, 4, "ids");
+    if (rc != TM_OK) return rc;
     hipStream_t st = b->last_stream;
     launch_emit(b, st, true, true);
     if ((e = hipStreamSynchronize(st)) != hipSuccess) return hip_fail(e, "emit rerun");

@@ -1581,26 +1581,12 @@ int origin_pass_on(tm_batch* b, hipStream_t st, uint32_t* host_docs) {
   const uint32_t nd = b->ndocs;
   if (nd == 0 || b->nbytes == 0) return TM_OK;
   const uint32_t capcode = b->vocab->host.capcode, norm_flag = b->vocab->host.norm_flag;
-  hipError_t e;
-  if (b->nbytes > b->own_cap) {
-    if (b->own_cap) trace_grow("origins", b->nbytes * 4);
-    (void)hipFree(b->d_own);
-    b->device_bytes -= b->own_cap * 4;
-    b->d_own = nullptr; b->own_cap = 0;
-    const uint64_t cap = b->nbytes + b->nbytes / 4 + 1024;
-    if ((e = batch_alloc_bytes(b, (void**)&b->d_own, cap * 4)) != hipSuccess) return hip_fail(e, "hipMalloc origins");
-    b->own_cap = cap;
-  }
+  int rc = grow_batch(b, (void**)&b->d_own, &b->own_cap, b->nbytes, b->nbytes + b->nbytes / 4 + 1024, 4, "origins");
+  if (rc != TM_OK) return rc;
   // scratch of the carry kernel: need_host[nd] | ninfo[8] | fb_ids[nd]
   const uint64_t o_info = ((uint64_t)nd + 7) & ~7ull, o_ids = o_info + 64, tmp_bytes = o_ids + (uint64_t)nd * 4;
-  if (tmp_bytes > b->own_tmp_cap) {
-    (void)hipFree(b->d_own_tmp);
-    b->device_bytes -= b->own_tmp_cap;
-    b->d_own_tmp = nullptr; b->own_tmp_cap = 0;
-    const uint64_t cap = tmp_bytes + tmp_bytes / 4 + 256;
-    if ((e = batch_alloc_bytes(b, (void**)&b->d_own_tmp, cap)) != hipSuccess) return hip_fail(e, "hipMalloc origins");
-    b->own_tmp_cap = cap;
-  }
+  if ((rc = grow_batch(b, (void**)&b->d_own_tmp, &b->own_tmp_cap, tmp_bytes, tmp_bytes + tmp_bytes / 4 + 256, 1, "origins scratch")) != TM_OK) return rc;
+  hipError_t e;
   (void)hipGetLastError();
   const bool on_device = (norm_flag & ~3u) == 0u && (capcode == 0 || capcode == 2);
   const uint64_t np = b->slab_pieces;

@@ -306,7 +306,6 @@ struct tm_dataset {
 namespace tmh {
 
 // tm_kernels.hip
-hipError_t batch_alloc_bytes(tm_batch* b, void** p, uint64_t bytes);
 int make_workspace(const tm_vocab* v, uint64_t max_bytes, uint32_t max_docs, bool own_text, bool with_output, tm_batch** out);
 void scan_u32(const uint32_t* in, uint64_t n, uint64_t* block_sums, uint64_t* total, uint64_t* out, hipStream_t st);
 void launch_doc_units(const uint64_t* doc_begin, const uint64_t* doc_end, uint32_t ndocs, uint32_t unit, uint32_t* doc_nunits, hipStream_t st);
@@ -336,27 +335,45 @@ void pack_text(tm_batch* b, hipStream_t st);     // tm_norm.hip: the normalizer'
 void launch_chain_hist(tm_batch* b, uint32_t delete_id, int n_cu, uint32_t* d_hist, unsigned long long* d_tokens, uint32_t* d_missing_bits,
                        uint32_t n_ids, hipStream_t st);
 int ensure_output(tm_batch* b);
-// tm_spans.hip: the byte span of every id of the last run.  spans_reserve: the batch's own buffer (d_spans) for n pairs; batch_spans_on: the pass
-// itself on `st` into `out` (device or page-locked, 8-byte aligned, room for `total` pairs) - the caller has waited for the run (ensure_output)
+// HIP events on `st` around the parts of a call that reports times: n events, or none at all (n = 0: the caller wants no times, nothing
+// here touches the device).  mark(k) records event k; finish waits for the last one, writes the n - 1 times between neighbouring marks to
+// `ms` and returns rc - or, where the work succeeded and an event did not, that failure.
+struct EventBracket {
+  hipStream_t st;
+  int n;
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  hipError_t e = hipSuccess;
+  EventBracket(hipStream_t stream, int count) : st(stream), n(count) { for (int k = 0; k < n && e == hipSuccess; k++) e = hipEventCreate(&ev[k]); }
+  void mark(int k) { if (n && e == hipSuccess) e = hipEventRecord(ev[k], st); }
+  int finish(float* ms, int rc) {
+    if (n && e == hipSuccess) e = hipEventSynchronize(ev[n - 1]);
+    for (int k = 0; k + 1 < n && e == hipSuccess; k++) e = hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]);
+    for (int k = 0; k < n; k++) if (ev[k]) (void)hipEventDestroy(ev[k]);
+    return rc == TM_OK && e != hipSuccess ? hip_fail(e, "HIP events") : rc;
+  }
+};
+// tm_spans.hip: the byte span of every id of the last run.  batch_spans_on: the pass itself on `st` into `out` (device or page-locked, 8-byte
+// aligned, room for `total` pairs) - the caller has waited for the run (ensure_output)
 int spans_ready(const tm_batch* b, const char* who);
-int spans_reserve(tm_batch* b, uint64_t n);
 int batch_spans_on(tm_batch* b, hipStream_t st, void* out, uint64_t total);
 // tm_norm.hip: origin_ready - the batch's text came from tm_batch_upload_raw + tm_batch_normalize and every raw document is shorter than 2^32
 // bytes; origin_pass_on - the owner of every normalized byte into b->d_own (indexed like the documents' ranges d_doc_begin), *host_docs = the
 // documents mapped on the host.  Reads what the normalizer and the run left, changes none of it.
 int origin_ready(const tm_batch* b, const char* who);
 int origin_pass_on(tm_batch* b, hipStream_t st, uint32_t* host_docs);
-int batch_raw_spans_on(tm_batch* b, hipStream_t st, void* out, uint64_t total, uint32_t* host_docs, float* ms = nullptr);      // tm_spans.hip: spans_reserve, batch_spans_on, origin_pass_on, k_raw_spans
+int batch_raw_spans_on(tm_batch* b, hipStream_t st, void* out, uint64_t total, uint32_t* host_docs, float* ms);      // tm_spans.hip: batch_spans_on into d_spans, origin_pass_on, k_raw_spans; ms[3] (may be null) as tm_batch_raw_spans_timed states
 // tm_units.hip: the pairs counted in code points or UTF-16 units (tokenmonster_hip.h, character offsets).  units_args: `text` and `unit` are known
-// (TM_E_INVALID otherwise; the callers ask origin_ready for TM_TEXT_RAW themselves).  batch_units_on: the ragged BYTE pairs in `pairs` (device or
-// page-locked, as batch_spans_on / batch_raw_spans_on left them for this `text`) converted in place on `st` - the unit index of the text first where the
-// batch does not hold it yet; nothing at all for TM_UNIT_BYTES.  batch_spans_in_on: the byte pairs of `text` and their conversion, ms[4] (may be
-// null) as tm_batch_spans_in states.  units_forget: new text has arrived (kinds: bit 0 the normalized text, bit 1 the raw text).
+// (TM_E_INVALID otherwise; the callers ask origin_ready for TM_TEXT_RAW themselves).  batch_spans_in_on: the byte pairs of `text` into `out` and
+// their conversion in place (nothing for TM_UNIT_BYTES), ms[4] (may be null) as tm_batch_spans_in states.  units_forget: new text has arrived
+// (kinds: bit 0 the normalized text, bit 1 the raw text).
 int units_args(uint32_t text, uint32_t unit, const char* who);
-int batch_units_on(tm_batch* b, hipStream_t st, uint32_t text, uint32_t unit, void* pairs, uint64_t total);
 int batch_spans_in_on(tm_batch* b, hipStream_t st, uint32_t text, uint32_t unit, void* out, uint64_t total, uint32_t* host_docs, float* ms);
 inline void units_forget(tm_batch* b, uint32_t kinds) { if (kinds & 1u) b->units_have[0] = 0; if (kinds & 2u) b->units_have[1] = 0; }
-// tm_spans.hip / tm_windows.hip: the bodies of the collate and window span calls (text: TM_TEXT_*, unit: TM_UNIT_*; `who` names the entry point)
+// tm_spans.hip: the bodies the span calls share (text: TM_TEXT_*, unit: TM_UNIT_*; `who` names the entry point).  batch_own_spans_on: the pairs
+// of `text` in `unit` into the batch's own buffer d_spans, grown for `total` pairs; ragged_spans_impl: tm_batch_spans, tm_batch_raw_spans(_timed)
+// and tm_batch_spans_in; collate_spans_impl: tm_batch_collate_spans, tm_batch_collate_raw_spans and tm_batch_collate_spans_in
+int batch_own_spans_on(tm_batch* b, hipStream_t st, uint32_t text, uint32_t unit, uint64_t total);
+int ragged_spans_impl(tm_batch* b, void* stream, uint32_t text, uint32_t unit, uint32_t* spans_out, uint64_t spans_cap, uint32_t* host_docs, float* ms, const char* who);
 int collate_spans_impl(tm_batch* b, const tm_collate* how, void* stream, uint32_t text, uint32_t unit, void* spans_out, uint32_t span_bytes, const char* who);
 // small device <-> host transfers that bypass the copy engines (tm_kernels.hip).  small_d2h's destination is filled by small_sync
 // (which synchronizes the stream); small_h2d's source may be reused as soon as the call returns (pageable memory, or at most MAIL_MAX bytes).
@@ -370,6 +387,11 @@ int small_sync(tm_batch* b, hipStream_t st);
 bool is_pinned(const void* p);      // page-locked host memory (hipHostMalloc / hipHostRegister)
 int grow_device(uint8_t** buf, uint64_t* cap, uint64_t need, uint64_t alloc, const char* what);
 int grow_pinned(uint8_t** buf, uint64_t* cap, uint64_t need, uint64_t alloc, const char* what);
+// ... and the same contract for the grow-only buffers a batch owns, which count in tm_batch::device_bytes (ids, spans, origins and their scratch,
+// window rows): `cap`, `need` and `alloc` in elements of elem_bytes.  batch_replace is the step behind it for a buffer whose size is no multiple of
+// its capacity (windows, the unit index): *p of old_bytes, too small for need_bytes, replaced by one of alloc_bytes; the caller keeps the capacity.
+int grow_batch(tm_batch* b, void** p, uint64_t* cap, uint64_t need, uint64_t alloc, uint32_t elem_bytes, const char* what);
+int batch_replace(tm_batch* b, void** p, uint64_t old_bytes, uint64_t need_bytes, uint64_t alloc_bytes, const char* what);
 // ... and a workspace of `v` for `bytes` of text in `docs` documents: a smaller one (or another vocabulary's) is replaced by one of alloc_bytes and docs + 25 %
 int grow_workspace(tm_batch** ws, const tm_vocab* v, uint64_t bytes, uint32_t docs, uint64_t alloc_bytes, const char* what);
 int batch_upload_on(tm_batch* b, const uint8_t* text, const uint64_t* offsets, uint32_t ndocs, hipStream_t st);

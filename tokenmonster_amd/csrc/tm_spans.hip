@@ -6,6 +6,11 @@
 // rows, the side lists / the dense T(p,1) array, the per-segment records of k_seg_params - walks every chain again and writes, for the
 // output slot K4 wrote an id to, the position the walk stood on and that position plus the advance.  It reads only the advance / flag byte of
 // a position, never an id, adds to no counter and writes nothing but its output.
+//
+// The collated form is tm_collate.h's fill body for pairs (fill_spans) with the plan of one document per row; tm_windows.hip runs the same body
+// with the plan of a window.  The host side holds the bodies the span calls share: ragged_spans_impl (the ragged calls, tm_units.hip's
+// included), batch_own_spans_on (the pairs into the batch's own buffer: the collate and window span calls, the one-shot calls of tm_host.hip)
+// and collate_spans_impl.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -193,37 +198,11 @@ __global__ __launch_bounds__(64) void k_span_list(const uint32_t* __restrict__ R
   }
 }
 
-// ---- k_collate_spans: the pairs laid out like tm_batch_collate's rows ------------------------------------------------------------------------------
-// The output [rows, L, 2] is one flat run of 2 * rows * L elements of T (tm_collate.h): element e is component e & 1 of column (e >> 1) % L of
-// row (e >> 1) / L.  A column that holds a content id gets that id's pair; BOS, EOS and padding get (0, 0).
+// ---- k_collate_spans: the pairs laid out like tm_batch_collate's rows (fill_spans, tm_collate.h, with the plan of one document per row) -------------
 template <typename T>
 __global__ __launch_bounds__(256) void k_collate_spans(CollateArgs a, Flat f, const uint32_t* __restrict__ spans, T* __restrict__ out) {
-  constexpr uint32_t PER = 16 / sizeof(T);
   const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  uint64_t e0;
-  uint32_t cnt;
-  if (!flat_span<T>(f, t, e0, cnt)) return;
-  const uint64_t L2 = 2ull * a.L;
-  uint64_t r;
-  uint64_t c;                                         // element of the row: 2 * column + component
-  if (f.n <= 0xFFFFFFFFull && L2 <= 0xFFFFFFFFull) { r = (uint32_t)e0 / (uint32_t)L2; c = (uint32_t)e0 - (uint32_t)r * (uint32_t)L2; }
-  else { r = e0 / L2; c = e0 - r * L2; }
-  RowPlan p = row_plan(a, r);
-  const uint32_t hb = a.bos != TM_NONE ? 1u : 0u;
-  T vals[PER];
-#pragma unroll
-  for (uint32_t k = 0; k < PER; k++) {
-    if (k < cnt) {
-      const uint32_t j = (uint32_t)(c >> 1) - p.lo;      // (wraps to a large number left of the entries)
-      uint32_t v = 0;
-      if (j < p.len && !(hb && j == 0) && !(a.eos != TM_NONE && j == p.len - 1)) v = spans[2 * (p.src + (j - hb)) + (c & 1u)];
-      vals[k] = (T)v;
-      if (++c == L2 && k + 1 < cnt) { c = 0; r++; p = row_plan(a, r); }
-    } else {
-      vals[k] = 0;
-    }
-  }
-  flat_store<T>(out, e0, cnt, vals);
+  fill_spans<T>(a, f, spans, out, t, [&](uint64_t r) { return row_plan(a, r); });
 }
 
 // ---- k_raw_spans: the pairs mapped back through the normalizer ----------------------------------------------------------------------------------------
@@ -237,9 +216,7 @@ __global__ __launch_bounds__(256) void k_raw_spans(const span_t* in, const uint6
                                                    const uint32_t* __restrict__ own, uint64_t total, span_t* out) {
   const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= total) return;
-  uint32_t lo = 0, hi = ndocs;                        // the last document whose first id is not behind t (documents without ids share their offset with the next)
-  while (hi - lo > 1u) { const uint32_t mid = lo + (hi - lo) / 2u; if (tok_offsets[mid] <= t) lo = mid; else hi = mid; }
-  const uint32_t d = lo;
+  const uint32_t d = doc_of_id(tok_offsets, ndocs, t);
   const span_t s = in[t];
   const uint64_t nlen = nend[d] - nbegin[d];
   const uint32_t rawlen = (uint32_t)(raw_off[d + 1] - raw_off[d]);
@@ -262,19 +239,8 @@ int spans_ready(const tm_batch* b, const char* who) {
   return TM_OK;
 }
 
-int spans_reserve(tm_batch* b, uint64_t n) {
-  if (n <= b->spans_cap) return TM_OK;
-  hipError_t e;
-  if (b->spans_cap) trace_grow("spans", n * 8);
-  (void)hipFree(b->d_spans);                         // (waits for the device: no pass is still writing the old buffer)
-  b->device_bytes -= b->spans_cap * 8;
-  b->d_spans = nullptr;
-  b->spans_cap = 0;
-  const uint64_t cap = n + n / 4 + 1024;
-  if ((e = batch_alloc_bytes(b, (void**)&b->d_spans, cap * 8)) != hipSuccess) return hip_fail(e, "hipMalloc spans");
-  b->spans_cap = cap;
-  return TM_OK;
-}
+// the batch's own buffer (d_spans) for n pairs
+static int spans_reserve(tm_batch* b, uint64_t n) { return grow_batch(b, (void**)&b->d_spans, &b->spans_cap, n, n + n / 4 + 1024, 8, "spans"); }
 
 // offsets are 32 bits: no document of the run may be 2^32 bytes or longer.  Only a run of 2^24 segments or more can hold one; then the
 // documents' ranges are fetched and looked at (the stream of the run has been waited for).
@@ -309,33 +275,31 @@ int batch_raw_spans_on(tm_batch* b, hipStream_t st, void* out, uint64_t total, u
   if (host_docs) *host_docs = 0;
   if (ms) ms[0] = ms[1] = ms[2] = 0.f;
   if (total == 0 || b->nseg == 0) return TM_OK;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  hipError_t e = hipSuccess;
-  if (ms) for (int k = 0; k < 4 && e == hipSuccess; k++) e = hipEventCreate(&ev[k]);
-  auto mark = [&](int k) { if (ms && e == hipSuccess) e = hipEventRecord(ev[k], st); };
+  EventBracket ev(st, ms ? 4 : 0);
   int rc = TM_OK;
-  mark(0);
+  ev.mark(0);
   // capcode 0 without normalization flags: the normalizer is the identity and so is the map, byte for byte (no rounding to characters)
   const bool identity = b->vocab->host.capcode == 0 && b->vocab->host.norm_flag == 0;
   if (identity) rc = batch_spans_on(b, st, out, total);
   else if ((rc = spans_reserve(b, total)) == TM_OK) rc = batch_spans_on(b, st, b->d_spans, total);
-  mark(1);
+  ev.mark(1);
   if (rc == TM_OK && !identity) rc = origin_pass_on(b, st, host_docs);
-  mark(2);
+  ev.mark(2);
   if (rc == TM_OK && !identity) {
     (void)hipGetLastError();
     TM_LAUNCH(k_raw_spans, grid_of(total), 256, 0, st, reinterpret_cast<const span_t*>(b->d_spans), b->d_tok_offsets, b->ndocs, b->d_doc_begin, b->d_doc_end,
               b->d_raw_off, b->d_own, total, static_cast<span_t*>(out));
     rc = launch_check();
   }
-  mark(3);
-  if (ms) {
-    if (e == hipSuccess) e = hipEventSynchronize(ev[3]);
-    for (int k = 0; k < 3 && e == hipSuccess; k++) e = hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]);
-    for (int k = 0; k < 4; k++) if (ev[k]) (void)hipEventDestroy(ev[k]);
-    if (rc == TM_OK && e != hipSuccess) rc = hip_fail(e, "HIP events");
-  }
-  return rc;
+  ev.mark(3);
+  return ev.finish(ms, rc);
+}
+
+// the ragged pairs of `text` into the batch's own buffer (the raw ones where the normalized ones lay), counted in `unit` (tm_units.hip): what the
+// collate and window fills and the one-shot span calls read
+int batch_own_spans_on(tm_batch* b, hipStream_t st, uint32_t text, uint32_t unit, uint64_t total) {
+  const int rc = spans_reserve(b, total);
+  return rc != TM_OK ? rc : batch_spans_in_on(b, st, text, unit, b->d_spans, total, nullptr, nullptr);
 }
 
 template <typename T>
@@ -359,16 +323,29 @@ int collate_spans_impl(tm_batch* b, const tm_collate* how, void* stream, uint32_
   if ((rc = enter_device(b->vocab)) != TM_OK || (rc = ensure_output(b)) != TM_OK) return rc;      // (waits for the run: the rows are all there)
   if (how->ndocs == 0) return TM_OK;
   const uint64_t total = b->last_totals[1];
-  if ((rc = spans_check_lengths(b, who)) != TM_OK || (rc = spans_reserve(b, total)) != TM_OK) return rc;
   hipStream_t st = (hipStream_t)stream;
-  // the ragged pairs first, into the batch's own buffer (the raw ones where the normalized ones lay)
-  if ((rc = raw ? batch_raw_spans_on(b, st, b->d_spans, total, nullptr, nullptr) : batch_spans_on(b, st, b->d_spans, total)) != TM_OK) return rc;
-  if ((rc = batch_units_on(b, st, text, unit, b->d_spans, total)) != TM_OK) return rc;
+  if ((rc = spans_check_lengths(b, who)) != TM_OK || (rc = batch_own_spans_on(b, st, text, unit, total)) != TM_OK) return rc;
   (void)hipGetLastError();
   const CollateArgs a{nullptr, b->d_tok_offsets + how->first_doc, how->ndocs, how->row_len, how->pad_id, how->bos_id, how->eos_id, how->flags};
   if (span_bytes == 4) launch_collate_spans<uint32_t>(a, reinterpret_cast<const uint32_t*>(b->d_spans), spans_out, st);
   else launch_collate_spans<uint64_t>(a, reinterpret_cast<const uint32_t*>(b->d_spans), spans_out, st);
   return launch_check();
+}
+
+// the one body of tm_batch_spans, tm_batch_raw_spans(_timed) and tm_batch_spans_in: the arguments, then the pairs of `text` in `unit` straight
+// into the caller's array.  ms: the four parts of tm_batch_spans_in (may be null)
+int ragged_spans_impl(tm_batch* b, void* stream, uint32_t text, uint32_t unit, uint32_t* spans_out, uint64_t spans_cap, uint32_t* host_docs, float* ms, const char* who) {
+  if (!b) return set_error(TM_E_INVALID, "%s: null argument", who);
+  if (host_docs) *host_docs = 0;
+  int rc = units_args(text, unit, who);               // (only tm_batch_spans_in can fail here: the others pass constants)
+  if (rc != TM_OK || (rc = spans_ready(b, who)) != TM_OK || (text == TM_TEXT_RAW && (rc = origin_ready(b, who)) != TM_OK)) return rc;
+  if (reinterpret_cast<uintptr_t>(spans_out) % 8) return set_error(TM_E_INVALID, "%s: spans_out not aligned to 8 bytes (a pair leaves in one store)", who);
+  if ((rc = enter_device(b->vocab)) != TM_OK || (rc = ensure_output(b)) != TM_OK) return rc;      // (waits for the run: the rows are all there)
+  const uint64_t total = b->ndocs ? b->last_totals[1] : 0;
+  if (total > spans_cap) return set_error(TM_E_NOSPACE, "%s: spans_cap %llu < %llu ids", who, (unsigned long long)spans_cap, (unsigned long long)total);
+  if (total && !spans_out) return set_error(TM_E_INVALID, "%s: null argument", who);
+  if ((rc = spans_check_lengths(b, who)) != TM_OK) return rc;
+  return batch_spans_in_on(b, (hipStream_t)stream, text, unit, spans_out, total, host_docs, ms);
 }
 
 }  // namespace tmh
@@ -378,16 +355,7 @@ using namespace tmh;
 extern "C" {
 
 int tm_batch_spans(tm_batch* b, void* stream, uint32_t* spans_out, uint64_t spans_cap) {
-  if (!b) return set_error(TM_E_INVALID, "tm_batch_spans: null argument");
-  int rc = spans_ready(b, "tm_batch_spans");
-  if (rc != TM_OK) return rc;
-  if (reinterpret_cast<uintptr_t>(spans_out) % 8) return set_error(TM_E_INVALID, "tm_batch_spans: spans_out not aligned to 8 bytes (a pair leaves in one store)");
-  if ((rc = enter_device(b->vocab)) != TM_OK || (rc = ensure_output(b)) != TM_OK) return rc;      // (waits for the run: the rows are all there)
-  const uint64_t total = b->ndocs ? b->last_totals[1] : 0;
-  if (total > spans_cap) return set_error(TM_E_NOSPACE, "tm_batch_spans: spans_cap %llu < %llu ids", (unsigned long long)spans_cap, (unsigned long long)total);
-  if (total && !spans_out) return set_error(TM_E_INVALID, "tm_batch_spans: null argument");
-  if ((rc = spans_check_lengths(b, "tm_batch_spans")) != TM_OK) return rc;
-  return batch_spans_on(b, (hipStream_t)stream, spans_out, total);
+  return ragged_spans_impl(b, stream, TM_TEXT_NORMALIZED, TM_UNIT_BYTES, spans_out, spans_cap, nullptr, nullptr, "tm_batch_spans");
 }
 
 int tm_batch_collate_spans(tm_batch* b, const tm_collate* how, void* stream, void* spans_out, uint32_t span_bytes) {
@@ -399,17 +367,10 @@ int tm_batch_raw_spans(tm_batch* b, void* stream, uint32_t* spans_out, uint64_t 
 }
 
 int tm_batch_raw_spans_timed(tm_batch* b, void* stream, uint32_t* spans_out, uint64_t spans_cap, uint32_t* host_docs, float* ms) {
-  if (!b) return set_error(TM_E_INVALID, "tm_batch_raw_spans: null argument");
-  if (host_docs) *host_docs = 0;
-  int rc = spans_ready(b, "tm_batch_raw_spans");
-  if (rc != TM_OK || (rc = origin_ready(b, "tm_batch_raw_spans")) != TM_OK) return rc;
-  if (reinterpret_cast<uintptr_t>(spans_out) % 8) return set_error(TM_E_INVALID, "tm_batch_raw_spans: spans_out not aligned to 8 bytes (a pair leaves in one store)");
-  if ((rc = enter_device(b->vocab)) != TM_OK || (rc = ensure_output(b)) != TM_OK) return rc;
-  const uint64_t total = b->ndocs ? b->last_totals[1] : 0;
-  if (total > spans_cap) return set_error(TM_E_NOSPACE, "tm_batch_raw_spans: spans_cap %llu < %llu ids", (unsigned long long)spans_cap, (unsigned long long)total);
-  if (total && !spans_out) return set_error(TM_E_INVALID, "tm_batch_raw_spans: null argument");
-  if ((rc = spans_check_lengths(b, "tm_batch_raw_spans")) != TM_OK) return rc;
-  return batch_raw_spans_on(b, (hipStream_t)stream, spans_out, total, host_docs, ms);
+  float parts[4] = {0.f, 0.f, 0.f, 0.f};      // (the caller's array holds three: the unit work of bytes is nothing)
+  const int rc = ragged_spans_impl(b, stream, TM_TEXT_RAW, TM_UNIT_BYTES, spans_out, spans_cap, host_docs, ms ? parts : nullptr, "tm_batch_raw_spans");
+  if (ms) std::memcpy(ms, parts, 3 * sizeof(float));
+  return rc;
 }
 
 int tm_batch_collate_raw_spans(tm_batch* b, const tm_collate* how, void* stream, void* spans_out, uint32_t span_bytes) {

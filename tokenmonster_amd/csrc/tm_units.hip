@@ -113,7 +113,7 @@ __global__ __launch_bounds__(256) void k_unit_index(const uint8_t* __restrict__ 
 }
 
 // ---- k_unit_spans: the byte pairs of the run converted where they lie ------------------------------------------------------------------------------
-// Id t of the run belongs to the document d found by the search of k_raw_spans; the document is text[dbegin[d], dend[d]) (clamped to the n bytes
+// Id t of the run belongs to the document d found by doc_of_id (tm_collate.h); the document is text[dbegin[d], dend[d]) (clamped to the n bytes
 // the index covers).  U at the absolute position p: pre[p / UNIT_BLOCK] plus the count over [p rounded down, p) - 128 bytes on average, and the
 // value at the document's begin is to be subtracted: two long counts.  But the 64 ids of a wavefront follow one another in a document and their
 // begins never decrease, so only the HEAD of a stretch pays them - lane 0, the first id of a document, a begin that lies in front of the lane's
@@ -138,9 +138,7 @@ __global__ __launch_bounds__(256) void k_unit_spans(span_t* pairs, const uint64_
   span_t s;
   s.x = s.y = 0u;
   if (live) {
-    uint32_t lo = 0, hi = ndocs;                      // the last document whose first id is not behind t (k_raw_spans)
-    while (hi - lo > 1u) { const uint32_t mid = lo + (hi - lo) / 2u; if (tok_offsets[mid] <= t) lo = mid; else hi = mid; }
-    d = lo;
+    d = doc_of_id(tok_offsets, ndocs, t);
     d0 = std::min<uint64_t>(dbegin[d], n);
     const uint64_t len = std::min<uint64_t>(std::max<uint64_t>(dend[d], d0), n) - d0;
     s = pairs[t];
@@ -201,17 +199,12 @@ static int unit_index_on(tm_batch* b, hipStream_t st, int kind, uint32_t unit, c
   const uint32_t make = want & ~b->units_have[kind];
   if (!make) return TM_OK;
   if (!b->d_units[kind] || nblk > b->units_cap[kind]) {
-    hipError_t e;
-    if (b->d_units[kind]) {
-      trace_grow("unit index", 2 * unit_plane_bytes(nblk));
-      (void)hipFree(b->d_units[kind]);                 // (waits for the device: no conversion is still reading the old buffer)
-      b->device_bytes -= 2 * unit_plane_bytes(b->units_cap[kind]);
-      b->d_units[kind] = nullptr;
-      b->units_cap[kind] = 0;
-    }
-    b->units_have[kind] = 0;
     const uint64_t cap = nblk + nblk / 8 + 16;          // (two planes of 12 bytes per 256 of text and an eighth of headroom: below 1/8 of the text)
-    if ((e = batch_alloc_bytes(b, (void**)&b->d_units[kind], 2 * unit_plane_bytes(cap))) != hipSuccess) return hip_fail(e, "hipMalloc unit index");
+    const uint64_t old_bytes = b->d_units[kind] ? 2 * unit_plane_bytes(b->units_cap[kind]) : 0;
+    b->units_cap[kind] = 0;
+    b->units_have[kind] = 0;
+    const int rc = batch_replace(b, (void**)&b->d_units[kind], old_bytes, 2 * unit_plane_bytes(nblk), 2 * unit_plane_bytes(cap), "unit index");
+    if (rc != TM_OK) return rc;
     b->units_cap[kind] = cap;
   }
   const uint32_t todo = want & ~b->units_have[kind];
@@ -232,7 +225,9 @@ static int unit_index_on(tm_batch* b, hipStream_t st, int kind, uint32_t unit, c
   return rc;
 }
 
-int batch_units_on(tm_batch* b, hipStream_t st, uint32_t text, uint32_t unit, void* pairs, uint64_t total) {
+// the ragged BYTE pairs in `pairs` (device or page-locked, as batch_spans_on / batch_raw_spans_on left them for this `text`) converted in place on
+// `st` - the unit index of the text first where the batch does not hold it yet; nothing at all for TM_UNIT_BYTES
+static int batch_units_on(tm_batch* b, hipStream_t st, uint32_t text, uint32_t unit, void* pairs, uint64_t total) {
   if (unit == TM_UNIT_BYTES || total == 0 || b->ndocs == 0) return TM_OK;
   const int kind = text == TM_TEXT_RAW ? 1 : 0;
   const uint8_t* buf;
@@ -258,23 +253,17 @@ int batch_units_on(tm_batch* b, hipStream_t st, uint32_t text, uint32_t unit, vo
 int batch_spans_in_on(tm_batch* b, hipStream_t st, uint32_t text, uint32_t unit, void* out, uint64_t total, uint32_t* host_docs, float* ms) {
   if (host_docs) *host_docs = 0;
   if (ms) ms[0] = ms[1] = ms[2] = ms[3] = 0.f;
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-  hipError_t e = hipSuccess;
-  if (ms) for (int k = 0; k < 3 && e == hipSuccess; k++) e = hipEventCreate(&ev[k]);
-  auto mark = [&](int k) { if (ms && e == hipSuccess) e = hipEventRecord(ev[k], st); };
-  int rc;
-  if (text == TM_TEXT_RAW) rc = batch_raw_spans_on(b, st, out, total, host_docs, ms);      // (fills ms[0..2] and synchronizes when ms is given)
-  else { mark(0); rc = batch_spans_on(b, st, out, total); }
-  mark(1);
+  const bool raw = text == TM_TEXT_RAW;
+  EventBracket ev(st, ms ? 3 : 0);
+  ev.mark(0);
+  int rc = raw ? batch_raw_spans_on(b, st, out, total, host_docs, ms)      // (fills ms[0..2] and synchronizes when ms is given)
+               : batch_spans_on(b, st, out, total);
+  ev.mark(1);
   if (rc == TM_OK) rc = batch_units_on(b, st, text, unit, out, total);
-  mark(2);
-  if (ms) {
-    if (e == hipSuccess) e = hipEventSynchronize(ev[2]);
-    if (e == hipSuccess && text != TM_TEXT_RAW) e = hipEventElapsedTime(&ms[0], ev[0], ev[1]);
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms[3], ev[1], ev[2]);
-    for (int k = 0; k < 3; k++) if (ev[k]) (void)hipEventDestroy(ev[k]);
-    if (rc == TM_OK && e != hipSuccess) rc = hip_fail(e, "HIP events");
-  }
+  ev.mark(2);
+  float parts[2] = {0.f, 0.f};                        // the byte pairs, the unit work
+  rc = ev.finish(parts, rc);
+  if (ms) { if (!raw) ms[0] = parts[0]; ms[3] = parts[1]; }
   return rc;
 }
 
@@ -285,18 +274,7 @@ using namespace tmh;
 extern "C" {
 
 int tm_batch_spans_in(tm_batch* b, void* stream, uint32_t text, uint32_t unit, uint32_t* spans_out, uint64_t spans_cap, uint32_t* host_docs, float* ms) {
-  const char* who = "tm_batch_spans_in";
-  if (!b) return set_error(TM_E_INVALID, "%s: null argument", who);
-  if (host_docs) *host_docs = 0;
-  int rc = units_args(text, unit, who);
-  if (rc != TM_OK || (rc = spans_ready(b, who)) != TM_OK || (text == TM_TEXT_RAW && (rc = origin_ready(b, who)) != TM_OK)) return rc;
-  if (reinterpret_cast<uintptr_t>(spans_out) % 8) return set_error(TM_E_INVALID, "%s: spans_out not aligned to 8 bytes (a pair leaves in one store)", who);
-  if ((rc = enter_device(b->vocab)) != TM_OK || (rc = ensure_output(b)) != TM_OK) return rc;
-  const uint64_t total = b->ndocs ? b->last_totals[1] : 0;
-  if (total > spans_cap) return set_error(TM_E_NOSPACE, "%s: spans_cap %llu < %llu ids", who, (unsigned long long)spans_cap, (unsigned long long)total);
-  if (total && !spans_out) return set_error(TM_E_INVALID, "%s: null argument", who);
-  if ((rc = spans_check_lengths(b, who)) != TM_OK) return rc;
-  return batch_spans_in_on(b, (hipStream_t)stream, text, unit, spans_out, total, host_docs, ms);
+  return ragged_spans_impl(b, stream, text, unit, spans_out, spans_cap, host_docs, ms, "tm_batch_spans_in");
 }
 
 int tm_batch_collate_spans_in(tm_batch* b, const tm_collate* how, void* stream, uint32_t text, uint32_t unit, void* spans_out, uint32_t span_bytes) {

@@ -4,11 +4,11 @@
 //
 // Four steps: the windows of every document from two token offsets (k_window_counts), their scan into win_off (scan_u32; the host reads
 // win_off[nd], the number of rows), the document of every row - a binary search over win_off, a DocCursor with win_off as its keys, once per
-// ROW (k_window_row_docs) - and the fill: streaming kernels of the kind of tm_collate.hip, no table, no LDS, the output one flat run of
-// elements, one 16-byte vector per work-item (tm_collate.h).  The row of a work-item's first element is a division, the row's document one
-// load; when the vector crosses a row end the next row's document is looked up the same way - the next window of the document, or any number
-// of documents on.  (One search per row, not one per 16-byte vector in the fill, where its dependent loads stood in front of every store:
-// the measured pair is in DESIGN.md, section 4c.)
+// ROW (k_window_row_docs) - and the fill: the fill bodies tm_collate.hip's kernels run (fill_rows / fill_spans, tm_collate.h: no table, no LDS,
+// the output one flat run of elements, one 16-byte vector per work-item), here with the plan of a window.  The row of a work-item's first
+// element is a division, the row's document one load; when the vector crosses a row end the next row's document is looked up the same way - the
+// next window of the document, or any number of documents on.  (One search per row, not one per 16-byte vector in the fill, where its
+// dependent loads stood in front of every store: the measured pair is in DESIGN.md, section 4c.)
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -38,12 +38,11 @@ __global__ __launch_bounds__(256) void k_window_row_docs(const uint64_t* __restr
 }
 
 // ---- k_window_rows: the ids (or the mask) of the rows ------------------------------------------------------------------------------------------
-// MASK: the element is 1 inside the row's entries and 0 on padding (T = uint8_t); else the id.  The per-row outputs (ids launch only, each
-// may be null): the first `rows` work-items write a row's length, document and start each.
+// The fill is fill_rows (tm_collate.h) with the plan of a window.  The per-row outputs (ids launch only, each may be null): the first `rows`
+// work-items write a row's length, document and start each.
 template <typename T, bool MASK>
 __global__ __launch_bounds__(256) void k_window_rows(WindowArgs a, Flat f, T* __restrict__ out, uint32_t* __restrict__ lengths, uint32_t* __restrict__ row_doc,
                                                      uint32_t* __restrict__ row_start) {
-  constexpr uint32_t PER = 16 / sizeof(T);
   const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (!MASK && (lengths || row_doc || row_start) && t < a.rows) {
     const WinPlan w = win_plan(a, t);
@@ -51,66 +50,14 @@ __global__ __launch_bounds__(256) void k_window_rows(WindowArgs a, Flat f, T* __
     if (row_doc) row_doc[t] = w.d;
     if (row_start) row_start[t] = (uint32_t)w.start;
   }
-  uint64_t e0;
-  uint32_t cnt;
-  if (!flat_span<T>(f, t, e0, cnt)) return;
-  uint64_t r;
-  uint32_t c;
-  if (f.n <= 0xFFFFFFFFull) { r = (uint32_t)e0 / a.L; c = (uint32_t)e0 - (uint32_t)r * a.L; }      // (a 64-bit division costs more than the store it is for)
-  else { r = e0 / a.L; c = (uint32_t)(e0 - r * a.L); }
-  RowPlan p = win_plan(a, r).p;                        // (r < rows: e0 is an element of the output)
-  const uint32_t hb = a.bos != TM_NONE ? 1u : 0u;
-  T vals[PER];
-#pragma unroll
-  for (uint32_t k = 0; k < PER; k++) {
-    if (k < cnt) {
-      const uint32_t j = c - p.lo;                     // (wraps to a large number left of the entries)
-      uint32_t v;
-      if (MASK) v = j < p.len ? 1u : 0u;
-      else if (j >= p.len) v = a.pad;
-      else if (hb && j == 0) v = a.bos;
-      else if (a.eos != TM_NONE && j == p.len - 1) v = a.eos;
-      else v = a.ids[p.src + (j - hb)];
-      vals[k] = (T)v;
-      if (++c == a.L && k + 1 < cnt) { c = 0; r++; p = win_plan(a, r).p; }      // (another element follows: r is a row)
-    } else {
-      vals[k] = 0;
-    }
-  }
-  flat_store<T>(out, e0, cnt, vals);
+  fill_rows<T, MASK>(a, f, out, t, [&](uint64_t r) { return win_plan(a, r).p; });
 }
 
-// ---- k_window_spans: the pairs of the ids laid out like the rows ------------------------------------------------------------------------------------
-// The output [rows, L, 2] is one flat run of 2 * rows * L elements of T, as k_collate_spans has it: element e is component e & 1 of column
-// (e >> 1) % L of row (e >> 1) / L.  A column that holds a content id gets that id's pair; BOS, EOS and padding get (0, 0).
+// ---- k_window_spans: the pairs of the ids laid out like the rows (fill_spans, tm_collate.h, with the plan of a window) ------------------------------
 template <typename T>
 __global__ __launch_bounds__(256) void k_window_spans(WindowArgs a, Flat f, const uint32_t* __restrict__ spans, T* __restrict__ out) {
-  constexpr uint32_t PER = 16 / sizeof(T);
   const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  uint64_t e0;
-  uint32_t cnt;
-  if (!flat_span<T>(f, t, e0, cnt)) return;
-  const uint64_t L2 = 2ull * a.L;
-  uint64_t r;
-  uint64_t c;                                         // element of the row: 2 * column + component
-  if (f.n <= 0xFFFFFFFFull && L2 <= 0xFFFFFFFFull) { r = (uint32_t)e0 / (uint32_t)L2; c = (uint32_t)e0 - (uint32_t)r * (uint32_t)L2; }
-  else { r = e0 / L2; c = e0 - r * L2; }
-  RowPlan p = win_plan(a, r).p;
-  const uint32_t hb = a.bos != TM_NONE ? 1u : 0u;
-  T vals[PER];
-#pragma unroll
-  for (uint32_t k = 0; k < PER; k++) {
-    if (k < cnt) {
-      const uint32_t j = (uint32_t)(c >> 1) - p.lo;      // (wraps to a large number left of the entries)
-      uint32_t v = 0;
-      if (j < p.len && !(hb && j == 0) && !(a.eos != TM_NONE && j == p.len - 1)) v = spans[2 * (p.src + (j - hb)) + (c & 1u)];
-      vals[k] = (T)v;
-      if (++c == L2 && k + 1 < cnt) { c = 0; r++; p = win_plan(a, r).p; }
-    } else {
-      vals[k] = 0;
-    }
-  }
-  flat_store<T>(out, e0, cnt, vals);
+  fill_spans<T>(a, f, spans, out, t, [&](uint64_t r) { return win_plan(a, r).p; });
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------------------------------
@@ -127,19 +74,13 @@ static WinBuf win_buf(const tm_batch* b) {
 }
 static int win_reserve(tm_batch* b, uint32_t nd) {
   if (b->d_win && nd <= b->win_cap) return TM_OK;
-  hipError_t e;
   auto bytes = [](uint32_t cap) { return ((uint64_t)cap + 1 + win_sum_words(cap)) * 8 + (uint64_t)cap * 4; };
-  if (b->d_win) {
-    trace_grow("windows", bytes(nd));
-    (void)hipFree(b->d_win);                         // (waits for the device: no fill is still reading the old buffer)
-    b->device_bytes -= bytes(b->win_cap);
-    b->d_win = nullptr;
-    b->win_cap = 0;
-  }
   const uint32_t cap = (uint32_t)std::min<uint64_t>((uint64_t)nd + nd / 4 + 1024, 0xFFFFFFFFull);
-  if ((e = batch_alloc_bytes(b, (void**)&b->d_win, bytes(cap))) != hipSuccess) return hip_fail(e, "hipMalloc windows");
-  b->win_cap = cap;
-  return TM_OK;
+  const uint64_t old_bytes = b->d_win ? bytes(b->win_cap) : 0;
+  b->win_cap = 0;
+  const int rc = batch_replace(b, (void**)&b->d_win, old_bytes, bytes(nd), bytes(cap), "windows");
+  if (rc == TM_OK) b->win_cap = cap;
+  return rc;
 }
 
 // what the four calls share: the arguments, the rows per document and their scan on the stream of the batch's last run, and the number of
@@ -174,17 +115,8 @@ static int window_plan(tm_batch* b, const tm_collate* how, uint32_t overlap, con
 
 // the document of every row into the batch's own buffer, on the stream of the fill behind it
 static int window_row_docs(tm_batch* b, WindowArgs* a, hipStream_t st) {
-  if (a->rows > b->win_rows_cap) {
-    hipError_t e;
-    if (b->win_rows_cap) trace_grow("window rows", a->rows * 4);
-    (void)hipFree(b->d_win_rows);                    // (waits for the device: no fill is still reading the old buffer)
-    b->device_bytes -= b->win_rows_cap * 4;
-    b->d_win_rows = nullptr;
-    b->win_rows_cap = 0;
-    const uint64_t cap = a->rows + a->rows / 4 + 1024;
-    if ((e = batch_alloc_bytes(b, (void**)&b->d_win_rows, cap * 4)) != hipSuccess) return hip_fail(e, "hipMalloc window rows");
-    b->win_rows_cap = cap;
-  }
+  const int rc = grow_batch(b, (void**)&b->d_win_rows, &b->win_rows_cap, a->rows, a->rows + a->rows / 4 + 1024, 4, "window rows");
+  if (rc != TM_OK) return rc;
   (void)hipGetLastError();
   TM_LAUNCH(k_window_row_docs, grid_of(a->rows), 256, 0, st, a->win_off, a->nd, a->rows, b->d_win_rows);
   a->row_doc = b->d_win_rows;
@@ -213,11 +145,8 @@ static int windows_spans(tm_batch* b, const tm_collate* how, uint32_t overlap, v
   if (a.rows > rows_cap) return set_error(TM_E_NOSPACE, "%s: rows_cap %llu < %llu rows required", who, (unsigned long long)rows_cap, (unsigned long long)a.rows);
   if (a.rows == 0) return TM_OK;
   const uint64_t total = b->last_totals[1];
-  if ((rc = spans_check_lengths(b, who)) != TM_OK || (rc = spans_reserve(b, total)) != TM_OK) return rc;
   hipStream_t st = (hipStream_t)stream;
-  // the ragged pairs first, into the batch's own buffer (the raw ones where the normalized ones lay)
-  if ((rc = raw ? batch_raw_spans_on(b, st, b->d_spans, total, nullptr, nullptr) : batch_spans_on(b, st, b->d_spans, total)) != TM_OK) return rc;
-  if ((rc = batch_units_on(b, st, raw ? TM_TEXT_RAW : TM_TEXT_NORMALIZED, unit, b->d_spans, total)) != TM_OK) return rc;      // (tm_units.hip; nothing for TM_UNIT_BYTES)
+  if ((rc = spans_check_lengths(b, who)) != TM_OK || (rc = batch_own_spans_on(b, st, raw ? TM_TEXT_RAW : TM_TEXT_NORMALIZED, unit, total)) != TM_OK) return rc;
   if ((rc = window_row_docs(b, &a, st)) != TM_OK) return rc;
   (void)hipGetLastError();
   a.ids = nullptr;
