@@ -669,15 +669,12 @@ static int pipeline_ring(PipeCall& c, const std::vector<Ring*>& rings) {
         RingSlot& s = r.slots[si];
         tm_batch* b = s.ws;
         uint64_t* lo = s.h_roff();
-        uint64_t npieces = 0;
         ch.local_offsets(lo);
-        const uint64_t grows = (v->host.norm_flag & 64u) ? 1u : 0u;       // (leadingspace: as batch_upload_raw_on counts them)
-        for (uint32_t d = 0; d < nd; d++) npieces += (lo[d + 1] - lo[d] + grows + RAW_PIECE - 1) / RAW_PIECE;
         hipStream_t cs = r.comp[issued % r.comp.size()];
         hipError_t e = hipSuccess;
         const double ti0 = trace ? now_ms() : 0;
         enqueued = true;
-        if ((rc = raw_prepare(b, nb, nd, npieces, cs)) != TM_OK) break;
+        if ((rc = raw_prepare(b, nb, nd, raw_piece_count(v, lo, nd), cs)) != TM_OK) break;
         if ((e = hipMemcpyAsync(b->d_raw, c.text + b0, nb, hipMemcpyHostToDevice, r.up)) != hipSuccess ||
             (e = hipMemcpyAsync(b->d_raw_off, lo, ((uint64_t)nd + 1) * 8, hipMemcpyHostToDevice, r.up)) != hipSuccess ||
             (e = hipEventRecord(s.up_done, r.up)) != hipSuccess || (e = hipStreamWaitEvent(cs, s.up_done, 0)) != hipSuccess) { rc = hip_fail(e, "ring upload"); break; }

@@ -2700,9 +2700,9 @@ void tm_batch_free(tm_batch* b) {
   void* ptrs[] = {b->text_borrowed ? nullptr : (void*)b->d_text, b->d_offsets, b->d_doc_nseg, b->d_doc_seg_start, b->d_seg_doc, b->d_R0, b->d_R1, b->d_side, b->d_exitmap, b->d_exit16, b->d_seg_entry,
                   b->d_seg_tokbase, b->d_seg_par, b->d_doc_ntok, b->d_doc_events, b->d_doc_missing, b->d_doc_fd, b->d_tok_offsets, b->d_scan_tmp, b->d_totals,
                   b->d_out, b->d_groups, b->d_longs, b->d_gmap, b->d_group_entry, b->d_group_base,
-                  b->d_raw, b->d_slab, b->d_raw_off, b->d_doc_npiece, b->d_doc_piece_start, b->d_piece_doc, b->d_piece_sum, b->d_piece_carry, b->d_piece_len,
-                  b->d_piece_off, b->d_need_host, b->d_nbegin, b->d_nend, b->d_ninfo, b->d_fb_roff, b->d_fb_noff, b->d_fb_ids, b->d_two, b->d_ctl_store, b->d_dec_a, b->d_dec_b, b->d_rawf, b->d_rawf_off, b->d_pf_piece, b->d_pf_doc, b->d_acc, b->d_spans, b->d_own, b->d_own_tmp, b->d_win, b->d_win_rows, b->d_units[0], b->d_units[1]};
+                  b->d_ctl_store, b->d_dec_a, b->d_dec_b, b->d_spans, b->d_own, b->d_own_tmp, b->d_win, b->d_win_rows, b->d_units[0], b->d_units[1]};
   for (void* p : ptrs) (void)hipFree(p);
+  tmh::raw_free(b);                                    // the normalizer's and the filter pass's device buffers (tm_norm.hip)
   if (b->have_events) for (auto& ev : b->ev) (void)hipEventDestroy(ev);
   if (b->aux_stream) (void)hipStreamDestroy(b->aux_stream);
   (void)hipHostFree(b->h_fb_raw); (void)hipHostFree(b->h_fb_norm); (void)hipHostFree(b->h_mail); (void)hipHostFree(b->h_groups);

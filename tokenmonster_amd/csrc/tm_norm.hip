@@ -2,6 +2,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <chrono>
 #include <cstring>
@@ -1133,15 +1134,6 @@ const std::vector<uint8_t>& norm_tables(uint32_t flags, bool capcode2) {
   }
   return t;
 }
-template <typename T>
-hipError_t grow(T** p, uint64_t* cap, uint64_t need, uint64_t slack = 0) {
-  if (*p && *cap >= need) return hipSuccess;
-  if (*p) trace_grow("normalizer buffer", need * sizeof(T));
-  (void)hipFree(*p);
-  *p = nullptr;
-  *cap = need + need / 4 + slack;
-  return hipMalloc((void**)p, *cap * sizeof(T));
-}
 }  // namespace
 
 extern "C" {
@@ -1160,18 +1152,56 @@ int batch_upload_raw_on(tm_batch* b, const uint8_t* raw, const uint64_t* raw_off
   if (ndocs > b->max_docs) return set_error(TM_E_LIMIT, "batch has %u documents, workspace sized for %u", ndocs, b->max_docs);
   const uint64_t nbytes = ndocs ? raw_offsets[ndocs] : 0;
   if (ndocs && raw_offsets[0] != 0) return set_error(TM_E_INVALID, "offsets[0] must be 0");
-  uint64_t npieces = 0;
-  const uint64_t grows = (b->vocab->host.norm_flag & 64u) ? 1u : 0u;       // leadingspace: the filter pass may put a byte in front of a document
-  for (uint32_t d = 0; d < ndocs; d++) {
+  for (uint32_t d = 0; d < ndocs; d++)
     if (raw_offsets[d + 1] < raw_offsets[d]) return set_error(TM_E_INVALID, "offsets not monotone at document %u", d);
-    npieces += (raw_offsets[d + 1] - raw_offsets[d] + grows + PIECE - 1) / PIECE;
-  }
-  { int rc = raw_prepare(b, nbytes, ndocs, npieces, st); if (rc != TM_OK) return rc; }
+  { int rc = raw_prepare(b, nbytes, ndocs, raw_piece_count(b->vocab, raw_offsets, ndocs), st); if (rc != TM_OK) return rc; }
   hipError_t e;
   if (nbytes && (e = hipMemcpyAsync(b->d_raw, raw, nbytes, hipMemcpyHostToDevice, st)) != hipSuccess) return hip_fail(e, "H2D raw text");
   b->h_raw_off.assign(raw_offsets, raw_offsets + (ndocs ? ndocs + 1 : 0));      // (the batch's own copy: it outlives the caller's array)
   if (ndocs) { int rc = small_h2d(b, b->d_raw_off, b->h_raw_off.data(), ((uint64_t)ndocs + 1) * 8, st); if (rc != TM_OK) return rc; }
   return TM_OK;
+}
+
+// The normalizer's per-document and per-piece arrays, listed ONCE: raw_prepare frees and allocates them, raw_upload_replaces_buffers asks whether it
+// would, piece_device_bytes counts them, raw_free frees them.  An array holds its kind's capacity + `extra` elements of `elem` bytes.
+struct NormArray { void** p; uint32_t elem, extra; bool per_piece; };
+static std::array<NormArray, 14> norm_arrays(tm_batch* b) {
+  return {{{(void**)&b->d_raw_off, 8, 0, false}, {(void**)&b->d_doc_npiece, 4, 0, false}, {(void**)&b->d_doc_piece_start, 8, 1, false}, {(void**)&b->d_need_host, 1, 0, false},
+           {(void**)&b->d_nbegin, 8, 0, false}, {(void**)&b->d_nend, 8, 0, false}, {(void**)&b->d_fb_ids, 4, 0, false}, {(void**)&b->d_fb_roff, 8, 1, false},
+           {(void**)&b->d_fb_noff, 8, 1, false},
+           {(void**)&b->d_piece_doc, 4, 0, true}, {(void**)&b->d_piece_sum, 4, 0, true}, {(void**)&b->d_piece_carry, 1, 0, true}, {(void**)&b->d_piece_len, 4, 0, true},
+           {(void**)&b->d_piece_off, 8, 1, true}}};
+}
+// a kind's capacity as the batch keeps it (0: nothing allocated yet; raw_docs_cap is two less than the documents' arrays were allocated for), and
+// whether its arrays take a batch of n documents / pieces as they are: two entries to spare
+static uint64_t norm_cap(const tm_batch* b, bool per_piece) { return per_piece ? (b->d_piece_doc ? b->piece_cap : 0) : (b->d_raw_off ? b->raw_docs_cap : 0); }
+static bool norm_holds(const tm_batch* b, bool per_piece, uint64_t n) { return n + 2 <= norm_cap(b, per_piece); }
+static uint64_t slab_bytes(uint64_t npieces) { return (npieces + 1) * (uint64_t)SLAB; }
+// the arrays of one kind freed and allocated again for n documents / pieces + 25 % + 16; after a failure none is left
+static int norm_replace(tm_batch* b, bool per_piece, uint64_t n) {
+  const auto arrays = norm_arrays(b);
+  const uint64_t cap = n + n / 4 + 16;
+  uint64_t each = 0;
+  for (const NormArray& a : arrays) if (a.per_piece == per_piece) each += a.elem;
+  if (norm_cap(b, per_piece)) trace_grow(per_piece ? "normalizer per-piece arrays" : "normalizer per-document arrays", n * each);
+  hipError_t e = hipSuccess;
+  for (const NormArray& a : arrays) if (a.per_piece == per_piece) { (void)hipFree(*a.p); *a.p = nullptr; }
+  for (const NormArray& a : arrays) if (a.per_piece == per_piece && e == hipSuccess) e = hipMalloc(a.p, (cap + a.extra) * a.elem);
+  if (e != hipSuccess) {
+    for (const NormArray& a : arrays) if (a.per_piece == per_piece) { (void)hipFree(*a.p); *a.p = nullptr; }
+    return hip_fail(e, per_piece ? "hipMalloc (pieces)" : "hipMalloc (raw documents)");
+  }
+  if (per_piece) b->piece_cap = cap;
+  else b->raw_docs_cap = (uint32_t)std::min<uint64_t>(cap - 2, 0xFFFFFFFFull);
+  return TM_OK;
+}
+
+// the 1 KiB pieces of a raw batch: of every document, and of the byte leadingspace may put in front of it in the filter pass
+uint64_t raw_piece_count(const tm_vocab* v, const uint64_t* offsets, uint32_t ndocs) {
+  const uint64_t grows = (v->host.norm_flag & 64u) ? 1u : 0u;
+  uint64_t npieces = 0;
+  for (uint32_t d = 0; d < ndocs; d++) npieces += (offsets[d + 1] - offsets[d] + grows + PIECE - 1) / PIECE;
+  return npieces;
 }
 
 // the device buffers of a raw batch of this size (grow-only), the normalizer's tables on first use, and the batch's counts
@@ -1182,41 +1212,18 @@ int raw_prepare(tm_batch* b, uint64_t nbytes, uint32_t ndocs, uint64_t npieces, 
   if (nbytes > b->max_bytes) return set_error(TM_E_LIMIT, "raw batch has %llu bytes, workspace sized for %llu", (unsigned long long)nbytes, (unsigned long long)b->max_bytes);
   if (npieces > b->max_bytes / 256 + (uint64_t)b->max_docs) return set_error(TM_E_LIMIT, "raw batch has %llu pieces, workspace scans hold %llu", (unsigned long long)npieces, (unsigned long long)(b->max_bytes / 256 + b->max_docs));
   hipError_t e;
-  uint64_t docs_cap = b->raw_docs_cap;
-  if ((e = grow(&b->d_raw, &b->raw_cap, nbytes + 256)) != hipSuccess) return hip_fail(e, "hipMalloc (raw text)");
-  if (!b->d_raw_off || ndocs + 2 > docs_cap) {
-    void** ps[] = {(void**)&b->d_raw_off, (void**)&b->d_doc_npiece, (void**)&b->d_doc_piece_start, (void**)&b->d_need_host, (void**)&b->d_nbegin, (void**)&b->d_nend,
-                   (void**)&b->d_fb_ids, (void**)&b->d_fb_roff, (void**)&b->d_fb_noff};
-    if (b->d_raw_off) trace_grow("normalizer per-document arrays", (uint64_t)ndocs * 60);
-    for (void** q : ps) { (void)hipFree(*q); *q = nullptr; }
-    docs_cap = (uint64_t)ndocs + ndocs / 4 + 16;
-    if ((e = hipMalloc((void**)&b->d_raw_off, docs_cap * 8)) != hipSuccess || (e = hipMalloc((void**)&b->d_doc_npiece, docs_cap * 4)) != hipSuccess ||
-        (e = hipMalloc((void**)&b->d_doc_piece_start, (docs_cap + 1) * 8)) != hipSuccess || (e = hipMalloc((void**)&b->d_need_host, docs_cap)) != hipSuccess ||
-        (e = hipMalloc((void**)&b->d_nbegin, docs_cap * 8)) != hipSuccess || (e = hipMalloc((void**)&b->d_nend, docs_cap * 8)) != hipSuccess ||
-        (e = hipMalloc((void**)&b->d_fb_ids, docs_cap * 4)) != hipSuccess || (e = hipMalloc((void**)&b->d_fb_roff, (docs_cap + 1) * 8)) != hipSuccess ||
-        (e = hipMalloc((void**)&b->d_fb_noff, (docs_cap + 1) * 8)) != hipSuccess)
-      return hip_fail(e, "hipMalloc (raw documents)");
-    b->raw_docs_cap = (uint32_t)std::min<uint64_t>(docs_cap - 2, 0xFFFFFFFFull);
-  }
+  int rc;
+  if ((rc = grow_device(&b->d_raw, &b->raw_cap, nbytes + 256, nbytes + 256 + (nbytes + 256) / 4, "raw text")) != TM_OK) return rc;
+  if (!norm_holds(b, false, ndocs) && (rc = norm_replace(b, false, ndocs)) != TM_OK) return rc;
   if (!b->d_ninfo && (e = hipMalloc((void**)&b->d_ninfo, 64)) != hipSuccess) return hip_fail(e, "hipMalloc");
   if (!b->d_two) {
     // what the vocabulary's flags {NFD, lowercase} do to the two-byte characters U+0080..U+017F, from the host normalizer's own building blocks
     if ((e = hipMalloc((void**)&b->d_two, NM_TABLE_BYTES)) != hipSuccess) return hip_fail(e, "hipMalloc");
     const std::vector<uint8_t>& tab = norm_tables(b->vocab->host.norm_flag & 7u, b->vocab->host.capcode == 2);
-    int rc = small_h2d(b, b->d_two, tab.data(), NM_TABLE_BYTES, st);
-    if (rc != TM_OK) return rc;
+    if ((rc = small_h2d(b, b->d_two, tab.data(), NM_TABLE_BYTES, st)) != TM_OK) return rc;
   }
-  if (!b->d_piece_doc || npieces + 2 > b->piece_cap) {
-    void** ps[] = {(void**)&b->d_piece_doc, (void**)&b->d_piece_sum, (void**)&b->d_piece_carry, (void**)&b->d_piece_len, (void**)&b->d_piece_off};
-    if (b->d_piece_doc) trace_grow("normalizer per-piece arrays", npieces * 21);
-    for (void** q : ps) { (void)hipFree(*q); *q = nullptr; }
-    b->piece_cap = npieces + npieces / 4 + 16;
-    if ((e = hipMalloc((void**)&b->d_piece_doc, b->piece_cap * 4)) != hipSuccess || (e = hipMalloc((void**)&b->d_piece_sum, b->piece_cap * 4)) != hipSuccess ||
-        (e = hipMalloc((void**)&b->d_piece_carry, b->piece_cap)) != hipSuccess || (e = hipMalloc((void**)&b->d_piece_len, b->piece_cap * 4)) != hipSuccess ||
-        (e = hipMalloc((void**)&b->d_piece_off, (b->piece_cap + 1) * 8)) != hipSuccess)
-      return hip_fail(e, "hipMalloc (pieces)");
-  }
-  if ((e = grow(&b->d_slab, &b->slab_cap, (npieces + 1) * (uint64_t)SLAB)) != hipSuccess) return hip_fail(e, "hipMalloc (normalizer slabs)");
+  if (!norm_holds(b, true, npieces) && (rc = norm_replace(b, true, npieces)) != TM_OK) return rc;
+  if ((rc = grow_device(&b->d_slab, &b->slab_cap, slab_bytes(npieces), slab_bytes(npieces) + slab_bytes(npieces) / 4, "normalizer slabs")) != TM_OK) return rc;
   b->raw_bytes = nbytes;
   b->raw_docs = ndocs;
   b->raw_pieces = npieces;
@@ -1229,11 +1236,15 @@ int raw_prepare(tm_batch* b, uint64_t nbytes, uint32_t ndocs, uint64_t npieces, 
 // per-document ranges (always) and - when the text stays in the slabs for k_match_branch - the slabs and the pieces' offsets.  The
 // host-to-host pipeline asks before it uploads a lane's next chunk beside the tokenizer kernels of the current one.
 bool raw_upload_replaces_buffers(const tm_batch* b, const uint64_t* raw_offsets, uint32_t ndocs) {
-  if (!b || !b->d_raw_off || !b->d_piece_doc) return true;
-  uint64_t npieces = 0;
-  const uint64_t grows = (b->vocab->host.norm_flag & 64u) ? 1u : 0u;       // (as batch_upload_raw_on counts them)
-  for (uint32_t d = 0; d < ndocs; d++) npieces += (raw_offsets[d + 1] - raw_offsets[d] + grows + PIECE - 1) / PIECE;
-  return (uint64_t)ndocs + 2 > b->raw_docs_cap || npieces + 2 > b->piece_cap || (npieces + 1) * (uint64_t)SLAB > b->slab_cap;
+  if (!b) return true;
+  const uint64_t npieces = raw_piece_count(b->vocab, raw_offsets, ndocs);
+  return !norm_holds(b, false, ndocs) || !norm_holds(b, true, npieces) || slab_bytes(npieces) > b->slab_cap;
+}
+// every device buffer raw_prepare and the filter pass have allocated (tm_batch_free)
+void raw_free(tm_batch* b) {
+  for (const NormArray& a : norm_arrays(b)) (void)hipFree(*a.p);
+  void* rest[] = {b->d_raw, b->d_slab, b->d_ninfo, b->d_two, b->d_rawf, b->d_rawf_off, b->d_pf_piece, b->d_pf_doc, b->d_acc};
+  for (void* p : rest) (void)hipFree(p);
 }
 
 // the slabs of the current batch packed into d_text (what tm_batch_normalize leaves out in the usual case); piece lengths and offsets are
@@ -1271,9 +1282,35 @@ static uint32_t norm_grid() {
   return slot;
 }
 
-// The filter pass (k_pf_*, above) on the uploaded text, enqueued: *R = the filtered text, *RB / *RE = where its documents begin and end (device); the
+// What a normalizer pass reads: the text and where its documents begin and end - the upload's, or what the filter pass makes of it - and its
+// np pieces.  np_dev != null (a chunk of the ring behind a filter pass): np is a bound and *np_dev, on the device, the count.
+struct NormSrc {
+  const uint8_t* R; const uint64_t* RB; const uint64_t* RE; uint64_t np; const uint64_t* np_dev;
+  uint32_t pgrid() const { return (uint32_t)((np + 3) / 4); }              // a wavefront per piece
+  uint32_t egrid() const { return std::min(pgrid(), norm_grid()); }        // k_norm_emit2: its wavefronts take piece after piece
+};
+
+// the filter pass's buffers (grow-only) for a batch of raw_bytes in nd documents; long_spans: the 16 KiB spans of the batch when a document has
+// more than one of them, else 0
+static int prefilter_reserve(tm_batch* b, uint64_t raw_bytes, uint32_t nd, uint64_t long_spans) {
+  const uint64_t out_cap = raw_bytes + (uint64_t)PF_GAP * nd + 256;
+  int rc = grow_device(&b->d_rawf, &b->rawf_cap, out_cap, out_cap + out_cap / 4, "filtered text");
+  if (rc != TM_OK) return rc;
+  if (!b->d_rawf_off || b->rawf_docs_cap < (uint64_t)nd + 2) {
+    (void)hipFree(b->d_rawf_off); (void)hipFree(b->d_pf_doc);
+    b->d_rawf_off = nullptr; b->d_pf_doc = nullptr;
+    b->rawf_docs_cap = (uint64_t)nd + nd / 4 + 16;
+    hipError_t e;
+    if ((e = hipMalloc((void**)&b->d_rawf_off, b->rawf_docs_cap * 16)) != hipSuccess || (e = hipMalloc((void**)&b->d_pf_doc, b->rawf_docs_cap * sizeof(PfDoc))) != hipSuccess)
+      return hip_fail(e, "hipMalloc (filtered documents)");
+  }
+  const uint64_t span_bytes = (long_spans + 1) * sizeof(PfPiece);
+  return long_spans ? grow_device(&b->d_pf_piece, &b->pf_piece_cap, span_bytes, span_bytes + span_bytes / 4, "filter pass spans") : TM_OK;
+}
+
+// The filter pass (k_pf_*, above) on the uploaded text, enqueued: s->R = the filtered text, s->RB / s->RE = where its documents begin and end (device); the
 // table of its pieces (k_norm_begin + scan) is made here as well, their count is left in d_totals[3].
-static int prefilter_enqueue(tm_batch* b, hipStream_t st, uint32_t norm_flag, const uint64_t* h_raw_off, const uint8_t** R, const uint64_t** RB, const uint64_t** RE) {
+static int prefilter_enqueue(tm_batch* b, hipStream_t st, uint32_t norm_flag, const uint64_t* h_raw_off, NormSrc* s) {
   const uint32_t nd = b->raw_docs;
   hipError_t e;
   uint64_t nspans = 0;
@@ -1284,21 +1321,9 @@ static int prefilter_enqueue(tm_batch* b, hipStream_t st, uint32_t norm_flag, co
     nspans += pf_spans(len);
     any_long = any_long || len > PF_WHOLE;
   }
-  const uint64_t out_cap = b->raw_bytes + (uint64_t)PF_GAP * nd + 256;
-  if ((e = grow(&b->d_rawf, &b->rawf_cap, out_cap)) != hipSuccess) return hip_fail(e, "hipMalloc (filtered text)");
-  if (!b->d_rawf_off || b->rawf_docs_cap < (uint64_t)nd + 2) {
-    (void)hipFree(b->d_rawf_off); (void)hipFree(b->d_pf_doc);
-    b->d_rawf_off = nullptr; b->d_pf_doc = nullptr;
-    b->rawf_docs_cap = (uint64_t)nd + nd / 4 + 16;
-    if ((e = hipMalloc((void**)&b->d_rawf_off, b->rawf_docs_cap * 16)) != hipSuccess || (e = hipMalloc((void**)&b->d_pf_doc, b->rawf_docs_cap * sizeof(PfDoc))) != hipSuccess)
-      return hip_fail(e, "hipMalloc (filtered documents)");
-  }
-  if (any_long) {
-    uint8_t* pp = (uint8_t*)b->d_pf_piece; uint64_t cap = b->pf_piece_cap;
-    if ((e = grow(&pp, &cap, (nspans + 1) * sizeof(PfPiece))) != hipSuccess) return hip_fail(e, "hipMalloc (filter pass)");
-    b->d_pf_piece = pp; b->pf_piece_cap = cap;
-    if (nspans + 2 > b->piece_cap) return set_error(TM_E_INTERNAL, "the filter pass has %llu spans, the workspace holds %llu pieces", (unsigned long long)nspans, (unsigned long long)b->piece_cap);
-  }
+  { int rc = prefilter_reserve(b, b->raw_bytes, nd, any_long ? nspans : 0); if (rc != TM_OK) return rc; }
+  if (any_long && nspans + 2 > b->piece_cap)
+    return set_error(TM_E_INTERNAL, "the filter pass has %llu spans, the workspace holds %llu pieces", (unsigned long long)nspans, (unsigned long long)b->piece_cap);
   if ((norm_flag & 4u) && !b->d_acc) {
     std::vector<uint32_t> acc(NM_TWO_SIZE);
     build_accent_table(acc.data());
@@ -1325,42 +1350,30 @@ static int prefilter_enqueue(tm_batch* b, hipStream_t st, uint32_t norm_flag, co
   // the pieces of the filtered documents
   TM_LAUNCH(k_norm_begin, (std::max(nd, 8u) + 255) / 256, 256, 0, st, rb, re, nd, b->d_doc_npiece, b->d_need_host, (unsigned long long*)b->d_ninfo);
   scan_u32(b->d_doc_npiece, nd, b->d_scan_tmp, b->d_totals + 3, b->d_doc_piece_start, st);
-  *R = b->d_rawf; *RB = rb; *RE = re;
-  return TM_OK;
-}
-// ... for tm_batch_normalize: with one trip to the host of its own (*np = the count of the filtered documents' pieces: the normalizer pass is launched over it)
-static int prefilter(tm_batch* b, hipStream_t st, uint32_t norm_flag, const uint8_t** R, const uint64_t** RB, const uint64_t** RE, uint64_t* np_out) {
-  int rc = prefilter_enqueue(b, st, norm_flag, b->h_raw_off.data(), R, RB, RE);
-  if (rc != TM_OK) return rc;
-  hipError_t e;
-  uint64_t np = 0;
-  if ((e = hipMemcpyAsync(&np, b->d_totals + 3, 8, hipMemcpyDeviceToHost, st)) != hipSuccess || (e = hipStreamSynchronize(st)) != hipSuccess) return hip_fail(e, "D2H filtered piece count");
-  if (np + 2 > b->piece_cap || (np + 1) * (uint64_t)SLAB > b->slab_cap * sizeof(b->d_slab[0]))
-    return set_error(TM_E_INTERNAL, "the filter pass left %llu pieces, the workspace holds %llu", (unsigned long long)np, (unsigned long long)b->piece_cap);
-  *np_out = np;
+  s->R = b->d_rawf; s->RB = rb; s->RE = re;
   return TM_OK;
 }
 
-// one_piece: the batch is a raw piece of the streaming encoder (tm_encoder.hip), which wants the normalized text and nothing of what the
-// tokenize pipeline needs behind it - no group tree for a long document (the workspace of such a batch has none)
-static int batch_normalize_impl(tm_batch* b, void* stream, bool one_piece) {
-  if (!b) return set_error(TM_E_INVALID, "null argument");
-  const tm_vocab* v = b->vocab;
-  { int rc = enter_device(v); if (rc != TM_OK) return rc; }
-  const uint32_t capcode = v->host.capcode, norm_flag = v->host.norm_flag;
-  if (!normalize_supported(capcode, norm_flag))
-    return set_error(TM_E_INVALID, "normalization flags %u / capcode %u not supported by the normalizer", norm_flag, capcode);
-  hipStream_t st = (hipStream_t)stream;
-  const uint32_t nd = b->raw_docs;
-  uint64_t np = b->raw_pieces;
-  hipError_t e;
-  const uint8_t* R = b->d_raw;                 // the text the normalizer pass reads, and its documents: the upload's, or what the filter pass makes of it
-  const uint64_t* RB = b->d_raw_off;
-  const uint64_t* RE = b->d_raw_off + 1;
+// ---- tm_batch_normalize, stage by stage ----------------------------------------------------------------------------------------------------------
+// How every normalizer call on an uploaded batch begins: the filter pass where the vocabulary has one (h_raw_off: the documents' offsets on the host),
+// the batch's state reset, the piece table and the document of every piece.  Behind a filter pass the count of the pieces is fetched (a trip of its
+// own: the pass is launched over it) - unless count_on_device: then s->np stays raw_prepare's bound and s->np_dev points at the count.
+static int norm_begin(tm_batch* b, hipStream_t st, const uint64_t* h_raw_off, bool count_on_device, NormSrc* s) {
+  const uint32_t capcode = b->vocab->host.capcode, norm_flag = b->vocab->host.norm_flag, nd = b->raw_docs;
+  *s = NormSrc{b->d_raw, b->d_raw_off, b->d_raw_off + 1, b->raw_pieces, nullptr};
   const bool filtered = (norm_flag & ~3u) && nd > 0 && (capcode == 0 || capcode == 2);
   if (filtered) {
-    int rc = prefilter(b, st, norm_flag, &R, &RB, &RE, &np);
+    int rc = prefilter_enqueue(b, st, norm_flag, h_raw_off, s);
     if (rc != TM_OK) return rc;
+    if (count_on_device) s->np_dev = b->d_totals + 3;
+    else {
+      hipError_t e;
+      uint64_t np = 0;
+      if ((e = hipMemcpyAsync(&np, b->d_totals + 3, 8, hipMemcpyDeviceToHost, st)) != hipSuccess || (e = hipStreamSynchronize(st)) != hipSuccess) return hip_fail(e, "D2H filtered piece count");
+      if (np + 2 > b->piece_cap || slab_bytes(np) > b->slab_cap)
+        return set_error(TM_E_INTERNAL, "the filter pass left %llu pieces, the workspace holds %llu", (unsigned long long)np, (unsigned long long)b->piece_cap);
+      s->np = np;
+    }
   }
   b->host_fallback_docs = 0;
   b->d_doc_begin = b->d_nbegin;
@@ -1368,192 +1381,228 @@ static int batch_normalize_impl(tm_batch* b, void* stream, bool one_piece) {
   b->ndocs = nd; b->nbytes = 0; b->nseg = 0; b->ngroups = 0; b->nlong = 0;
   b->text_in_slabs = false;
   units_forget(b, 1u);
-  b->slab_pieces = np;
+  b->slab_pieces = s->np;
   if (nd == 0) return TM_OK;
-  static const bool trace = getenv("TM_TRACE") != nullptr;
-  auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  const double t0 = now();
-  const uint32_t lower_all = (norm_flag & 2u) ? 1u : 0u;
-  unsigned long long* ninfo = (unsigned long long*)b->d_ninfo;
-  // piece table
   if (!filtered) {                             // (the filter pass has made the table of ITS documents' pieces)
-    TM_LAUNCH(k_norm_begin, (std::max(nd, 8u) + 255) / 256, 256, 0, st, RB, RE, nd, b->d_doc_npiece, b->d_need_host, ninfo);
+    TM_LAUNCH(k_norm_begin, (std::max(nd, 8u) + 255) / 256, 256, 0, st, s->RB, s->RE, nd, b->d_doc_npiece, b->d_need_host, (unsigned long long*)b->d_ninfo);
     scan_u32(b->d_doc_npiece, nd, b->d_scan_tmp, b->d_totals + 3, b->d_doc_piece_start, st);
   }
-  const uint32_t pgrid = (uint32_t)((np + 3) / 4);
-  const uint32_t egrid = std::min(pgrid, norm_grid());       // k_norm_emit2: its wavefronts take piece after piece
-  if (np > 0) launch_unit_owner(b->d_doc_piece_start, nd, np, b->d_piece_doc, st);
-  unsigned long long h_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  // The usual path is ONE pass over the raw text: k_norm_emit2<false> takes the carries of a piece from the 64 bytes either side of it and
-  // finds the documents that need the host normalizer as it goes.  A piece whose margins cannot tell (a run of 64 digits / apostrophes /
-  // capitals across a piece boundary) or whose output outgrows its slab sends the batch through the exact path after all: summaries of the
-  // pieces, carries per document, then the same emit kernel with the carries given.
-  bool fast = np > 0 && (capcode == 2 || capcode == 0) && normalize_on_device(capcode, norm_flag) && !(tm_debug_flags(-1) & 256);
-  // ... and ONE trip to the host: the whole device part — the pass, the scan of the piece lengths, the compaction, the documents' ranges
-  // and segment counts — is enqueued before anything comes back, and what comes back is everything at once: how many documents need the
-  // host normalizer, whether a piece was undecided or outgrew its slab, the normalized size, the segment and long-document counts.  (A
-  // chunk of the host-to-host pipeline used to wait for the device three times here; with four lanes' launches queueing on the runtime's
-  // lock every wait was also a gap in its stream.)  `pre`: the device part is done and valid.
-  bool pre = false;
-  uint64_t pre_bytes = 0;
-  if (fast) {
-    if (capcode == 2)
-      TM_LAUNCH(k_norm_emit2<false>, egrid, 256, 0, st, R, RB, RE, b->d_piece_doc, b->d_doc_piece_start, np, lower_all, nullptr,
-                                                 b->d_need_host, b->d_piece_len, b->d_slab, ninfo + 3, b->d_two, nullptr);
-    else
-      TM_LAUNCH(k_norm_emit<3>, pgrid, 256, 0, st, R, RB, RE, b->d_piece_doc, b->d_doc_piece_start, np, capcode, lower_all,
-                                            nullptr, b->d_need_host, b->d_piece_len, nullptr, b->d_slab, ninfo + 3, b->d_two, nullptr);
-    TM_LAUNCH(k_norm_bad, (uint32_t)((std::max<uint64_t>(np, nd) + 255) / 256), 256, 0, st, b->d_piece_doc, b->d_need_host, b->d_doc_piece_start, np, nd, b->d_piece_len, ninfo, b->d_fb_ids, nullptr);
-    scan_u32(b->d_piece_len, np, b->d_scan_tmp, reinterpret_cast<uint64_t*>(ninfo + 5), b->d_piece_off, st);      // (the total lands beside the info words: one copy brings everything)
-    // NO compaction pass here: in the usual case the text stays in the slabs and k_match_branch stages its segments from there (k_seg_fill) —
-    // packing it was 2.2 GB of traffic and 0.8 ms per GiB; pack_text() below is for the cases that need the packed text after all
-    TM_LAUNCH(k_norm_ranges_info, (nd + 255) / 256, 256, 0, st, b->d_piece_off, b->d_doc_piece_start, b->d_need_host, nd, b->d_nbegin, b->d_nend, ninfo, long_segs());
-    { int rc = small_d2h(b, h_info, ninfo, 56, st); if (rc == TM_OK) rc = small_sync(b, st);
-      if (rc != TM_OK) return rc; }
-    pre_bytes = h_info[5];
-    if (h_info[3] != 0 || h_info[4] != 0) {        // a piece whose margins could not tell, or one that outgrew its slab: the exact path, from the start
-      fast = false;
-      (void)hipMemsetAsync(ninfo, 0, 64, st);
-    } else if (h_info[0] == 0) {                    // the usual case: every document was normalized on the device
-      if (pre_bytes > b->max_bytes)
-        return set_error(TM_E_LIMIT, "normalized text needs %llu bytes, workspace sized for %llu", (unsigned long long)pre_bytes, (unsigned long long)b->max_bytes);
-      b->nbytes = pre_bytes;
-      b->nseg = h_info[2];
-      b->text_in_slabs = true;
-      if (h_info[6] != 0 || (tm_debug_flags(-1) & 2048)) pack_text(b, st);        // a short piece inside a document (or the test hook): the packed text after all
-      int rc = TM_OK;
-      if (h_info[1] > 0 && !one_piece) {
-        std::vector<uint64_t> hb(nd), he(nd);
-        if ((e = hipMemcpyAsync(hb.data(), b->d_nbegin, (size_t)nd * 8, hipMemcpyDeviceToHost, st)) != hipSuccess ||
-            (e = hipMemcpyAsync(he.data(), b->d_nend, (size_t)nd * 8, hipMemcpyDeviceToHost, st)) != hipSuccess || (e = hipStreamSynchronize(st)) != hipSuccess) return hip_fail(e, "D2H ranges");
-        rc = build_groups(b, hb.data(), he.data(), nd, st);
-      }
-      if (trace) fprintf(stderr, "[tm_batch_normalize] one trip: %.2f ms\n", now() - t0);
-      return rc;
-    } else {                                        // some documents need the host normalizer: fetch, normalize, place them behind the device part below
-      pre = true;
-      b->text_in_slabs = true;
-      pack_text(b, st);
-    }
-  }
-  if (!fast) {
-    if (np > 0) TM_LAUNCH(k_norm_summary, pgrid, 256, 0, st, R, RB, RE, b->d_piece_doc, b->d_doc_piece_start, np, lower_all, b->d_two, b->d_piece_sum);
-    TM_LAUNCH(k_norm_carry, (nd + 255) / 256, 256, 0, st, b->d_piece_sum, b->d_doc_piece_start, nd, b->d_piece_carry, b->d_need_host, ninfo, b->d_fb_ids,
-                                                    0u);
-    int rc = small_d2h(b, h_info, ninfo, 8, st); if (rc == TM_OK) rc = small_sync(b, st); if (rc != TM_OK) return rc;
-  }
-  const double t1 = now();
-  const uint32_t nf = (uint32_t)h_info[0];
-  std::vector<uint32_t> ids;
-  std::vector<uint64_t> roff;
-  double f1 = now(), f2 = 0, f3 = 0, f4 = 0;
-  // the exact path: the device normalizes its documents with the carries given (one pass into per-piece slabs, lengths on the side) ...
-  if (!fast && np > 0 && capcode == 2 && !(tm_debug_flags(-1) & 256))
-    TM_LAUNCH(k_norm_emit2<true>, egrid, 256, 0, st, R, RB, RE, b->d_piece_doc, b->d_doc_piece_start, np, lower_all, b->d_piece_carry,
-                                              b->d_need_host, b->d_piece_len, b->d_slab, ninfo + 3, b->d_two, nullptr);
-  else if (!fast && np > 0)           // capcode 0, or debug bit 8: the per-lane version of the rules
-    TM_LAUNCH(k_norm_emit<2>, pgrid, 256, 0, st, R, RB, RE, b->d_piece_doc, b->d_doc_piece_start, np, capcode, lower_all,
-                                          b->d_piece_carry, b->d_need_host, b->d_piece_len, nullptr, b->d_slab, ninfo + 3, b->d_two, nullptr);
-  if (!pre) scan_u32(b->d_piece_len, np, b->d_scan_tmp, b->d_totals + 2, b->d_piece_off, st);
-  if (!pre && np > 0 && nf == 0) TM_LAUNCH(k_norm_short, (uint32_t)((np + 255) / 256), 256, 0, st, b->d_piece_doc, b->d_need_host, b->d_doc_piece_start, np, b->d_piece_len, ninfo);
-  if (nf > 0) {
-    // ... while the documents it cannot normalize (other non-ASCII content: NFD / Unicode case need ICU) are fetched on a
-    // second stream, so that the fetch does not hold up the pass above
-    if (!b->aux_stream && (e = hipStreamCreateWithFlags(&b->aux_stream, hipStreamNonBlocking)) != hipSuccess) return hip_fail(e, "hipStreamCreate");
-    hipStream_t sx = b->aux_stream;
-    // the (unordered) list k_norm_carry / k_norm_bad has left on the device, put into document order
-    ids.resize(nf);
-    { int rc = small_d2h(b, ids.data(), b->d_fb_ids, (uint64_t)nf * 4, sx); if (rc == TM_OK) rc = small_sync(b, sx); if (rc != TM_OK) return rc; }
-    std::sort(ids.begin(), ids.end());
-    roff.assign(ids.size() + 1, 0);
-    for (size_t k = 0; k < ids.size(); k++) roff[k + 1] = roff[k] + (b->h_raw_off[ids[k] + 1] - b->h_raw_off[ids[k]]);
-    if (!b->h_fb_raw || b->h_fb_raw_cap < roff.back() + 16) {
-      (void)hipHostFree(b->h_fb_raw);
-      b->h_fb_raw = nullptr;
-      b->h_fb_raw_cap = roff.back() + roff.back() / 4 + 4096;
-      if ((e = hipHostMalloc((void**)&b->h_fb_raw, b->h_fb_raw_cap, hipHostMallocDefault)) != hipSuccess) return hip_fail(e, "hipHostMalloc (fallback staging)");
-    }
-    { int rc = small_h2d(b, b->d_fb_ids, ids.data(), ids.size() * 4, sx); if (rc == TM_OK) rc = small_h2d(b, b->d_fb_roff, roff.data(), roff.size() * 8, sx); if (rc != TM_OK) return rc; }
-    // the gather writes straight into the pinned host buffer (no staging copy, nothing on the copy engines)
-    TM_LAUNCH(k_gather_docs, (uint32_t)ids.size(), 256, 0, sx, b->d_raw, b->d_raw_off, b->d_fb_ids, b->d_fb_roff, (uint32_t)ids.size(), b->h_fb_raw);
-    if ((e = hipStreamSynchronize(sx)) != hipSuccess) return hip_fail(e, "fallback documents to the host");
-    f2 = now();
-  }
-  uint64_t gpu_bytes = 0;
-  // the host normalizes those; they are appended after the device part
-  uint8_t* hnorm = nullptr;
-  std::vector<uint64_t> noff(ids.size() + 1, 0);
-  if (nf > 0) {
-    // pooled workers: up to 128, but only this process's share of the host when there is one process per GPU of the node
-    static const uint32_t host_share = std::max(8u, std::max(1u, std::thread::hardware_concurrency()) / (uint32_t)std::max(1, tm_device_count()));
-    // ... and only as many as the bytes are worth: the pool runs one job at a time, so a chunk of the host-to-host pipeline (a few
-    // dozen fallback documents) normalizes them on its own lane thread and leaves the pool to batches that need it
-    const uint32_t threads = (uint32_t)std::min<size_t>(std::min<size_t>(std::min<uint32_t>(128u, host_share), ids.size() / 8 + 1), (size_t)(roff.back() >> 18) + 1);
-    hipError_t he = hipSuccess;
-    int rc = normalize_batch_into(b->h_fb_raw, roff.data(), (uint32_t)ids.size(), capcode, norm_flag, threads, noff.data(), [&](uint64_t total) -> uint8_t* {
-      if (!b->h_fb_norm || b->h_fb_norm_cap < total + 16) {                         // pinned: the placement kernel reads it where it lies
-        (void)hipHostFree(b->h_fb_norm);
-        b->h_fb_norm = nullptr;
-        b->h_fb_norm_cap = total + total / 4 + 4096;
-        if ((he = hipHostMalloc((void**)&b->h_fb_norm, b->h_fb_norm_cap, hipHostMallocDefault)) != hipSuccess) return nullptr;
-      }
-      return b->h_fb_norm;
-    });
-    if (he != hipSuccess) return hip_fail(he, "hipHostMalloc (fallback output)");
-    if (rc != TM_OK) return rc;
-    hnorm = b->h_fb_norm;
-    f3 = now();
-  }
-  { int rc = small_d2h(b, h_info, ninfo, 56, st); if (rc == TM_OK && !pre) rc = small_d2h(b, &gpu_bytes, b->d_totals + 2, 8, st); if (rc == TM_OK) rc = small_sync(b, st);
-    if (rc != TM_OK) return rc; }
-  if (pre) gpu_bytes = pre_bytes;
-  if (gpu_bytes + noff.back() > b->max_bytes) {
-    return set_error(TM_E_LIMIT, "normalized text needs %llu bytes, workspace sized for %llu", (unsigned long long)(gpu_bytes + noff.back()), (unsigned long long)b->max_bytes);
-  }
-  // the host-normalized documents go behind the device part; placing them (reads over PCIe) runs on the second stream beside the
-  // compaction of the device part — different bytes of d_text, different documents' ranges
-  if (nf > 0) {
-    hipStream_t sx = b->aux_stream;
-    { int rc = small_h2d(b, b->d_fb_noff, noff.data(), noff.size() * 8, sx); if (rc != TM_OK) return rc; }
-    TM_LAUNCH(k_place_fallback, (uint32_t)ids.size(), 256, 0, sx, hnorm, b->d_fb_noff, b->d_fb_ids, (uint32_t)ids.size(), gpu_bytes, b->d_text, b->d_nbegin, b->d_nend);
-  }
-  if (np > 0 && !pre) {
-    if (h_info[3] == 0) {
-      // every document normalized on the device and no short piece inside a document: the text stays in the slabs here too (k_match_branch
-      // stages it from there); otherwise it is packed - the host-normalized documents are placed behind the packed device part
-      b->text_in_slabs = true;
-      if (nf > 0 || h_info[6] != 0 || (tm_debug_flags(-1) & 2048)) pack_text(b, st);
-    } else {
-      // some piece expands beyond its slab (long runs of capitals): exact two-pass path
-      TM_LAUNCH(k_norm_emit<1>, pgrid, 256, 0, st, R, RB, RE, b->d_piece_doc, b->d_doc_piece_start, np, capcode, lower_all,
-                                            b->d_piece_carry, b->d_need_host, b->d_piece_len, b->d_piece_off, b->d_text, nullptr, b->d_two, nullptr);
-    }
-  }
-  TM_LAUNCH(k_norm_ranges, (nd + 255) / 256, 256, 0, st, b->d_piece_off, b->d_doc_piece_start, b->d_need_host, nd, b->d_nbegin, b->d_nend);
-  uint64_t total = gpu_bytes;
-  if (nf > 0) {
-    { int rc = small_sync(b, b->aux_stream); if (rc != TM_OK) return rc; }       // the placement: the text and ranges it wrote are read on `st` next
-    total += noff.back();
-    b->host_fallback_docs = (uint32_t)ids.size();
-    f4 = now();
-    if (trace) fprintf(stderr, "[fallback] flags+gather+D2H %.2f ms, host normalize (overlaps the device pass) %.2f ms, wait + H2D + place %.2f ms\n", f2 - f1, f3 - f2, f4 - f3);
-  }
-  const double t2 = now();
-  // ---- what the tokenize pipeline needs to know on the host: #segments, and the long documents if any ------------
-  if (pre) (void)hipMemsetAsync(ninfo + 1, 0, 16, st);          // (k_norm_ranges_info has counted the device documents already: count them all again)
-  TM_LAUNCH(k_norm_info, (nd + 255) / 256, 256, 0, st, b->d_nbegin, b->d_nend, nd, ninfo, long_segs());
-  { int rc = small_d2h(b, h_info, ninfo, 24, st); if (rc == TM_OK) rc = small_sync(b, st); if (rc != TM_OK) return rc; }
-  b->nbytes = total;
+  if (s->np > 0) launch_unit_owner(b->d_doc_piece_start, nd, s->np, b->d_piece_doc, st, s->np_dev);
+  return TM_OK;
+}
+
+// The one-pass form, enqueued on `st` and NOT waited for: norm_begin, then ONE pass over the raw text - the emit kernel takes the carries of a piece
+// from the 64 bytes either side of it and finds the documents that need the host normalizer as it goes -, the scan of the piece lengths, the
+// documents' ranges and segment counts.  It leaves in d_ninfo: [0] documents for the host normalizer, [1] long documents, [2] segments, [3] pieces
+// whose margins could not tell (a run of 64 digits / apostrophes / capitals across a piece boundary), [4] pieces that outgrew their slab, [5] the
+// normalized size (the scan's total lands beside the info words: one copy brings everything), [6] short pieces inside a document.  NO compaction
+// pass: the text stays in the slabs, k_match_branch stages its segments from there (packing was 0.8 ms per GiB); pack_text() where it is needed.
+static int onepass_enqueue(tm_batch* b, hipStream_t st, const uint64_t* h_raw_off, bool count_on_device, NormSrc* s) {
+  int rc = norm_begin(b, st, h_raw_off, count_on_device, s);
+  if (rc != TM_OK || s->np == 0) return rc;
+  const uint32_t capcode = b->vocab->host.capcode, lower_all = (b->vocab->host.norm_flag & 2u) ? 1u : 0u, nd = b->raw_docs;
+  unsigned long long* ninfo = (unsigned long long*)b->d_ninfo;
+  if (capcode == 2)
+    TM_LAUNCH(k_norm_emit2<false>, s->egrid(), 256, 0, st, s->R, s->RB, s->RE, b->d_piece_doc, b->d_doc_piece_start, s->np, lower_all, nullptr,
+                                               b->d_need_host, b->d_piece_len, b->d_slab, ninfo + 3, b->d_two, s->np_dev);
+  else
+    TM_LAUNCH(k_norm_emit<3>, s->pgrid(), 256, 0, st, s->R, s->RB, s->RE, b->d_piece_doc, b->d_doc_piece_start, s->np, capcode, lower_all,
+                                          nullptr, b->d_need_host, b->d_piece_len, nullptr, b->d_slab, ninfo + 3, b->d_two, s->np_dev);
+  TM_LAUNCH(k_norm_bad, (uint32_t)((std::max<uint64_t>(s->np, nd) + 255) / 256), 256, 0, st, b->d_piece_doc, b->d_need_host, b->d_doc_piece_start, s->np, nd, b->d_piece_len, ninfo, b->d_fb_ids, s->np_dev);
+  scan_u32(b->d_piece_len, s->np, b->d_scan_tmp, reinterpret_cast<uint64_t*>(ninfo + 5), b->d_piece_off, st);
+  TM_LAUNCH(k_norm_ranges_info, (nd + 255) / 256, 256, 0, st, b->d_piece_off, b->d_doc_piece_start, b->d_need_host, nd, b->d_nbegin, b->d_nend, ninfo, long_segs());
+  return TM_OK;
+}
+// the exact path's first half: summaries of the pieces, then the carries per document (the origin pass has its document flags, info words and list written on the side)
+static void launch_carries(tm_batch* b, hipStream_t st, const NormSrc& s, uint32_t nd, uint8_t* need_host, unsigned long long* ninfo, uint32_t* fb_ids) {
+  const uint32_t lower_all = (b->vocab->host.norm_flag & 2u) ? 1u : 0u;
+  if (s.np > 0) TM_LAUNCH(k_norm_summary, s.pgrid(), 256, 0, st, s.R, s.RB, s.RE, b->d_piece_doc, b->d_doc_piece_start, s.np, lower_all, b->d_two, b->d_piece_sum);
+  TM_LAUNCH(k_norm_carry, (nd + 255) / 256, 256, 0, st, b->d_piece_sum, b->d_doc_piece_start, nd, b->d_piece_carry, need_host, ninfo, fb_ids, 0u);
+}
+// the documents' ranges to the host, on the caller's stream, and the group tree of the long ones (what the tokenize pipeline needs behind the normalizer)
+static int groups_from_ranges(tm_batch* b, hipStream_t st) {
+  const uint32_t nd = b->ndocs;
+  std::vector<uint64_t> hb(nd), he(nd);
+  hipError_t e;
+  if ((e = hipMemcpyAsync(hb.data(), b->d_nbegin, (size_t)nd * 8, hipMemcpyDeviceToHost, st)) != hipSuccess ||
+      (e = hipMemcpyAsync(he.data(), b->d_nend, (size_t)nd * 8, hipMemcpyDeviceToHost, st)) != hipSuccess || (e = hipStreamSynchronize(st)) != hipSuccess) return hip_fail(e, "D2H ranges");
+  return build_groups(b, hb.data(), he.data(), nd, st);
+}
+// pooled workers for `docs` documents of `bytes` in all: up to 128, but only this process's share of the host when there is one process per GPU of
+// the node - and only one per 2^shift bytes: the pool runs one job at a time, so a chunk of the host-to-host pipeline (a few dozen fallback
+// documents) normalizes them on its own lane thread and leaves the pool to batches that need it
+static uint32_t norm_workers(size_t docs, uint64_t bytes, uint32_t shift) {
+  static const uint32_t host_share = std::max(8u, std::max(1u, std::thread::hardware_concurrency()) / (uint32_t)std::max(1, tm_device_count()));
+  return (uint32_t)std::min<size_t>(std::min<size_t>(std::min<uint32_t>(128u, host_share), docs / 8 + 1), (size_t)(bytes >> shift) + 1);
+}
+static double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+static bool norm_trace() { static const bool on = getenv("TM_TRACE") != nullptr; return on; }
+
+// The documents the device leaves to the host normalizer (other non-ASCII content: NFD / Unicode case need ICU); none: every step is a no-op.
+struct HostDocs {
+  std::vector<uint32_t> ids;            // in document order
+  std::vector<uint64_t> roff, noff;     // their offsets in the pinned staging of the raw and of the normalized bytes
+  double t[4] = {0, 0, 0, 0};
+  uint64_t bytes() const { return noff.empty() ? 0 : noff.back(); }
+};
+// ... fetched on a second stream, so that the fetch does not hold up the pass on the caller's, and normalized by the host's workers
+static int host_docs_normalize(tm_batch* b, uint32_t nf, HostDocs* h) {
+  if (nf == 0) return TM_OK;
+  hipError_t e;
+  h->t[0] = now_ms();
+  if (!b->aux_stream && (e = hipStreamCreateWithFlags(&b->aux_stream, hipStreamNonBlocking)) != hipSuccess) return hip_fail(e, "hipStreamCreate");
+  hipStream_t sx = b->aux_stream;
+  h->ids.resize(nf);
+  int rc;
+  if ((rc = small_d2h(b, h->ids.data(), b->d_fb_ids, (uint64_t)nf * 4, sx)) != TM_OK || (rc = small_sync(b, sx)) != TM_OK) return rc;
+  std::sort(h->ids.begin(), h->ids.end());
+  h->roff.assign(nf + 1, 0);
+  for (size_t k = 0; k < nf; k++) h->roff[k + 1] = h->roff[k] + (b->h_raw_off[h->ids[k] + 1] - b->h_raw_off[h->ids[k]]);
+  const uint64_t raw_bytes = h->roff.back();
+  if ((rc = grow_pinned(&b->h_fb_raw, &b->h_fb_raw_cap, raw_bytes + 16, raw_bytes + raw_bytes / 4 + 4096, "fallback staging")) != TM_OK) return rc;
+  if ((rc = small_h2d(b, b->d_fb_ids, h->ids.data(), (uint64_t)nf * 4, sx)) != TM_OK || (rc = small_h2d(b, b->d_fb_roff, h->roff.data(), h->roff.size() * 8, sx)) != TM_OK) return rc;
+  // the gather writes straight into the pinned host buffer (no staging copy, nothing on the copy engines)
+  TM_LAUNCH(k_gather_docs, nf, 256, 0, sx, b->d_raw, b->d_raw_off, b->d_fb_ids, b->d_fb_roff, nf, b->h_fb_raw);
+  if ((e = hipStreamSynchronize(sx)) != hipSuccess) return hip_fail(e, "fallback documents to the host");
+  h->t[1] = now_ms();
+  h->noff.assign(nf + 1, 0);
+  int grc = TM_OK;
+  rc = normalize_batch_into(b->h_fb_raw, h->roff.data(), nf, b->vocab->host.capcode, b->vocab->host.norm_flag, norm_workers(nf, raw_bytes, 18), h->noff.data(), [&](uint64_t total) -> uint8_t* {
+    grc = grow_pinned(&b->h_fb_norm, &b->h_fb_norm_cap, total + 16, total + total / 4 + 4096, "fallback output");      // pinned: the placement kernel reads it where it lies
+    return b->h_fb_norm;
+  });
+  h->t[2] = now_ms();
+  return grc != TM_OK ? grc : rc;
+}
+// ... placed behind the `base` bytes of the device part (reads over PCIe) on the second stream: different bytes of d_text, different documents' ranges
+static int host_docs_place(tm_batch* b, const HostDocs& h, uint64_t base) {
+  if (h.ids.empty()) return TM_OK;
+  int rc = small_h2d(b, b->d_fb_noff, h.noff.data(), h.noff.size() * 8, b->aux_stream);
+  if (rc != TM_OK) return rc;
+  TM_LAUNCH(k_place_fallback, (uint32_t)h.ids.size(), 256, 0, b->aux_stream, b->h_fb_norm, b->d_fb_noff, b->d_fb_ids, (uint32_t)h.ids.size(), base, b->d_text, b->d_nbegin, b->d_nend);
+  return TM_OK;
+}
+// ... and waited for: the text and ranges the placement wrote are read on the caller's stream next
+static int host_docs_wait(tm_batch* b, HostDocs* h) {
+  if (h->ids.empty()) return TM_OK;
+  int rc = small_sync(b, b->aux_stream);
+  if (rc != TM_OK) return rc;
+  b->host_fallback_docs = (uint32_t)h->ids.size();
+  h->t[3] = now_ms();
+  if (norm_trace()) fprintf(stderr, "[fallback] flags+gather+D2H %.2f ms, host normalize (overlaps the device pass) %.2f ms, wait + H2D + place %.2f ms\n", h->t[1] - h->t[0], h->t[2] - h->t[1], h->t[3] - h->t[2]);
+  return TM_OK;
+}
+static int limit_bytes(const tm_batch* b, uint64_t bytes) {
+  return bytes <= b->max_bytes ? TM_OK : set_error(TM_E_LIMIT, "normalized text needs %llu bytes, workspace sized for %llu", (unsigned long long)bytes, (unsigned long long)b->max_bytes);
+}
+struct NormCall { hipStream_t st; bool one_piece; double t0, t1; };      // one_piece: below; t0, t1: the call's start and the end of its first trip (TM_TRACE)
+
+// How every path but the usual one ends: the documents' ranges, then what the tokenize pipeline needs to know on the host - the segments, and the
+// long documents if any.  recount: k_norm_ranges_info has counted the device's documents already, count them all again.
+static int norm_close(tm_batch* b, const NormCall& c, uint64_t device_bytes, HostDocs* h, bool recount) {
+  const uint32_t nd = b->ndocs;
+  unsigned long long* ninfo = (unsigned long long*)b->d_ninfo;
+  TM_LAUNCH(k_norm_ranges, (nd + 255) / 256, 256, 0, c.st, b->d_piece_off, b->d_doc_piece_start, b->d_need_host, nd, b->d_nbegin, b->d_nend);
+  int rc = host_docs_wait(b, h);
+  if (rc != TM_OK) return rc;
+  const double t2 = now_ms();
+  if (recount) (void)hipMemsetAsync(ninfo + 1, 0, 16, c.st);
+  TM_LAUNCH(k_norm_info, (nd + 255) / 256, 256, 0, c.st, b->d_nbegin, b->d_nend, nd, ninfo, long_segs());
+  unsigned long long h_info[3] = {0, 0, 0};
+  if ((rc = small_d2h(b, h_info, ninfo, 24, c.st)) != TM_OK || (rc = small_sync(b, c.st)) != TM_OK) return rc;
+  b->nbytes = device_bytes + h->bytes();
   b->nseg = h_info[2];
-  int rc = TM_OK;
-  if (h_info[1] > 0 && !one_piece) {
-    std::vector<uint64_t> hb(nd), he(nd);
-    if ((e = hipMemcpy(hb.data(), b->d_nbegin, (size_t)nd * 8, hipMemcpyDeviceToHost)) != hipSuccess ||
-        (e = hipMemcpy(he.data(), b->d_nend, (size_t)nd * 8, hipMemcpyDeviceToHost)) != hipSuccess) return hip_fail(e, "D2H ranges");
-    rc = build_groups(b, hb.data(), he.data(), nd, st);
-  }
-  if (trace) fprintf(stderr, "[tm_batch_normalize] summaries %.2f ms, device pass + host fallback (%u docs) %.2f ms, info %.2f ms\n", t1 - t0, nf, t2 - t1, now() - t2);
+  if (h_info[1] > 0 && !c.one_piece) rc = groups_from_ranges(b, c.st);
+  if (norm_trace()) fprintf(stderr, "[tm_batch_normalize] summaries %.2f ms, device pass + host fallback (%u docs) %.2f ms, info %.2f ms\n", c.t1 - c.t0, (unsigned)h->ids.size(), t2 - c.t1, now_ms() - t2);
   return rc;
+}
+// Outcome 1, the usual one: the one pass normalized every document.  The text stays in the slabs, but for a short piece inside a document (or the test hook).
+static int onepass_done(tm_batch* b, const NormCall& c, const unsigned long long* h_info) {
+  int rc = limit_bytes(b, h_info[5]);
+  if (rc != TM_OK) return rc;
+  b->nbytes = h_info[5];
+  b->nseg = h_info[2];
+  b->text_in_slabs = true;
+  if (h_info[6] != 0 || (debug_flags() & 2048)) pack_text(b, c.st);
+  if (h_info[1] > 0 && !c.one_piece) rc = groups_from_ranges(b, c.st);
+  if (norm_trace()) fprintf(stderr, "[tm_batch_normalize] one trip: %.2f ms\n", now_ms() - c.t0);
+  return rc;
+}
+// Outcome 2: the one pass is valid, and h_info[0] documents need the host normalizer - the device part is packed and they are placed behind it.
+static int onepass_with_host_docs(tm_batch* b, const NormCall& c, unsigned long long* h_info) {
+  const uint64_t device_bytes = h_info[5];
+  b->text_in_slabs = true;
+  pack_text(b, c.st);
+  HostDocs h;
+  int rc = host_docs_normalize(b, (uint32_t)h_info[0], &h);
+  if (rc != TM_OK) return rc;
+  if ((rc = small_d2h(b, h_info, b->d_ninfo, 56, c.st)) != TM_OK || (rc = small_sync(b, c.st)) != TM_OK) return rc;
+  if ((rc = limit_bytes(b, device_bytes + h.bytes())) != TM_OK || (rc = host_docs_place(b, h, device_bytes)) != TM_OK) return rc;
+  return norm_close(b, c, device_bytes, &h, true);
+}
+
+// Outcomes 3 to 5, the exact path - after a piece whose margins could not tell or one that outgrew its slab, or from the start (flags the one pass
+// does not take, hook 8): summaries of the pieces, carries per document, then the device normalizes its documents with the carries given (one pass
+// into per-piece slabs, lengths on the side; capcode 0 or hook 8: the per-lane version of the rules) while the host normalizes the others.  A piece
+// that outgrows its slab even so (long runs of capitals) sends the device part through the two-pass emit, which writes the packed text.
+static int exact_path(tm_batch* b, NormCall& c, const NormSrc& s) {
+  hipStream_t st = c.st;
+  const uint32_t capcode = b->vocab->host.capcode, lower_all = (b->vocab->host.norm_flag & 2u) ? 1u : 0u, nd = b->raw_docs;
+  unsigned long long* ninfo = (unsigned long long*)b->d_ninfo;
+  unsigned long long h_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  launch_carries(b, st, s, nd, b->d_need_host, ninfo, b->d_fb_ids);
+  int rc;
+  if ((rc = small_d2h(b, h_info, ninfo, 8, st)) != TM_OK || (rc = small_sync(b, st)) != TM_OK) return rc;
+  c.t1 = now_ms();
+  const uint32_t nf = (uint32_t)h_info[0];
+  if (s.np > 0 && capcode == 2 && !(debug_flags() & 256))
+    TM_LAUNCH(k_norm_emit2<true>, s.egrid(), 256, 0, st, s.R, s.RB, s.RE, b->d_piece_doc, b->d_doc_piece_start, s.np, lower_all, b->d_piece_carry,
+                                              b->d_need_host, b->d_piece_len, b->d_slab, ninfo + 3, b->d_two, nullptr);
+  else if (s.np > 0)
+    TM_LAUNCH(k_norm_emit<2>, s.pgrid(), 256, 0, st, s.R, s.RB, s.RE, b->d_piece_doc, b->d_doc_piece_start, s.np, capcode, lower_all,
+                                          b->d_piece_carry, b->d_need_host, b->d_piece_len, nullptr, b->d_slab, ninfo + 3, b->d_two, nullptr);
+  scan_u32(b->d_piece_len, s.np, b->d_scan_tmp, b->d_totals + 2, b->d_piece_off, st);
+  if (s.np > 0 && nf == 0) TM_LAUNCH(k_norm_short, (uint32_t)((s.np + 255) / 256), 256, 0, st, b->d_piece_doc, b->d_need_host, b->d_doc_piece_start, s.np, b->d_piece_len, ninfo);
+  HostDocs h;
+  if ((rc = host_docs_normalize(b, nf, &h)) != TM_OK) return rc;
+  uint64_t device_bytes = 0;
+  if ((rc = small_d2h(b, h_info, ninfo, 56, st)) != TM_OK || (rc = small_d2h(b, &device_bytes, b->d_totals + 2, 8, st)) != TM_OK || (rc = small_sync(b, st)) != TM_OK) return rc;
+  if ((rc = limit_bytes(b, device_bytes + h.bytes())) != TM_OK || (rc = host_docs_place(b, h, device_bytes)) != TM_OK) return rc;
+  if (s.np > 0 && h_info[3] == 0) {
+    // no short piece inside a document and no host document: the text stays in the slabs here too (k_match_branch stages it from there);
+    // otherwise it is packed - the host-normalized documents are placed behind the packed device part
+    b->text_in_slabs = true;
+    if (nf > 0 || h_info[6] != 0 || (debug_flags() & 2048)) pack_text(b, st);
+  } else if (s.np > 0)
+    TM_LAUNCH(k_norm_emit<1>, s.pgrid(), 256, 0, st, s.R, s.RB, s.RE, b->d_piece_doc, b->d_doc_piece_start, s.np, capcode, lower_all,
+                                          b->d_piece_carry, b->d_need_host, b->d_piece_len, b->d_piece_off, b->d_text, nullptr, b->d_two, nullptr);
+  return norm_close(b, c, device_bytes, &h, false);
+}
+
+// tm_batch_normalize: the one-pass form and ONE trip to the host - the whole device part is enqueued before anything comes back, and what comes
+// back is everything at once.  (A chunk of the host-to-host pipeline used to wait for the device three times here; with four lanes' launches
+// queueing on the runtime's lock every wait was also a gap in its stream.)  What the info words say decides the outcome.  one_piece: the batch is
+// a raw piece of the streaming encoder (tm_encoder.hip), which wants the normalized text and no group tree (the workspace of such a batch has none)
+static int batch_normalize_impl(tm_batch* b, void* stream, bool one_piece) {
+  if (!b) return set_error(TM_E_INVALID, "null argument");
+  const tm_vocab* v = b->vocab;
+  { int rc = enter_device(v); if (rc != TM_OK) return rc; }
+  const uint32_t capcode = v->host.capcode, norm_flag = v->host.norm_flag;
+  if (!normalize_supported(capcode, norm_flag))
+    return set_error(TM_E_INVALID, "normalization flags %u / capcode %u not supported by the normalizer", norm_flag, capcode);
+  NormCall c{(hipStream_t)stream, one_piece, now_ms(), 0};
+  NormSrc s;
+  const bool one_pass = (capcode == 2 || capcode == 0) && normalize_on_device(capcode, norm_flag) && !(debug_flags() & 256);
+  int rc = one_pass ? onepass_enqueue(b, c.st, b->h_raw_off.data(), false, &s) : norm_begin(b, c.st, b->h_raw_off.data(), false, &s);
+  if (rc != TM_OK || b->raw_docs == 0) return rc;
+  if (one_pass && s.np > 0) {
+    unsigned long long h_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if ((rc = small_d2h(b, h_info, b->d_ninfo, 56, c.st)) != TM_OK || (rc = small_sync(b, c.st)) != TM_OK) return rc;
+    c.t1 = now_ms();
+    if (h_info[3] == 0 && h_info[4] == 0) return h_info[0] == 0 ? onepass_done(b, c, h_info) : onepass_with_host_docs(b, c, h_info);
+    (void)hipMemsetAsync(b->d_ninfo, 0, 64, c.st);        // a piece whose margins could not tell, or one that outgrew its slab: the exact path, from the start
+  }
+  return exact_path(b, c, s);
 }
 
 int tm_batch_normalize(tm_batch* b, void* stream) { return batch_normalize_impl(b, stream, false); }
@@ -1593,17 +1642,13 @@ int origin_pass_on(tm_batch* b, hipStream_t st, uint32_t* host_docs) {
   std::vector<uint8_t> need(nd, 1);
   if (on_device) {
     const uint32_t lower_all = (norm_flag & 2u) ? 1u : 0u;
-    const uint32_t pgrid = (uint32_t)((np + 3) / 4);
-    const uint64_t* RB = b->d_raw_off;
-    const uint64_t* RE = b->d_raw_off + 1;
+    const NormSrc s{b->d_raw, b->d_raw_off, b->d_raw_off + 1, np, nullptr};
     if (np > 0 && capcode == 2) {
-      TM_LAUNCH(k_norm_summary, pgrid, 256, 0, st, b->d_raw, RB, RE, b->d_piece_doc, b->d_doc_piece_start, np, lower_all, b->d_two, b->d_piece_sum);
       (void)hipMemsetAsync(b->d_own_tmp + o_info, 0, 64, st);
-      TM_LAUNCH(k_norm_carry, (nd + 255) / 256, 256, 0, st, b->d_piece_sum, b->d_doc_piece_start, nd, b->d_piece_carry, b->d_own_tmp,
-                (unsigned long long*)(b->d_own_tmp + o_info), reinterpret_cast<uint32_t*>(b->d_own_tmp + o_ids), 0u);
+      launch_carries(b, st, s, nd, b->d_own_tmp, (unsigned long long*)(b->d_own_tmp + o_info), reinterpret_cast<uint32_t*>(b->d_own_tmp + o_ids));
     }
     if (np > 0)
-      TM_LAUNCH(k_norm_emit<4>, pgrid, 256, 0, st, b->d_raw, RB, RE, b->d_piece_doc, b->d_doc_piece_start, np, capcode, lower_all, b->d_piece_carry,
+      TM_LAUNCH(k_norm_emit<4>, s.pgrid(), 256, 0, st, s.R, s.RB, s.RE, b->d_piece_doc, b->d_doc_piece_start, np, capcode, lower_all, b->d_piece_carry,
                 b->d_need_host, b->d_piece_len, b->d_piece_off, reinterpret_cast<uint8_t*>(b->d_own), nullptr, b->d_two, nullptr);
     if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "kernel launch");
     if (b->host_fallback_docs == 0) return TM_OK;
@@ -1637,11 +1682,9 @@ int origin_pass_on(tm_batch* b, hipStream_t st, uint32_t* host_docs) {
     if ((e = hipStreamSynchronize(st)) != hipSuccess) return hip_fail(e, "D2H raw documents");
   }
   std::vector<uint32_t> stage(hi - lo, 0u);
-  static const uint32_t host_share = std::max(8u, std::max(1u, std::thread::hardware_concurrency()) / (uint32_t)std::max(1, tm_device_count()));
-  const uint32_t threads = (uint32_t)std::min<size_t>(std::min<size_t>(std::min<uint32_t>(128u, host_share), ids.size() / 8 + 1), (size_t)(rawh.size() >> 16) + 1);
   std::atomic<uint32_t> next{0};
   std::atomic<int> bad{0};
-  run_on_workers(threads, [&]() {
+  run_on_workers(norm_workers(ids.size(), rawh.size(), 16), [&]() {
     std::vector<uint8_t> text;
     std::vector<uint32_t> own;
     for (;;) {
@@ -1663,55 +1706,23 @@ bool ring_supported(const tm_vocab* v) {
   // (a vocabulary with byte-level flags: the filter pass in front is enqueued like everything else, and the normalizer pass behind it is launched
   // over the pieces of the RAW documents - a bound: a filtered document is no longer than the raw one, but for the space leadingspace may put in
   // front, which raw_prepare has counted - and takes the count from the device)
-  return normalize_supported(capcode, norm_flag) && (capcode == 2 || capcode == 0) && !(tm_debug_flags(-1) & (256 | 2048));
+  return normalize_supported(capcode, norm_flag) && (capcode == 2 || capcode == 0) && !(debug_flags() & (256 | 2048));
 }
-// tm_batch_normalize's usual path - ONE pass over the raw text that raw_prepare + the upload have put into the workspace - enqueued on `st`
+// tm_batch_normalize's usual path (onepass_enqueue) on the chunk raw_prepare + the upload have put into the workspace, enqueued on `st`
 // and NOT waited for: what the host would read back stays in d_ninfo, k_chunk_ctl turns it into the control words the kernels behind it
 // look at (the segments are launched over `seg_bound`), and a chunk the pass cannot finish by itself (documents for the host normalizer, a
 // piece whose margins could not tell, a long document ...) is marked there and run through tm_batch_normalize by the caller afterwards.
 int ring_enqueue_normalize(tm_batch* b, hipStream_t st, uint64_t seg_bound, const uint64_t* h_raw_off) {
-  const tm_vocab* v = b->vocab;
-  const uint32_t capcode = v->host.capcode, norm_flag = v->host.norm_flag;
-  const uint32_t nd = b->raw_docs;
-  const uint64_t np = b->raw_pieces;
-  if (nd == 0 || np == 0) return set_error(TM_E_INTERNAL, "ring_enqueue_normalize: empty chunk");
+  if (b->raw_docs == 0 || b->raw_pieces == 0) return set_error(TM_E_INTERNAL, "ring_enqueue_normalize: empty chunk");
   hipError_t e;
   if (!b->d_ctl_store && (e = hipMalloc((void**)&b->d_ctl_store, 64)) != hipSuccess) return hip_fail(e, "hipMalloc");
+  (void)hipGetLastError();
+  NormSrc s;
+  int rc = onepass_enqueue(b, st, h_raw_off, true, &s);
+  if (rc != TM_OK) return rc;
   b->d_ctl = b->d_ctl_store;
-  b->host_fallback_docs = 0;
-  b->d_doc_begin = b->d_nbegin;
-  b->d_doc_end = b->d_nend;
-  b->ndocs = nd; b->nbytes = 0; b->ngroups = 0; b->nlong = 0;
   b->nseg = std::min<uint64_t>(seg_bound, b->max_segs);
   b->text_in_slabs = true;
-  b->slab_pieces = np;
-  (void)hipGetLastError();
-  const uint32_t lower_all = (norm_flag & 2u) ? 1u : 0u;
-  unsigned long long* ninfo = (unsigned long long*)b->d_ninfo;
-  const uint8_t* R = b->d_raw;
-  const uint64_t* RB = b->d_raw_off;
-  const uint64_t* RE = b->d_raw_off + 1;
-  const uint64_t* np_dev = nullptr;             // behind a filter pass np is a bound, and this the count
-  if (norm_flag & ~3u) {
-    int rc = prefilter_enqueue(b, st, norm_flag, h_raw_off, &R, &RB, &RE);
-    if (rc != TM_OK) return rc;
-    np_dev = b->d_totals + 3;
-  } else {
-    TM_LAUNCH(k_norm_begin, (std::max(nd, 8u) + 255) / 256, 256, 0, st, RB, RE, nd, b->d_doc_npiece, b->d_need_host, ninfo);
-    scan_u32(b->d_doc_npiece, nd, b->d_scan_tmp, b->d_totals + 3, b->d_doc_piece_start, st);
-  }
-  const uint32_t pgrid = (uint32_t)((np + 3) / 4);
-  const uint32_t egrid = std::min(pgrid, norm_grid());
-  launch_unit_owner(b->d_doc_piece_start, nd, np, b->d_piece_doc, st, np_dev);
-  if (capcode == 2)
-    TM_LAUNCH(k_norm_emit2<false>, egrid, 256, 0, st, R, RB, RE, b->d_piece_doc, b->d_doc_piece_start, np, lower_all, nullptr,
-                                               b->d_need_host, b->d_piece_len, b->d_slab, ninfo + 3, b->d_two, np_dev);
-  else
-    TM_LAUNCH(k_norm_emit<3>, pgrid, 256, 0, st, R, RB, RE, b->d_piece_doc, b->d_doc_piece_start, np, capcode, lower_all,
-                                          nullptr, b->d_need_host, b->d_piece_len, nullptr, b->d_slab, ninfo + 3, b->d_two, np_dev);
-  TM_LAUNCH(k_norm_bad, (uint32_t)((std::max<uint64_t>(np, nd) + 255) / 256), 256, 0, st, b->d_piece_doc, b->d_need_host, b->d_doc_piece_start, np, nd, b->d_piece_len, ninfo, b->d_fb_ids, np_dev);
-  scan_u32(b->d_piece_len, np, b->d_scan_tmp, reinterpret_cast<uint64_t*>(ninfo + 5), b->d_piece_off, st);
-  TM_LAUNCH(k_norm_ranges_info, (nd + 255) / 256, 256, 0, st, b->d_piece_off, b->d_doc_piece_start, b->d_need_host, nd, b->d_nbegin, b->d_nend, ninfo, long_segs());
   launch_chunk_ctl(b, b->nseg, st);
   e = hipGetLastError();
   return e == hipSuccess ? TM_OK : hip_fail(e, "kernel launch");
@@ -1721,27 +1732,13 @@ int ring_enqueue_normalize(tm_batch* b, hipStream_t st, uint64_t seg_bound, cons
 // A raw piece is ONE document of the encoder's normalizer workspace.  piece_reserve grows every buffer the normalizer (and the filter pass in
 // front of it) takes for a piece of max_raw bytes, once, so that no later piece allocates; piece_device_bytes is what those buffers hold.
 int piece_reserve(tm_batch* b, uint64_t max_raw, hipStream_t st) {
-  const uint32_t norm_flag = b->vocab->host.norm_flag;
   int rc = raw_prepare(b, max_raw, 1, (max_raw + PIECE - 1) / PIECE, st);
-  if (rc != TM_OK) return rc;
-  if (!(norm_flag & ~3u)) return TM_OK;
-  hipError_t e;
-  if ((e = grow(&b->d_rawf, &b->rawf_cap, max_raw + (uint64_t)PF_GAP + 256)) != hipSuccess) return hip_fail(e, "hipMalloc (filtered text)");
-  if (!b->d_rawf_off) {
-    b->rawf_docs_cap = 17;
-    if ((e = hipMalloc((void**)&b->d_rawf_off, b->rawf_docs_cap * 16)) != hipSuccess || (e = hipMalloc((void**)&b->d_pf_doc, b->rawf_docs_cap * sizeof(PfDoc))) != hipSuccess)
-      return hip_fail(e, "hipMalloc (filtered documents)");
-  }
-  if (max_raw > PF_WHOLE) {
-    uint8_t* pp = (uint8_t*)b->d_pf_piece; uint64_t cap = b->pf_piece_cap;
-    if ((e = grow(&pp, &cap, (pf_spans(max_raw) + 1) * sizeof(PfPiece))) != hipSuccess) return hip_fail(e, "hipMalloc (filter pass)");
-    b->d_pf_piece = pp; b->pf_piece_cap = cap;
-  }
-  return TM_OK;
+  if (rc != TM_OK || !(b->vocab->host.norm_flag & ~3u)) return rc;
+  return prefilter_reserve(b, max_raw, 1, max_raw > PF_WHOLE ? pf_spans(max_raw) : 0);
 }
-uint64_t piece_device_bytes(const tm_batch* b) {
-  const uint64_t docs = (uint64_t)b->raw_docs_cap + 2;
-  uint64_t n = b->raw_cap + docs * 57 + 24 + 64 + NM_TABLE_BYTES + b->piece_cap * 21 + 8 + b->slab_cap;
+uint64_t piece_device_bytes(tm_batch* b) {
+  uint64_t n = b->raw_cap + 64 + NM_TABLE_BYTES + b->slab_cap;      // the raw text, the info words, the tables, the slabs
+  for (const NormArray& a : norm_arrays(b)) n += (norm_cap(b, a.per_piece) + (a.per_piece ? 0 : 2) + a.extra) * a.elem;
   if (b->d_rawf) n += b->rawf_cap + b->rawf_docs_cap * (16 + sizeof(PfDoc)) + b->pf_piece_cap;
   if (b->vocab->host.norm_flag & 4u) n += (uint64_t)NM_TWO_SIZE * 4;      // (the accent table: made by the first piece's filter pass)
   return n;

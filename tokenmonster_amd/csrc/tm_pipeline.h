@@ -205,7 +205,7 @@ struct tm_batch {
   // the filter pass of a vocabulary with byte-level normalization flags (tm_norm.hip: k_pf_*): the filtered text and its documents
   uint8_t* d_rawf = nullptr; uint64_t rawf_cap = 0;
   uint64_t* d_rawf_off = nullptr; uint64_t rawf_docs_cap = 0;
-  void* d_pf_piece = nullptr; uint64_t pf_piece_cap = 0;
+  uint8_t* d_pf_piece = nullptr; uint64_t pf_piece_cap = 0;      // (bytes of PfPiece)
   void* d_pf_doc = nullptr;
   uint32_t* d_acc = nullptr;             // what `accents` leaves of the two-byte characters
   uint8_t* d_slab = nullptr;            // normalizer: one 2 KiB slab per 1 KiB piece
@@ -381,7 +381,7 @@ constexpr uint64_t MAIL_BYTES = 4ull << 20, MAIL_MAX = 1ull << 20;
 int small_d2h(tm_batch* b, void* host_dst, const void* dev_src, uint64_t bytes, hipStream_t st);
 int small_h2d(tm_batch* b, void* dev_dst, const void* host_src, uint64_t bytes, hipStream_t st);
 int small_sync(tm_batch* b, hipStream_t st);
-// Grow-only buffers outside tm_batch::device_bytes (tm_kernels.hip): lanes, ring slots, document slots, the decode arenas.  A buffer of at least `need` bytes
+// Grow-only buffers outside tm_batch::device_bytes (tm_kernels.hip): lanes, ring slots, document slots, the decode arenas, the normalizer's texts and staging.  A buffer of at least `need` bytes
 // stays; a smaller one is replaced by one of `alloc` bytes (the caller's headroom), and `what` names it in the [grow] line of TM_TRACE and in the
 // error message.  On failure the pointer is null and the capacity 0.
 bool is_pinned(const void* p);      // page-locked host memory (hipHostMalloc / hipHostRegister)
@@ -400,7 +400,9 @@ void launch_serialize(const uint32_t* ids, uint64_t n, uint32_t enc, uint8_t* ou
 constexpr uint32_t RING_HOST_DOCS = 1, RING_LONG_DOCS = 2, RING_UNDECIDED = 4, RING_SLAB = 8, RING_SHORT_PIECE = 16, RING_BYTES = 32, RING_SEGS = 64,
                    RING_ERROR = 128, RING_OUT_CAP = 256;      // status bits of a chunk the ring hands to the exact path instead
 bool ring_supported(const tm_vocab* v);
+uint64_t raw_piece_count(const tm_vocab* v, const uint64_t* offsets, uint32_t ndocs);      // the 1 KiB pieces of these raw documents, as raw_prepare wants them counted
 int raw_prepare(tm_batch* b, uint64_t nbytes, uint32_t ndocs, uint64_t npieces, hipStream_t st);      // the buffers tm_batch_upload_raw fills, grown to size
+void raw_free(tm_batch* b);      // ... and freed, with the filter pass's (tm_batch_free)
 int ring_enqueue_normalize(tm_batch* b, hipStream_t st, uint64_t seg_bound, const uint64_t* h_raw_off);      // h_raw_off: the chunk's document offsets on the host (ndocs + 1)
 void launch_chunk_ctl(tm_batch* b, uint64_t seg_bound, hipStream_t st);
 // K0 .. K4, the ids packed to `enc` bytes into d_bytes (16-byte aligned), and the chunk's verdict written to `h_status` (page-locked host memory, 8 words:
@@ -460,7 +462,7 @@ int batch_upload_raw_on(tm_batch* b, const uint8_t* raw, const uint64_t* raw_off
 // launch_enc_pack (k_enc_pack) copies a range of them to `dst`, device to device
 int make_piece_workspace(const tm_vocab* v, uint64_t max_bytes, hipStream_t st, tm_batch** out);
 int piece_reserve(tm_batch* b, uint64_t max_raw, hipStream_t st);
-uint64_t piece_device_bytes(const tm_batch* b);
+uint64_t piece_device_bytes(tm_batch* b);
 int piece_normalize_on(tm_batch* b, hipStream_t st);
 void launch_enc_pack(const tm_batch* b, uint64_t from, uint64_t n, uint8_t* dst, hipStream_t st);
 // tm_normalize.cpp
