@@ -351,6 +351,89 @@ func (b *HipBatch) WindowsSpansIn(how HipCollate, overlap uint32, stream unsafe.
 	return 0, err
 }
 
+// ---- text pairs: two documents of one run in a row, [bos] A [sep] B [eos] (tm_batch_pair and its companions) ---------------------------------------
+const (
+	PairLongestFirst uint32 = 0 // TM_PAIR_LONGEST_FIRST
+	PairOnlyFirst    uint32 = 1 // TM_PAIR_ONLY_FIRST
+	PairOnlySecond   uint32 = 2 // TM_PAIR_ONLY_SECOND
+)
+
+// HipPair is tm_pair: pair p is (document FirstA + p, document FirstB + p) of the last run; the row length, the width of an id, the special
+// ids (HipNone: none), SepCount copies of Sep between the sides (1 or 2; 0 without Sep) and the truncation (Pair*).
+type HipPair struct {
+	FirstA, FirstB, Pairs uint32
+	RowLen, IdBytes       uint32
+	Pad, Bos, Sep, Eos    uint32
+	SepCount, Truncation  uint32
+	PadLeft               bool
+}
+
+func (p HipPair) c() C.tm_pair {
+	var flags C.uint32_t
+	if p.PadLeft {
+		flags |= C.TM_COLLATE_PAD_LEFT
+	}
+	return C.tm_pair{first_a: C.uint32_t(p.FirstA), first_b: C.uint32_t(p.FirstB), npairs: C.uint32_t(p.Pairs), row_len: C.uint32_t(p.RowLen),
+		id_bytes: C.uint32_t(p.IdBytes), pad_id: C.uint32_t(p.Pad), bos_id: C.uint32_t(p.Bos), sep_id: C.uint32_t(p.Sep), eos_id: C.uint32_t(p.Eos),
+		sep_count: C.uint32_t(p.SepCount), truncation: C.uint32_t(p.Truncation), flags: flags}
+}
+
+// Pair lays one pair out per row: ids[Pairs * RowLen] of IdBytes each; mask and types (each may be nil) a byte per id - types is 1 on B's ids
+// and on EOS -; kept (may be nil) two uint32 per row, the ids kept of A and of B (tm_batch_pair).
+func (b *HipBatch) Pair(how HipPair, stream, ids, mask, types, kept unsafe.Pointer) error {
+	h := how.c()
+	_, err := locked(func() C.int {
+		return C.tm_batch_pair(b.h, &h, stream, ids, (*C.uint8_t)(mask), (*C.uint8_t)(types), (*C.uint32_t)(kept))
+	})
+	return err
+}
+
+// PairSpansIn is the companion of Pair: spans [Pairs, RowLen, 2] elements of spanBytes 4 or 8, the pair of every content column counted in
+// `unit` from its own document's start in `text`, (0, 0) on specials and padding (tm_batch_pair_spans_in).
+func (b *HipBatch) PairSpansIn(how HipPair, stream unsafe.Pointer, text, unit uint32, spans unsafe.Pointer, spanBytes uint32) error {
+	h := how.c()
+	_, err := locked(func() C.int {
+		return C.tm_batch_pair_spans_in(b.h, &h, stream, C.uint32_t(text), C.uint32_t(unit), spans, C.uint32_t(spanBytes))
+	})
+	return err
+}
+
+// PairWindowRows is the number of rows PairWindows writes (tm_batch_pair_window_rows).
+func (b *HipBatch) PairWindowRows(how HipPair, overlap, maxFirst uint32) (uint64, error) {
+	h := how.c()
+	var rows C.uint64_t
+	_, err := locked(func() C.int { return C.tm_batch_pair_window_rows(b.h, &h, C.uint32_t(overlap), C.uint32_t(maxFirst), &rows) })
+	return uint64(rows), err
+}
+
+// PairWindows is the QA form: A, cut to maxFirst ids, stands in every row of its pair and B slides with `overlap` ids shared between rows.
+// ids, mask, types as for Pair; kept two uint32 per row, rowPair - the row's pair - and rowStart - the index inside B of the row's first id
+// of B - a uint32 per row, each may be nil (tm_batch_pair_windows).  With rowsCap too small nothing is written and the rows needed are returned.
+func (b *HipBatch) PairWindows(how HipPair, overlap, maxFirst uint32, stream unsafe.Pointer, rowsCap uint64, ids, mask, types, kept, rowPair, rowStart unsafe.Pointer) (uint64, error) {
+	h := how.c()
+	rc, err := locked(func() C.int {
+		return C.tm_batch_pair_windows(b.h, &h, C.uint32_t(overlap), C.uint32_t(maxFirst), stream, C.uint64_t(rowsCap), ids, (*C.uint8_t)(mask), (*C.uint8_t)(types),
+			(*C.uint32_t)(kept), (*C.uint32_t)(rowPair), (*C.uint32_t)(rowStart))
+	})
+	if err == nil && rc == C.TM_E_NOSPACE {
+		return b.PairWindowRows(how, overlap, maxFirst)
+	}
+	return 0, err
+}
+
+// PairWindowsSpansIn is the companion of PairWindows (tm_batch_pair_windows_spans_in).
+func (b *HipBatch) PairWindowsSpansIn(how HipPair, overlap, maxFirst uint32, stream unsafe.Pointer, rowsCap uint64, text, unit uint32, spans unsafe.Pointer, spanBytes uint32) (uint64, error) {
+	h := how.c()
+	rc, err := locked(func() C.int {
+		return C.tm_batch_pair_windows_spans_in(b.h, &h, C.uint32_t(overlap), C.uint32_t(maxFirst), stream, C.uint64_t(rowsCap), C.uint32_t(text), C.uint32_t(unit), spans,
+			C.uint32_t(spanBytes))
+	})
+	if err == nil && rc == C.TM_E_NOSPACE {
+		return b.PairWindowRows(how, overlap, maxFirst)
+	}
+	return 0, err
+}
+
 // HipUtf8Units is the unit rule on the host (tm_utf8_units): U(x), or D(x) with roundDown, of the byte offset x of doc in `unit`.
 func HipUtf8Units(doc []byte, unit uint32, x uint64, roundDown bool) uint64 {
 	var p *C.uint8_t

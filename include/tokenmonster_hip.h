@@ -460,6 +460,86 @@ int tm_tokenize_batch_spans_in(const tm_vocab* v, const uint8_t* docs, const uin
                                uint32_t text, uint32_t unit, uint32_t* tokens_out, uint64_t tokens_cap,
                                uint64_t* tok_offsets, uint32_t* spans_out, uint32_t* missing);
 
+/* ---- text pairs: two documents in one row, [bos] A [sep] B [eos] with token types (text_pair / truncation / stride of other tokenizers) ----- */
+/* The fourth layout: what rerankers, cross-encoders, NLI models and extractive QA read.  No counterpart in the reference.
+ * Sides:
+ *  - Both sides are documents of the same run: pair p is (document first_a + p, document first_b + p), p in 0..npairs.  The two ranges may
+ *    overlap or coincide.  A range that reaches beyond the run is TM_E_INVALID.
+ *  - A and B are tokenized as separate documents: no token spans the join.
+ * Row of pair p, with a and b the id counts of the two documents:
+ *  - ns is the number of specials: bos if given, plus sep_count, plus eos if given.  R = row_len - ns; row_len < ns is TM_E_INVALID.
+ *  - sep_count is 1 or 2 copies of sep_id between the sides, and 0 if and only if sep_id == TM_NONE; anything else is TM_E_INVALID.
+ *  - The row is [bos] A[0..a') [sep]*sep_count B[0..b') [eos], then pad_id up to row_len - on the left under TM_COLLATE_PAD_LEFT.
+ *  - Both sides keep their heads.  TM_COLLATE_KEEP_TAIL, or any other flag, is TM_E_INVALID.
+ * Kept counts (a', b').  If a + b <= R nothing is cut.  Otherwise:
+ *  - TM_PAIR_LONGEST_FIRST: remove one id at a time from the end of the side that is currently longer, from A on a tie, until
+ *    a' + b' == R.  (In closed form, with h = R / 2 rounded down, the first that applies: a <= h gives (a, R - a); b <= R - h gives
+ *    (R - b, b); otherwise (h, R - h).)
+ *  - TM_PAIR_ONLY_SECOND: a' = min(a, R) and b' = min(b, R - a').
+ *  - TM_PAIR_ONLY_FIRST: b' = min(b, R) and a' = min(a, R - b').
+ *  - Neither ONLY_* form ever fails per row (the device has nowhere to report a per-row error): the side that is not to be cut is cut when
+ *    it alone overflows the row.
+ *  - An unknown `truncation` is TM_E_INVALID. */
+#define TM_PAIR_LONGEST_FIRST 0u
+#define TM_PAIR_ONLY_FIRST    1u
+#define TM_PAIR_ONLY_SECOND   2u
+typedef struct tm_pair {
+  uint32_t first_a, first_b, npairs;   /* pair p = (document first_a + p, document first_b + p) of the last run */
+  uint32_t row_len, id_bytes;          /* L; 2, 4 or 8 */
+  uint32_t pad_id, bos_id, sep_id, eos_id;   /* TM_NONE: no such special (pad_id must be given) */
+  uint32_t sep_count;                  /* copies of sep_id between the sides: 1 or 2 (0 iff sep_id == TM_NONE) */
+  uint32_t truncation;                 /* TM_PAIR_* */
+  uint32_t flags;                      /* TM_COLLATE_PAD_LEFT only */
+} tm_pair;
+/* Outputs of tm_batch_pair.  EVERY element of every output is written: the caller passes uninitialized memory.  Pointers are device or
+ * page-locked, as for tm_batch_collate, with 16-byte stores between an unaligned head and tail; the call waits for the batch's last run
+ * and is then asynchronous on `stream` in the same way, and every argument error is TM_E_INVALID.
+ *  - ids_out[npairs * row_len] elements of id_bytes.
+ *  - mask_out (may be NULL) [npairs * row_len] bytes: 1 on an entry and 0 on padding.
+ *  - type_out (may be NULL) [npairs * row_len] bytes, the token_type_ids: 0 on bos, on A's ids and on the separators; 1 on B's ids and on
+ *    eos; 0 on padding.
+ *  - kept_out (may be NULL) uint32_t[npairs][2]: (a', b').  The row's entry count is ns + a' + b', and every column's role follows from
+ *    (a', b') and the specials given - hence there is no separate special-tokens mask.
+ *  - Two-byte ids follow the rule of tm_collate, with sep_id counted among the specials.
+ *  - More than 2^36 elements in one output is TM_E_LIMIT.  npairs == 0 is TM_OK and touches nothing. */
+int tm_batch_pair(tm_batch* b, const tm_pair* how, void* stream,
+                  void* ids_out, uint8_t* mask_out, uint8_t* type_out, uint32_t* kept_out);
+/* The spans of the ids laid out like the rows: spans_out[npairs * row_len * 2] elements of span_bytes 4 or 8, (begin, end) per column.  A
+ * content column gets exactly the pair tm_batch_spans_in(text, unit) gives for its id, so each side's offsets count from its OWN
+ * document's start; specials and padding get (0, 0).  The ragged pairs are produced first, on `stream`, into the batch's own buffer as for
+ * tm_batch_collate_spans_in, whose errors and stream remark apply unchanged: TM_TEXT_RAW on a batch without raw text, ids that came from
+ * tm_batch_load_ids and an unknown `text` or `unit` are TM_E_INVALID.  This is the one entry point: TM_TEXT_NORMALIZED with TM_UNIT_BYTES
+ * is the plain case. */
+int tm_batch_pair_spans_in(tm_batch* b, const tm_pair* how, void* stream, uint32_t text, uint32_t unit,
+                           void* spans_out, uint32_t span_bytes);
+/* Pair windows, the QA form: the question (A) stands in every row and the context (B) slides, every id of B kept.
+ *  - `truncation` must be TM_PAIR_ONLY_SECOND, else TM_E_INVALID.
+ *  - a' = min(a, max_first).  Per pair, room_p = R - a' ids of B per row and step_p = room_p - overlap.
+ *  - max_first > R, or R - max_first <= overlap, is TM_E_INVALID (checked on the host): every pair has step_p >= 1.
+ *  - Pair p yields w(b) rows with room_p and step_p, w as for tm_batch_windows: 1 if b <= room_p (an empty B too), else
+ *    1 + ceil((b - room_p) / step_p).
+ *  - Row k of pair p is [bos] A[0..a') [sep]*sep_count B[k * step_p .. min(k * step_p + room_p, b)) [eos] plus padding.
+ *  - Rows stand in pair order, then k.
+ * tm_batch_pair_window_rows: the rows that takes, counted on the device; synchronizes like tm_batch_window_rows.  tm_batch_pair_windows
+ * writes them: ids_out, mask_out and type_out as above with rows in place of npairs; kept_out (may be NULL) [rows][2]: (a', ids of B in
+ * this row); row_pair_out (may be NULL) [rows]: the pair of a row, counted from 0 (overflow_to_sample_mapping); row_start_out (may be
+ * NULL) [rows]: k * step_p, the index inside B of the row's first id of B.  rows_cap smaller than the rows needed: TM_E_NOSPACE, nothing is
+ * written, tm_last_error names the number (tm_batch_pair_window_rows returns it); more than 2^36 elements in one output: TM_E_LIMIT.
+ * tm_batch_pair_windows_spans_in: spans_out[rows * row_len * 2] as for tm_batch_pair_spans_in; B's offsets count from B's document start
+ * in every row.
+ * Streams: the counts per pair, their scan and the pair of every row live in the SAME buffers of the batch as those of tm_batch_windows.
+ * So the stricter stream rule of tm_batch_windows applies word for word, over the window calls of both kinds: every one of these three
+ * calls, tm_batch_pair_window_rows included, rewrites the rows per pair and their offsets on the stream of the batch's last run, and the
+ * fill calls rewrite the pair of every row (and the span form the ragged pairs) on `stream`, while a fill reads all of them on `stream`.
+ * Before the next window call of any kind on the batch, the last fill must have completed or have run on the stream of the batch's last
+ * run - passing that stream to every call is the simple way. */
+int tm_batch_pair_window_rows(tm_batch* b, const tm_pair* how, uint32_t overlap, uint32_t max_first, uint64_t* rows_needed);
+int tm_batch_pair_windows(tm_batch* b, const tm_pair* how, uint32_t overlap, uint32_t max_first, void* stream, uint64_t rows_cap,
+                          void* ids_out, uint8_t* mask_out, uint8_t* type_out, uint32_t* kept_out,
+                          uint32_t* row_pair_out, uint32_t* row_start_out);
+int tm_batch_pair_windows_spans_in(tm_batch* b, const tm_pair* how, uint32_t overlap, uint32_t max_first, void* stream,
+                                   uint64_t rows_cap, uint32_t text, uint32_t unit, void* spans_out, uint32_t span_bytes);
+
 /* Streaming Decoder (go/tokenmonster.go:552-700 NewDecoder / Decode / DecodeSerialized / Flush; server jobs 5-9): ids arrive a few
  * at a time, a call returns the text that is COMPLETE so far; the bytes of a character that is not (a token may end in the middle of a
  * UTF-8 sequence) and the state of the capcode decoder are carried to the next call.  Per-connection host state: the gather of a

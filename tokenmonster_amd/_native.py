@@ -16,6 +16,14 @@ TM_NUM_KERNELS = 5
 KIND_ENGLISH, KIND_ENGLISHCODE, KIND_CODE = 0, 1, 2
 TM_UNIT_BYTES, TM_UNIT_CODEPOINTS, TM_UNIT_UTF16 = 0, 1, 2
 TM_TEXT_NORMALIZED, TM_TEXT_RAW = 0, 1
+TM_PAIR_LONGEST_FIRST, TM_PAIR_ONLY_FIRST, TM_PAIR_ONLY_SECOND = 0, 1, 2
+
+
+class Pair(C.Structure):
+    """tm_pair"""
+    _fields_ = [(n, C.c_uint32) for n in ("first_a", "first_b", "npairs", "row_len", "id_bytes", "pad_id", "bos_id", "sep_id", "eos_id", "sep_count",
+                                          "truncation", "flags")]
+
 
 u8p = C.POINTER(C.c_uint8)
 u32p = C.POINTER(C.c_uint32)
@@ -99,6 +107,11 @@ SIGNATURES = {
     "tm_batch_collate_spans_in": (C.c_int, [vp, vp, vp, C.c_uint32, C.c_uint32, vp, C.c_uint32]),
     "tm_batch_windows_spans_in": (C.c_int, [vp, vp, C.c_uint32, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, C.c_uint32]),
     "tm_tokenize_batch_spans_in": (C.c_int, [vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_uint64, vp, vp, vp]),
+    "tm_batch_pair": (C.c_int, [vp, vp, vp, vp, vp, vp, vp]),
+    "tm_batch_pair_spans_in": (C.c_int, [vp, vp, vp, C.c_uint32, C.c_uint32, vp, C.c_uint32]),
+    "tm_batch_pair_window_rows": (C.c_int, [vp, vp, C.c_uint32, C.c_uint32, u64p]),
+    "tm_batch_pair_windows": (C.c_int, [vp, vp, C.c_uint32, C.c_uint32, vp, C.c_uint64, vp, vp, vp, vp, vp, vp]),
+    "tm_batch_pair_windows_spans_in": (C.c_int, [vp, vp, C.c_uint32, C.c_uint32, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, C.c_uint32]),
     "tm_decoder_new":(C.c_int, [vp, C.POINTER(vp)]),
     "tm_decoder_free": (None, [vp]),
     "tm_decoder_decode": (C.c_int, [vp, vp, C.c_uint64, vp, C.c_uint64, u64p]),

@@ -61,10 +61,9 @@ __global__ __launch_bounds__(256) void k_window_spans(WindowArgs a, Flat f, cons
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------------------------------
-// the batch's window buffer for nd documents: win_off[cap + 1] | block sums of the scan, its total behind them | windows per document
-struct WinBuf { uint64_t* win_off; uint64_t* sums; uint64_t* total; uint32_t* counts; };
+// the batch's window buffer for nd documents: win_off[cap + 1] | block sums of the scan, its total behind them | windows per document (WinBuf: tm_collate.h)
 static uint64_t win_sum_words(uint32_t cap) { return ((uint64_t)cap + 1 + SCAN_CH - 1) / SCAN_CH + 1; }
-static WinBuf win_buf(const tm_batch* b) {
+WinBuf win_buf(const tm_batch* b) {
   WinBuf w;
   w.win_off = reinterpret_cast<uint64_t*>(b->d_win);
   w.sums = w.win_off + (uint64_t)b->win_cap + 1;
@@ -72,7 +71,7 @@ static WinBuf win_buf(const tm_batch* b) {
   w.counts = reinterpret_cast<uint32_t*>(w.total + 1);
   return w;
 }
-static int win_reserve(tm_batch* b, uint32_t nd) {
+int win_reserve(tm_batch* b, uint32_t nd) {
   if (b->d_win && nd <= b->win_cap) return TM_OK;
   auto bytes = [](uint32_t cap) { return ((uint64_t)cap + 1 + win_sum_words(cap)) * 8 + (uint64_t)cap * 4; };
   const uint32_t cap = (uint32_t)std::min<uint64_t>((uint64_t)nd + nd / 4 + 1024, 0xFFFFFFFFull);
@@ -114,13 +113,17 @@ static int window_plan(tm_batch* b, const tm_collate* how, uint32_t overlap, con
 }
 
 // the document of every row into the batch's own buffer, on the stream of the fill behind it
-static int window_row_docs(tm_batch* b, WindowArgs* a, hipStream_t st) {
-  const int rc = grow_batch(b, (void**)&b->d_win_rows, &b->win_rows_cap, a->rows, a->rows + a->rows / 4 + 1024, 4, "window rows");
+int win_row_docs(tm_batch* b, const uint64_t* win_off, uint32_t nd, uint64_t rows, hipStream_t st) {
+  const int rc = grow_batch(b, (void**)&b->d_win_rows, &b->win_rows_cap, rows, rows + rows / 4 + 1024, 4, "window rows");
   if (rc != TM_OK) return rc;
   (void)hipGetLastError();
-  TM_LAUNCH(k_window_row_docs, grid_of(a->rows), 256, 0, st, a->win_off, a->nd, a->rows, b->d_win_rows);
-  a->row_doc = b->d_win_rows;
+  TM_LAUNCH(k_window_row_docs, grid_of(rows), 256, 0, st, win_off, nd, rows, b->d_win_rows);
   return launch_check();
+}
+static int window_row_docs(tm_batch* b, WindowArgs* a, hipStream_t st) {
+  const int rc = win_row_docs(b, a->win_off, a->nd, a->rows, st);
+  a->row_doc = b->d_win_rows;
+  return rc;
 }
 
 template <typename T>

@@ -1,8 +1,10 @@
 """Fixed-shape id tensors for code that lives beside this library in one PyTorch-ROCm process: text -> [rows, L] CUDA tensors and back,
-without an id crossing the host link (tm_batch_collate / tm_batch_windows / tm_batch_pack / tm_batch_load_ids, include/tokenmonster_hip.h).
+without an id crossing the host link (tm_batch_collate / tm_batch_windows / tm_batch_pair / tm_batch_pack / tm_batch_load_ids, include/tokenmonster_hip.h).
 
     encode_batch   one document per row: padded or truncated, BOS / EOS, attention mask, lengths
     encode_windows every id kept: a long document as several rows that overlap, with the row -> document map
+    encode_pairs   two documents per row, [bos] A [sep] B [eos]: pair truncation, token type ids
+    encode_pair_windows   the QA form: A in every row, B slides over several rows that overlap
     pack_batch     the pre-training form: one EOS-separated id stream cut into rows, with document numbers and positions
     decode_batch   a [rows, L] tensor of ids -> list of bytes
 
@@ -231,6 +233,118 @@ def encode_windows(vocab, docs, max_length, overlap, *, pad_id, bos_id=None, eos
             text = N.TM_TEXT_RAW if return_offsets == "raw" else N.TM_TEXT_NORMALIZED
             if rows:
                 N.check(N.lib.tm_batch_windows_spans_in(b, C.byref(how), overlap, st, rows, text, unit, spans.data_ptr(), 8))
+            res["offset_mapping"] = spans
+    return res
+
+
+_TRUNCATION = {"longest_first": N.TM_PAIR_LONGEST_FIRST, "only_first": N.TM_PAIR_ONLY_FIRST, "only_second": N.TM_PAIR_ONLY_SECOND}
+
+
+def _pair_args(torch, first, second, max_length, pad_id, bos_id, sep_id, sep_count, eos_id, truncation, pad_left, dtype, raw, return_offsets, offset_unit):
+    """the checks both pair calls share, every one before any device call -> (unit, id_bytes, dtype, room, tm_pair without its ranges)"""
+    unit = span_unit(offset_unit)
+    if isinstance(return_offsets, str):
+        if return_offsets != "raw":
+            raise ValueError("return_offsets %r: False, True or \"raw\"" % (return_offsets,))
+        if not raw:
+            raise ValueError("return_offsets=\"raw\" needs raw=True: normalized documents have no raw text to point into")
+    if len(first) != len(second):
+        raise ValueError("%d first and %d second documents: a pair takes one of each" % (len(first), len(second)))
+    if truncation not in _TRUNCATION:
+        raise ValueError("truncation %r: \"longest_first\", \"only_first\" or \"only_second\"" % (truncation,))
+    dtype = dtype or torch.int64
+    id_bytes = _check_dtype(torch, dtype)
+    sep_count = int(sep_count) if sep_id is not None else 0
+    if sep_id is not None and sep_count not in (1, 2):
+        raise ValueError("sep_count %d: 1 or 2" % sep_count)
+    max_length = int(max_length)
+    room = max_length - (bos_id is not None) - sep_count - (eos_id is not None)
+    if room < 0 or max_length < 1:
+        raise ValueError("max_length %d holds no row" % max_length)
+    how = N.Pair(0, 0, 0, max_length, id_bytes, int(pad_id), _special(bos_id), _special(sep_id), _special(eos_id), sep_count, _TRUNCATION[truncation],
+                 PAD_LEFT if pad_left else 0)
+    return unit, id_bytes, dtype, room, how
+
+
+def encode_pairs(vocab, first, second, max_length, *, pad_id, bos_id=None, sep_id=None, sep_count=1, eos_id=None, truncation="longest_first", pad_left=False, dtype=None,
+                 raw=True, device=None, return_offsets=False, offset_unit="bytes"):
+    """two lists of documents of equal length (bytes or str; raw=False: already normalized bytes) -> one pair per row, the text / text_pair
+    form of other tokenizers (tm_batch_pair): {"input_ids" [rows, max_length] of `dtype` (default int64), "attention_mask" [rows, max_length]
+    bool, "token_type_ids" [rows, max_length] uint8 - 0 on BOS, the first side and the separators, 1 on the second side and EOS, 0 on
+    padding; `.long()` for a model that wants int64 -, "kept" [rows, 2] int32 - the ids kept of either side}.  Row r is
+    [bos] first[r] [sep]*sep_count second[r] [eos] pad... (pad_left: the padding on the left); the two sides are tokenized as separate
+    documents.  truncation, when the two do not fit max_length less the specials: "longest_first" takes one id at a time from the end of
+    the longer side (from the first on a tie), "only_second" cuts the second side and "only_first" the first (the other one only where it
+    alone overflows the row).  sep_count: 1, or 2 for models that double the separator; ignored without sep_id.  return_offsets and
+    offset_unit as for encode_batch: "offset_mapping" [rows, max_length, 2] int64, each side's pairs counted from its own document's
+    start, (0, 0) on specials and padding (tm_batch_pair_spans_in).  With str documents, return_offsets="raw" and offset_unit="chars",
+    first[r][b:e] or second[r][b:e] - by token_type_ids - is the text of the id."""
+    torch = _torch()
+    unit, id_bytes, dtype, _, how = _pair_args(torch, first, second, max_length, pad_id, bos_id, sep_id, sep_count, eos_id, truncation, pad_left, dtype, raw, return_offsets,
+                                               offset_unit)
+    max_length = how.row_len
+    dev = _device(vocab, device)
+    with torch.cuda.device(dev):
+        st = _stream(dev)
+        b, nd = _tokenize(vocab, list(first) + list(second), raw, st)      # ONE batch: the first sides, then the second
+        n = nd // 2
+        how.first_a, how.first_b, how.npairs = 0, n, n
+        ids = torch.empty((n, max_length), dtype=dtype, device=dev)
+        mask = torch.empty((n, max_length), dtype=torch.uint8, device=dev)
+        types = torch.empty((n, max_length), dtype=torch.uint8, device=dev)
+        kept = torch.empty((n, 2), dtype=torch.int32, device=dev)
+        N.check(N.lib.tm_batch_pair(b, C.byref(how), st, ids.data_ptr(), mask.data_ptr(), types.data_ptr(), kept.data_ptr()))
+        res = {"input_ids": ids, "attention_mask": mask.view(torch.bool), "token_type_ids": types, "kept": kept}
+        if return_offsets:
+            spans = torch.empty((n, max_length, 2), dtype=torch.int64, device=dev)
+            text = N.TM_TEXT_RAW if return_offsets == "raw" else N.TM_TEXT_NORMALIZED
+            N.check(N.lib.tm_batch_pair_spans_in(b, C.byref(how), st, text, unit, spans.data_ptr(), 8))
+            res["offset_mapping"] = spans
+    return res
+
+
+def encode_pair_windows(vocab, first, second, max_length, overlap, max_first, *, pad_id, bos_id=None, sep_id=None, sep_count=1, eos_id=None, truncation="only_second",
+                        pad_left=False, dtype=None, raw=True, device=None, return_offsets=False, offset_unit="bytes"):
+    """the extractive-QA form of encode_pairs (tm_batch_pair_windows): the first side (the question), cut to max_first ids, stands in every
+    row of its pair, and every id of the second side (the context) is kept - a pair whose second side does not fit takes several rows, and
+    consecutive rows of a pair share `overlap` ids of it (stride / return_overflowing_tokens).  The keys of encode_pairs - "kept" [rows, 2]
+    holds the ids of the first side and those of the second in THIS row - and "overflow_to_sample_mapping" [rows] int32, the pair of a row,
+    and "window_start" [rows] int32, the index inside the second document of the row's first id of it.  Per pair the second side has
+    room = max_length - specials - min(ids of first, max_first) ids per row, rows are room - overlap ids apart; max_first + overlap must
+    be smaller than max_length less the specials.  truncation must be "only_second" (the default here).  "offset_mapping": the second
+    side's pairs count from its document's start in every row (tm_batch_pair_windows_spans_in)."""
+    torch = _torch()
+    unit, id_bytes, dtype, room, how = _pair_args(torch, first, second, max_length, pad_id, bos_id, sep_id, sep_count, eos_id, truncation, pad_left, dtype, raw, return_offsets,
+                                                  offset_unit)
+    if truncation != "only_second":
+        raise ValueError("truncation %r: pair windows cut the second side only (\"only_second\")" % (truncation,))
+    max_length, overlap, max_first = how.row_len, int(overlap), int(max_first)
+    if not 0 <= max_first <= room or overlap < 0 or room - max_first <= overlap:
+        raise ValueError("max_first %d and overlap %d: both >= 0 and max_first + overlap < %d (the ids a row holds beside the specials)" % (max_first, overlap, room))
+    dev = _device(vocab, device)
+    with torch.cuda.device(dev):
+        st = _stream(dev)
+        b, nd = _tokenize(vocab, list(first) + list(second), raw, st)
+        n = nd // 2
+        how.first_a, how.first_b, how.npairs = 0, n, n
+        rows = C.c_uint64()
+        N.check(N.lib.tm_batch_pair_window_rows(b, C.byref(how), overlap, max_first, C.byref(rows)))
+        rows = int(rows.value)
+        ids = torch.empty((rows, max_length), dtype=dtype, device=dev)
+        mask = torch.empty((rows, max_length), dtype=torch.uint8, device=dev)
+        types = torch.empty((rows, max_length), dtype=torch.uint8, device=dev)
+        kept = torch.empty((rows, 2), dtype=torch.int32, device=dev)
+        row_pair, row_start = (torch.empty((rows,), dtype=torch.int32, device=dev) for _ in range(2))
+        if rows:
+            N.check(N.lib.tm_batch_pair_windows(b, C.byref(how), overlap, max_first, st, rows, ids.data_ptr(), mask.data_ptr(), types.data_ptr(), kept.data_ptr(),
+                                                row_pair.data_ptr(), row_start.data_ptr()))
+        res = {"input_ids": ids, "attention_mask": mask.view(torch.bool), "token_type_ids": types, "kept": kept, "overflow_to_sample_mapping": row_pair,
+               "window_start": row_start}
+        if return_offsets:
+            spans = torch.empty((rows, max_length, 2), dtype=torch.int64, device=dev)
+            text = N.TM_TEXT_RAW if return_offsets == "raw" else N.TM_TEXT_NORMALIZED
+            if rows:
+                N.check(N.lib.tm_batch_pair_windows_spans_in(b, C.byref(how), overlap, max_first, st, rows, text, unit, spans.data_ptr(), 8))
             res["offset_mapping"] = spans
     return res
 

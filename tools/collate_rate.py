@@ -1,18 +1,20 @@
 """Rates of the layout kernels (tm_collate.hip) beside a device-to-device copy of the same byte count, in the same run:
 
-    python tools/collate_rate.py [--mib 256] [--out profiles/collate.txt]
+    python tools/collate_rate.py [--mib 256] [--out profiles/collate.txt] [--only pairs] [--append]
 
 collate at int64 and pack at uint16 (both L = 2048), windows at int64 beside a collate of the same output element count (L = 256 and L = 2048) and load_ids
-of the int64 rows, on the ids of a --mib MiB batch of the benchmark's
+of the int64 rows, and text pairs and pair windows at int64 and L = 512 beside a collate of the same output element count (the batch's documents paired
+first half against second half), on the ids of a --mib MiB batch of the benchmark's
 englishcode-32000 shape.  HIP events (torch's) around the launches on ONE stream; GB/s counts the bytes a call reads plus the bytes it writes;
 the yardstick is hipMemcpyAsync device to device of that many bytes (half read, half written), timed the same way.  Three warm-up calls, then
-the median of 20.  (tm_batch_collate / tm_batch_pack wait for the batch's last run before they launch and tm_batch_pack_rows fetches two
+the median of 20.  --only pairs: the pair lines alone; --append: add to --out under a dated heading instead of replacing it.  (tm_batch_collate / tm_batch_pack wait for the batch's last run before they launch and tm_batch_pack_rows fetches two
 offsets: host time, outside the kernels but inside the events - with 256 MiB of text it is a few percent of a call.)"""
 import argparse
 import ctypes as C
 import os
 import statistics
 import sys
+import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
@@ -42,6 +44,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mib", type=int, default=256)
     ap.add_argument("--out", default=os.path.join("profiles", "collate.txt"))
+    ap.add_argument("--only", choices=["pairs"], default=None)
+    ap.add_argument("--append", action="store_true")
     a = ap.parse_args()
     L = 2048
     v = Vocab(synth.config_vocab("englishcode-32000-consistent"))
@@ -57,7 +61,8 @@ def main():
     total = C.c_uint64()
     N.check(N.lib.tm_batch_totals(b, C.byref(total), None))
     n_ids, pad, eos = int(total.value), v.n_ids(), v.n_ids() + 1
-    lines = ["%d MiB of englishcode-32000 text, %d documents, %d ids, L = %d; median of 20 (min .. max), GB/s = bytes read + written" % (a.mib, nd, n_ids, L)]
+    lines = ["%d MiB of englishcode-32000 text, %d documents, %d ids, L = %s; median of 20 (min .. max), GB/s = bytes read + written" % (
+        a.mib, nd, n_ids, "512" if a.only == "pairs" else "%d (the pair lines: 512)" % L)]
 
     def copy_rate(nbytes):
         src = torch.empty(nbytes // 2, dtype=torch.uint8, device="cuda")
@@ -72,6 +77,79 @@ def main():
         lines.append("%-34s %8.3f ms (%.3f .. %.3f)  %7.1f GB/s | copy of %d MB: %8.3f ms %7.1f GB/s | ratio %.2f" % (name, med, lo, hi, gbs, nbytes >> 20, cmed, cgbs, gbs / cgbs))
         print(lines[-1], flush=True)
 
+    def pairs_lines():
+        """pairs and pair windows, int64, L = 512: document p against document nd / 2 + p.  Beside each a collate of the SAME output element count
+        with the outputs a collate has (ids, mask, a count per row), the pair fill once with exactly those (ids, mask, kept) and once with the
+        types too, and the copy yardstick of report().  A pair row's plan is four offset loads where a collate row's is two."""
+        LP, n = 512, nd // 2
+        pids = torch.empty((nd, LP), dtype=torch.int64, device="cuda")
+        pmask = torch.empty((nd, LP), dtype=torch.uint8, device="cuda")
+        ptype = torch.empty((nd, LP), dtype=torch.uint8, device="cuda")
+        pkept = torch.empty((nd, 2), dtype=torch.int32, device="cuda")
+        plens, prow, pstart = (torch.empty((nd,), dtype=torch.int32, device="cuda") for _ in range(3))
+        sep = eos + 1
+
+        def pair_how(k, trunc):
+            return N.Pair(0, n, k, LP, 8, pad, N.TM_NONE, sep, N.TM_NONE, 1, trunc, 0)
+
+        def collate_line(rows):
+            howc = torch_api._Collate(0, rows, LP, 8, pad, N.TM_NONE, N.TM_NONE, 0)
+            med, lo, hi = timed(lambda: N.check(N.lib.tm_batch_collate(b, C.byref(howc), st, pids.data_ptr(), pmask.data_ptr(), plens.data_ptr())), stream)
+            keptc = int(plens[:rows].to(torch.int64).sum().item())
+            report("collate int64, %d rows of %d" % (rows, LP), keptc * 4 + rows * LP * 9 + rows * 4, med, lo, hi)
+            lines.append("  (collate's spread over its 20 repetitions: %.3f ms)" % (hi - lo))
+            return med, hi - lo
+
+        cmed, spread = collate_line(n)
+        howp = pair_how(n, N.TM_PAIR_LONGEST_FIRST)
+        med, lo, hi = timed(lambda: N.check(N.lib.tm_batch_pair(b, C.byref(howp), st, pids.data_ptr(), pmask.data_ptr(), None, pkept.data_ptr())), stream)
+        keptp = int(pkept[:n].to(torch.int64).sum().item())
+        report("pairs int64 + mask + kept, %d rows" % n, keptp * 4 + n * LP * 9 + n * 8, med, lo, hi)
+        lines.append("  (pairs less collate at the same element count: %+.3f ms, collate's spread %.3f ms)" % (med - cmed, spread))
+        med, lo, hi = timed(lambda: N.check(N.lib.tm_batch_pair(b, C.byref(howp), st, pids.data_ptr(), pmask.data_ptr(), ptype.data_ptr(), pkept.data_ptr())), stream)
+        report("pairs int64 + mask + types + kept", keptp * 4 + n * LP * 10 + n * 8, med, lo, hi)
+        # pair windows: A cut to MF ids, OV ids of B shared between rows, over the first pairs whose windows make at most nd rows
+        OV, MF = 64, 64
+        need = C.c_uint64()
+
+        def pair_window_rows(k):
+            N.check(N.lib.tm_batch_pair_window_rows(b, C.byref(pair_how(k, N.TM_PAIR_ONLY_SECOND)), OV, MF, C.byref(need)))
+            return int(need.value)
+
+        lo_p, hi_p = 1, n
+        while lo_p < hi_p:
+            mid = (lo_p + hi_p + 1) // 2
+            lo_p, hi_p = (mid, hi_p) if pair_window_rows(mid) <= nd else (lo_p, mid - 1)
+        k, rw = lo_p, pair_window_rows(lo_p)
+        howw = pair_how(k, N.TM_PAIR_ONLY_SECOND)
+        cmed, spread = collate_line(rw)
+
+        def windows(types):
+            N.check(N.lib.tm_batch_pair_windows(b, C.byref(howw), OV, MF, st, rw, pids.data_ptr(), pmask.data_ptr(), types, pkept.data_ptr(), prow.data_ptr(), pstart.data_ptr()))
+
+        med, lo, hi = timed(lambda: windows(None), stream)
+        keptw = int(pkept[:rw].to(torch.int64).sum().item())
+        report("pair windows int64 + mask + kept + maps", keptw * 4 + rw * LP * 9 + rw * 16, med, lo, hi)
+        rmed, rlo, rhi = timed(lambda: pair_window_rows(k), stream)
+        lines.append("  pair_window_rows alone              %8.3f ms (%.3f .. %.3f)  -> row pairs + fill: %.3f ms; less collate: %+.3f ms, collate's spread %.3f ms" % (
+            rmed, rlo, rhi, med - rmed, med - rmed - cmed, spread))
+        med, lo, hi = timed(lambda: windows(ptype.data_ptr()), stream)
+        report("pair windows, the types too", keptw * 4 + rw * LP * 10 + rw * 16, med, lo, hi)
+        lines.append("(pair windows: %d pairs -> %d rows, max_first %d, overlap %d; a call = tm_batch_pair_window_rows' work, then the row pairs and the fill)" % (k, rw, MF, OV))
+
+    def write_out():
+        os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
+        with open(a.out, "a" if a.append else "w") as f:
+            if a.append:
+                f.write("\n==== %s: tools/collate_rate.py%s ====\n" % (time.strftime("%Y-%m-%d"), " --only " + a.only if a.only else ""))
+            f.write("\n".join(lines) + "\n")
+
+    if a.only == "pairs":
+        with torch.cuda.stream(stream):
+            pairs_lines()
+        N.lib.tm_batch_free(b)
+        write_out()
+        return
     with torch.cuda.stream(stream):
         # collate, int64: reads the ids a row keeps (at most L each), writes rows * L * (8 + 1) + rows * 4
         how = torch_api._Collate(0, nd, L, 8, pad, N.TM_NONE, N.TM_NONE, 0)
@@ -134,11 +212,10 @@ def main():
         N.check(N.lib.tm_batch_create(v.handle, 4096, nd, C.byref(b2)))
         med, lo, hi = timed(lambda: N.check(N.lib.tm_batch_load_ids(b2, ids.data_ptr(), nd, L, 8, lens.data_ptr(), pad, N.TM_NONE, N.TM_NONE, st)), stream)
         report("load_ids int64 rows", nd * L * 8 + kept * 12 + nd * 16, med, lo, hi)
+        pairs_lines()
     N.lib.tm_batch_free(b2)
     N.lib.tm_batch_free(b)
-    os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
-    with open(a.out, "w") as f:
-        f.write("\n".join(lines) + "\n")
+    write_out()
 
 
 if __name__ == "__main__":

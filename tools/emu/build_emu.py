@@ -11,7 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 CSRC = os.path.join(ROOT, "tokenmonster_amd", "csrc")
 LIB = os.path.join(HERE, "libtokenmonster_emu.so")
 BUILD = os.path.join(HERE, "build")
-SOURCES = ["tm_vocab.hip", "tm_kernels.hip", "tm_score.hip", "tm_norm.hip", "tm_decode.hip", "tm_collate.hip", "tm_spans.hip", "tm_units.hip", "tm_windows.hip", "tm_host.hip", "tm_decoder.hip", "tm_encoder.hip", "tm_document.hip", "tm_formats.hip", "tm_multi.hip",
+SOURCES = ["tm_vocab.hip", "tm_kernels.hip", "tm_score.hip", "tm_norm.hip", "tm_decode.hip", "tm_collate.hip", "tm_spans.hip", "tm_units.hip", "tm_windows.hip", "tm_pairs.hip", "tm_host.hip", "tm_decoder.hip", "tm_encoder.hip", "tm_document.hip", "tm_formats.hip", "tm_multi.hip",
            "tm_build.cpp", "tm_normalize.cpp"]
 
 

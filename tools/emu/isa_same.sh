@@ -12,17 +12,18 @@ REV=${1:-HEAD}
 OLD=$(mktemp -d) ; NEW=$(mktemp -d)
 trap 'rm -rf "$OLD" "$NEW"' EXIT
 git -C "$ROOT" archive "$REV" tokenmonster_amd/csrc include | tar -x -C "$OLD"
-UNITS="tm_kernels tm_norm tm_decode tm_spans tm_collate tm_windows tm_units"
+UNITS="tm_kernels tm_norm tm_decode tm_spans tm_collate tm_windows tm_pairs tm_units"
 for f in $UNITS; do
   ( cd "$OLD/tokenmonster_amd/csrc" && /opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -I ../../include -I . -x hip $f.hip --cuda-device-only -S -o "$OLD/$f.s" 2>/dev/null ) &
   ( cd "$ROOT/tokenmonster_amd/csrc" && /opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -I ../../include -I . -x hip $f.hip --cuda-device-only -S -o "$NEW/$f.s" 2>/dev/null ) &
 done
 wait
 python3 - "$OLD" "$NEW" $UNITS <<'EOF'
-import re, subprocess, sys
+import os, re, subprocess, sys
 
 def kernels(path):
-    """{symbol: (instructions, {metadata field: value})} of one assembly file"""
+    """{symbol: (instructions, {metadata field: value})} of one assembly file (none at all: the unit does not exist on that side)"""
+    if not os.path.exists(path): return {}
     lines = open(path).read().split("\n")
     out, meta, i = {}, {}, 0
     cur = {}
