@@ -14,7 +14,7 @@ LIB = os.path.join(HERE, "libtokenmonster_hip.so")
 SUPPORT_LIB = os.path.join(HERE, "libtm_testsupport.so")
 SUPPORT_SOURCES = [os.path.join(HERE, "testsupport", "tm_synth.cpp")]
 SOURCES = ["tm_vocab.hip", "tm_kernels.hip", "tm_score.hip", "tm_norm.hip", "tm_decode.hip", "tm_collate.hip", "tm_spans.hip", "tm_units.hip", "tm_windows.hip", "tm_pairs.hip", "tm_host.hip", "tm_decoder.hip", "tm_encoder.hip", "tm_document.hip", "tm_formats.hip", "tm_multi.hip", "tm_build.cpp", "tm_normalize.cpp"]
-HEADERS = ["tm_device.h", "tm_internal.h", "tm_tables.h", "tm_pipeline.h", "tm_cuts.h", "tm_collate.h", "tm_norm_masks.h", "../../include/tokenmonster_hip.h", "../../include/tm_build.h"]
+HEADERS = ["tm_device.h", "tm_internal.h", "tm_tables.h", "tm_pipeline.h", "tm_cuts.h", "tm_chunks.h", "tm_collate.h", "tm_norm_masks.h", "../../include/tokenmonster_hip.h", "../../include/tm_build.h"]
 
 
 def _hipcc():

@@ -219,23 +219,7 @@ int harvest(DocCall& c, DocSlot& s) {
   s.harvested = true;
   if (!s.computes) return TM_OK;
   tm_batch* b = s.ws;
-  hipError_t e = hipSuccess;
-  {
-    // (the verdict is a word in page-locked memory that the pass's last kernel writes: watched, with a look at the event now and then - a
-    // stream that has failed must not be waited for for ever; tm_host.hip's finisher does the same)
-    const volatile uint64_t* flag = s.h_status();
-    for (uint32_t spin = 1;; spin++) {
-      if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) != ~0ull) break;
-      if ((spin & 0xFFFu) == 0) {
-        const hipError_t q = hipEventQuery(s.comp_done);
-        if (q == hipSuccess) { if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == ~0ull) e = hipEventSynchronize(s.comp_done); break; }
-        if (q != hipErrorNotReady) { e = q; break; }
-      }
-#if defined(__x86_64__) || defined(__i386__)
-      __builtin_ia32_pause();
-#endif
-    }
-  }
+  hipError_t e = wait_verdict(s.h_status(), s.comp_done);      // (the word that the pass's last kernel writes, watched as the ring's finisher watches its chunks')
   if (e != hipSuccess) return hip_fail(e, "document piece");
   const uint64_t st = s.h_status()[0];
   if (st == ~0ull) return set_error(TM_E_INTERNAL, "a piece of the document ended without its verdict");

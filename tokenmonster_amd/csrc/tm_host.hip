@@ -25,6 +25,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <climits>
 #include <condition_variable>
 #include <cstring>
 #include <functional>
@@ -34,6 +35,7 @@
 #include <thread>
 #include <vector>
 
+#include "tm_chunks.h"
 #include "tm_pipeline.h"
 
 #ifndef TM_EMU
@@ -46,6 +48,14 @@ __attribute__((constructor)) static void tm_runtime_defaults() { (void)setenv("G
 #endif
 
 namespace tmh {
+
+// a tuning variable of the environment: its value where it lies in [lo, hi], the default where it does not or is not set (a call site that
+// reads it once keeps it in a static)
+static int env_int(const char* name, int lo, int hi, int dflt) {
+  const char* e = getenv(name);
+  const int v = e ? atoi(e) : dflt;
+  return e && v >= lo && v <= hi ? v : dflt;
+}
 
 struct Lane {
   hipStream_t stream = nullptr;
@@ -68,11 +78,6 @@ struct Lane {
 // ---- the host-to-host ring (tm_tokenize_pipeline on page-locked buffers) ---------------------------------------------------------------------
 // A slot = one chunk in flight: a workspace, the packed ids on the device, and a page-locked block for what goes to and comes from the host
 // beside the bulk data (the chunk's verdict, raw offsets in, id offsets and missing counts out).
-#if defined(__x86_64__) || defined(__i386__)
-#define TM_CPU_RELAX() __builtin_ia32_pause()
-#else
-#define TM_CPU_RELAX() ((void)0)
-#endif
 struct RingSlot {
   tm_batch* ws = nullptr;
   uint8_t* d_bytes = nullptr;
@@ -136,7 +141,7 @@ static LanePool* pool_of(const tm_vocab* v) {
   std::lock_guard<std::mutex> g(create_mu);
   if (!v->pool) {
     v->pool = new LanePool();
-    if (const char* e = getenv("TM_LANES")) { int n = atoi(e); if (n >= 1 && n <= 64) v->pool->max_lanes = (size_t)n; }
+    v->pool->max_lanes = (size_t)env_int("TM_LANES", 1, 64, (int)v->pool->max_lanes);
   }
   return v->pool;
 }
@@ -490,6 +495,15 @@ struct PipeCall {
     void local_offsets(uint64_t* lo) const { for (uint32_t d = 0; d <= nd; d++) lo[d] = off[d] - b0; }      // lo[nd + 1]: the documents' offsets counted from the chunk's first byte
   };
   Chunk chunk(size_t k) const { const uint32_t d0 = first[k], nd = first[k + 1] - d0; return Chunk{offsets + d0, d0, nd, offsets[d0], offsets[d0 + nd] - offsets[d0]}; }
+  // A chunk's place in the output, once the chain of counts has said that `base` ids lie before its `ntok`: the bytes of bytes_out that take its
+  // packed ids - none (bytes == 0) when it has no ids, or when they do not fit and the call ends with TM_E_NOSPACE - and its documents' byte
+  // offsets from their id offsets toff[nd + 1] within the chunk.  How the bytes get there is the caller's business (a lane's, the ring's).
+  struct Place { uint8_t* at; uint64_t bytes; };
+  Place place(uint64_t base, uint64_t ntok) const {
+    const bool fits = (base + ntok) * enc <= bytes_cap && bytes_out;
+    return fits ? Place{bytes_out + base * enc, ntok * enc} : Place{nullptr, 0};
+  }
+  void place_offsets(const Chunk& ch, uint64_t base, const uint64_t* toff) const { for (uint32_t d = 1; d <= ch.nd; d++) byte_offsets[ch.d0 + d] = (base + toff[d]) * enc; }
   // test hook 24 (tm_debug_flags, TM_TEST_FAIL="<place>:<chunk>[:<chunks>]"): ONE chunk of this call fails with TM_E_INPUT at a place of the
   // host code - an error return like any other, nothing on the device differs.  hook_place stays 0 in every call of a process without the hook.
   enum { HOOK_FINISHER = 1, HOOK_EXACT, HOOK_ISSUER, HOOK_DOWNLOAD };
@@ -539,29 +553,47 @@ static int chunk_deliver(PipeCall& c, Lane* l, size_t k, uint64_t ntok, bool dow
   if (!c.order(k, ntok, &base)) return TM_OK;          // publish this chunk's count, learn where its ids go
   if (t_ordered) *t_ordered = now_ms();
   tm_batch* b = l->ws;
-  const uint64_t out_b = ntok * c.enc;
+  const PipeCall::Place out = c.place(base, ntok);
   int rc = TM_OK;
   toff.resize((size_t)ch.nd + 1);
   if ((rc = small_d2h(b, toff.data(), b->d_tok_offsets, toff.size() * 8, l->stream)) != TM_OK) return rc;
   if (c.missing && ch.nd && (rc = small_d2h(b, c.missing + ch.d0, b->d_doc_missing, (uint64_t)ch.nd * 4, l->stream)) != TM_OK) return rc;
-  const bool fits = (base + ntok) * c.enc <= c.bytes_cap && c.bytes_out;
-  if (fits && out_b) {
+  if (out.bytes) {
     // (Writing the ids straight into the caller's page-locked buffer from the serialize kernel - no device staging, no copy command - was
     // built and timed in round 5: 42 - 45 ms per GiB call against 32 - 36 with the copy engine, profiles/r05_h2h.txt: stores of a kernel to
     // fine-grained host memory cross PCIe far below the engine's rate.  Removed.)
-    if ((rc = lane_dbytes(l, out_b)) != TM_OK) return rc;
+    if ((rc = lane_dbytes(l, out.bytes)) != TM_OK) return rc;
     launch_serialize(b->d_out, ntok, c.enc, l->d_bytes, l->stream);
-    if (c.out_pinned) rc = d2h(c.bytes_out + base * c.enc, l->d_bytes, out_b, l->stream, "D2H ids");
-    else if ((rc = lane_pinned(&l->h_stage, &l->h_cap, out_b)) == TM_OK) rc = d2h(l->h_stage, l->d_bytes, out_b, l->stream, "D2H ids");
+    if (c.out_pinned) rc = d2h(out.at, l->d_bytes, out.bytes, l->stream, "D2H ids");
+    else if ((rc = lane_pinned(&l->h_stage, &l->h_cap, out.bytes)) == TM_OK) rc = d2h(l->h_stage, l->d_bytes, out.bytes, l->stream, "D2H ids");
     if (rc != TM_OK) return rc;
   }
   if (download_hook && c.hook(PipeCall::HOOK_DOWNLOAD, k)) return PipeCall::hook_fail("download", k);
   if ((rc = small_sync(b, l->stream)) != TM_OK) return rc;
-  if (fits && out_b && !c.out_pinned) std::memcpy(c.bytes_out + base * c.enc, l->h_stage, out_b);
-  for (uint32_t d = 1; d <= ch.nd; d++) c.byte_offsets[ch.d0 + d] = (base + toff[d]) * c.enc;
+  if (out.bytes && !c.out_pinned) std::memcpy(out.at, l->h_stage, out.bytes);
+  c.place_offsets(ch, base, toff.data());
   if (c.stats) { std::lock_guard<std::mutex> g(c.mu); c.stats->host_fallback_docs += c.raw ? b->host_fallback_docs : 0; c.stats->normalized_bytes += b->nbytes; }
   *delivered = true;
   return TM_OK;
+}
+
+// Where an upload reads the chunk's text from: the caller's buffer when that is page-locked, else the lane's pinned input staging with the text
+// copied into it, so that the H2D runs at link speed
+static int chunk_text(const PipeCall& c, Lane* l, const PipeCall::Chunk& ch, const uint8_t** src) {
+  *src = c.text + ch.b0;
+  if (c.in_pinned) return TM_OK;
+  const int rc = lane_pinned(&l->h_stage_in, &l->h_in_cap, ch.nb);
+  if (rc != TM_OK) return rc;
+  std::memcpy(l->h_stage_in, *src, ch.nb);
+  *src = l->h_stage_in;
+  return TM_OK;
+}
+// A lane on its way back after the failure `rc`: nothing of the chunk is in flight when it gets there - no download into the caller's buffer, no
+// small transfer that would land in the failed thread's own arrays during a later call.  The failure's message outlives the wait.
+static void lane_quiet(Lane* l, int rc) {
+  const std::string msg = last_error();
+  if (l->ws) (void)small_sync(l->ws, l->stream); else (void)hipStreamSynchronize(l->stream);
+  set_error(rc, "%s", msg.c_str());
 }
 
 // One chunk through the exact path on a borrowed lane, start to finish (the ring's way out for a chunk its one-pass form does not take; no
@@ -573,24 +605,12 @@ static int chunk_exact(PipeCall& c, const tm_vocab* v, size_t k) {
   if (rc != TM_OK) return rc;
   std::vector<uint64_t> lo((size_t)ch.nd + 1), toff;
   ch.local_offsets(lo.data());
-  const uint8_t* src = c.text + ch.b0;
-  do {
-    if (!c.in_pinned) {
-      if ((rc = lane_pinned(&l->h_stage_in, &l->h_in_cap, ch.nb)) != TM_OK) break;
-      std::memcpy(l->h_stage_in, src, ch.nb);
-      src = l->h_stage_in;
-    }
-    RunOut ro;
-    if ((rc = lane_run(l, v, src, lo.data(), ch.nd, c.raw != 0, true, &ro)) != TM_OK) break;
-    if (c.hook(PipeCall::HOOK_EXACT, k)) { rc = PipeCall::hook_fail("exact", k); break; }
-    bool delivered = false;
-    rc = chunk_deliver(c, l, k, ro.total_tokens, false, toff, &delivered);
-  } while (false);
-  if (rc != TM_OK) {          // (nothing of the chunk in flight when the lane goes back, and no small transfer left that would land in `toff` later)
-    const std::string msg = last_error();
-    if (l->ws) (void)small_sync(l->ws, l->stream); else (void)hipStreamSynchronize(l->stream);
-    set_error(rc, "%s", msg.c_str());
-  }
+  const uint8_t* src = nullptr;
+  RunOut ro;
+  bool delivered = false;
+  if ((rc = chunk_text(c, l, ch, &src)) == TM_OK && (rc = lane_run(l, v, src, lo.data(), ch.nd, c.raw != 0, true, &ro)) == TM_OK)
+    rc = c.hook(PipeCall::HOOK_EXACT, k) ? PipeCall::hook_fail("exact", k) : chunk_deliver(c, l, k, ro.total_tokens, false, toff, &delivered);
+  if (rc != TM_OK) lane_quiet(l, rc);
   lane_release(v, l);
   return rc;
 }
@@ -623,7 +643,7 @@ static int ring_slot_size(RingSlot& s, const tm_vocab* v, uint64_t need_bytes, u
 
 static int pipeline_ring(PipeCall& c, const std::vector<Ring*>& rings) {
   static const bool trace = getenv("TM_TRACE") != nullptr;
-  static const uint32_t slack_pct = [] { const char* e = getenv("TM_RING_SLACK"); const int v = e ? atoi(e) : 0; return (uint32_t)(v >= 100 && v <= 400 ? v : 125); }();
+  static const uint32_t slack_pct = (uint32_t)env_int("TM_RING_SLACK", 100, 400, 125);
   // per device: a queue of issued chunks for the finisher, and the slots' states
   struct Dev {
     const tm_vocab* v; Ring* r;
@@ -633,6 +653,20 @@ static int pipeline_ring(PipeCall& c, const std::vector<Ring*>& rings) {
     bool issuer_done = false;
     std::vector<char> slot_free;
   };
+  // A slot in the finisher's hands.  The issuer may be waiting for it, so it goes back on EVERY way out: the lease's end gives it back, and the
+  // lease ends when its holder lets go of it (the chunk is complete, or runs on through the exact path, which needs no slot) or goes out of scope
+  // (the chunk failed, or is drained behind a failure).  A chunk whose download is enqueued takes its lease along into Pending.  A chunk issued
+  // for the exact path has no slot and no lease.
+  struct Lease {
+    Dev& dv; const int si;
+    Lease(Dev& d, int slot) : dv(d), si(slot) {}
+    Lease(const Lease&) = delete;
+    ~Lease() {
+      { std::lock_guard<std::mutex> g(dv.mu); dv.slot_free[si] = 1; }
+      dv.cv.notify_all();
+    }
+  };
+  typedef std::unique_ptr<Lease> Held;
   std::vector<std::unique_ptr<Dev>> devs;
   for (uint32_t i = 0; i < c.nv; i++) { auto d = std::make_unique<Dev>(); d->v = c.vs[i]; d->r = rings[i]; d->slot_free.assign(rings[i]->slots.size(), 1); devs.push_back(std::move(d)); }
 
@@ -654,10 +688,8 @@ static int pipeline_ring(PipeCall& c, const std::vector<Ring*>& rings) {
       const size_t k = c.next.fetch_add(1);
       if (k >= c.nchunks) break;
       const PipeCall::Chunk ch = c.chunk(k);
-      const uint32_t nd = ch.nd;
-      const uint64_t b0 = ch.b0, nb = ch.nb;
       int si = -1;
-      if (nb > 0) {
+      if (ch.nb > 0) {
         // a free slot (the finisher hands them back in order)
         std::unique_lock<std::mutex> lk(dv.mu);
         dv.cv.wait(lk, [&] { for (char f : dv.slot_free) if (f) return true; return c.failed(); });
@@ -674,17 +706,17 @@ static int pipeline_ring(PipeCall& c, const std::vector<Ring*>& rings) {
         hipError_t e = hipSuccess;
         const double ti0 = trace ? now_ms() : 0;
         enqueued = true;
-        if ((rc = raw_prepare(b, nb, nd, raw_piece_count(v, lo, nd), cs)) != TM_OK) break;
-        if ((e = hipMemcpyAsync(b->d_raw, c.text + b0, nb, hipMemcpyHostToDevice, r.up)) != hipSuccess ||
-            (e = hipMemcpyAsync(b->d_raw_off, lo, ((uint64_t)nd + 1) * 8, hipMemcpyHostToDevice, r.up)) != hipSuccess ||
+        if ((rc = raw_prepare(b, ch.nb, ch.nd, raw_piece_count(v, lo, ch.nd), cs)) != TM_OK) break;
+        if ((e = hipMemcpyAsync(b->d_raw, c.text + ch.b0, ch.nb, hipMemcpyHostToDevice, r.up)) != hipSuccess ||
+            (e = hipMemcpyAsync(b->d_raw_off, lo, ((uint64_t)ch.nd + 1) * 8, hipMemcpyHostToDevice, r.up)) != hipSuccess ||
             (e = hipEventRecord(s.up_done, r.up)) != hipSuccess || (e = hipStreamWaitEvent(cs, s.up_done, 0)) != hipSuccess) { rc = hip_fail(e, "ring upload"); break; }
         if (c.hook(PipeCall::HOOK_ISSUER, k)) { rc = PipeCall::hook_fail("issuer", k); break; }
-        const uint64_t seg_bound = (nb / 100 * slack_pct + 99) / SEG + nd + 1;
+        const uint64_t seg_bound = (ch.nb / 100 * slack_pct + 99) / SEG + ch.nd + 1;
         s.h_status()[0] = ~0ull;
         if ((rc = ring_enqueue_normalize(b, cs, seg_bound, lo)) != TM_OK) break;
         if ((rc = ring_enqueue_tokenize(b, cs, c.enc, s.d_bytes, s.d_bytes_cap, s.h_status(), &s.ids_at)) != TM_OK) break;
         if ((e = hipEventRecord(s.comp_done, cs)) != hipSuccess) { rc = hip_fail(e, "hipEventRecord"); break; }
-        if (trace) fprintf(stderr, "[ring] issue chunk %3zu (%5.1f MiB, %u docs) slot %d at %7.2f ms, %.3f ms of launches\n", k, nb / 1048576.0, nd, si, ti0 - c.t0, now_ms() - ti0);
+        if (trace) fprintf(stderr, "[ring] issue chunk %3zu (%5.1f MiB, %u docs) slot %d at %7.2f ms, %.3f ms of launches\n", k, ch.nb / 1048576.0, ch.nd, si, ti0 - c.t0, now_ms() - ti0);
         issued++;
       }
       { std::lock_guard<std::mutex> g(dv.mu); dv.queue.emplace_back(k, si); }
@@ -705,27 +737,60 @@ static int pipeline_ring(PipeCall& c, const std::vector<Ring*>& rings) {
     Ring& r = *dv.r;
     NearDevice near_gpu(v->device);
     int rc = enter_device(v);
-    struct Pending { size_t k; int si; uint64_t base, ntok; };
-    Pending prev{0, -1, 0, 0};
-    // a slot whose chunk goes no further (a failure, here or elsewhere) back to the issuer, which may be waiting for it
-    auto give_back = [&](int si) {
-      if (si < 0) return;
-      { std::lock_guard<std::mutex> g(dv.mu); dv.slot_free[si] = 1; }
-      dv.cv.notify_all();
-    };
-    // the downloads of a chunk are through: its offsets and counts to the caller, the slot back to the issuer
-    auto complete = [&](const Pending& p) -> int {
-      RingSlot& s = r.slots[p.si];
+    struct Pending { size_t k; uint64_t base; Held slot; };      // the chunk whose download is enqueued, with its slot
+    Pending prev{0, 0, nullptr};
+    // the downloads of a chunk are through: its offsets and counts to the caller, the slot back to the issuer (a failure leaves the slot with
+    // `p`: the issuers hear of the failure first)
+    auto complete = [&](Pending& p) -> int {
+      RingSlot& s = r.slots[p.slot->si];
       hipError_t e = hipEventSynchronize(s.dl_done);
       if (e != hipSuccess) return hip_fail(e, "hipEventSynchronize (ring download)");
-      const uint32_t d0 = c.first[p.k], nd = c.first[p.k + 1] - d0;
-      const uint64_t* toff = s.h_toff();
-      for (uint32_t d = 1; d <= nd; d++) c.byte_offsets[d0 + d] = (p.base + toff[d]) * c.enc;
-      if (c.missing && nd) std::memcpy(c.missing + d0, s.h_missing(), (size_t)nd * 4);
+      const PipeCall::Chunk ch = c.chunk(p.k);
+      c.place_offsets(ch, p.base, s.h_toff());
+      if (c.missing && ch.nd) std::memcpy(c.missing + ch.d0, s.h_missing(), (size_t)ch.nd * 4);
       if (c.stats) { std::lock_guard<std::mutex> g(c.mu); c.stats->normalized_bytes += s.h_status()[2]; }
-      { std::lock_guard<std::mutex> g(dv.mu); dv.slot_free[p.si] = 1; }
-      dv.cv.notify_all();
+      p.slot.reset();
       if (trace) fprintf(stderr, "[ring] chunk %3zu complete at %7.2f ms\n", p.k, now_ms() - c.t0);
+      return TM_OK;
+    };
+    // One issued chunk from its verdict to its enqueued download (or through the exact path); `slot` is the caller's, and stays the caller's on
+    // every way out but the last line, where the download owns it.  TM_OK without a download: another chunk has failed.
+    auto finish = [&](size_t k, Held& slot) -> int {
+      bool exact = !slot;
+      uint64_t ntok = 0;
+      if (slot) {
+        RingSlot& s = r.slots[slot->si];
+        // (the chunk's verdict: the issuer has set the word to ~0, the chunk's last kernel writes it, and the download stream waits for the
+        // event on the device)
+        const hipError_t e = wait_verdict(s.h_status(), s.comp_done);
+        if (e != hipSuccess) return hip_fail(e, "ring chunk");
+        if (c.hook(PipeCall::HOOK_FINISHER, k)) return PipeCall::hook_fail("finisher", k);
+        const uint64_t st = s.h_status()[0];
+        if (st == ~0ull) return set_error(TM_E_INTERNAL, "a chunk of the ring ended without its verdict");
+        if (trace) fprintf(stderr, "[ring] chunk %3zu computed at %7.2f ms: status %llu, %llu ids, %llu segments\n", k, now_ms() - c.t0, (unsigned long long)st,
+                           (unsigned long long)s.h_status()[1], (unsigned long long)s.h_status()[3]);
+        if (st != 0 || c.hook(PipeCall::HOOK_EXACT, k)) exact = true; else ntok = s.h_status()[1];
+      }
+      if (exact) {          // (on a borrowed lane: the slot is the issuer's again while the chunk runs there)
+        if (c.stats && slot) { std::lock_guard<std::mutex> g(c.mu); c.stats->ring_exact_chunks++; }
+        slot.reset();
+        return chunk_exact(c, v, k);
+      }
+      RingSlot& s = r.slots[slot->si];
+      uint64_t base = 0;
+      if (!c.order(k, ntok, &base)) return TM_OK;
+      const uint32_t nd = c.chunk(k).nd;
+      const PipeCall::Place out = c.place(base, ntok);
+      hipError_t e = hipStreamWaitEvent(r.down, s.comp_done, 0);
+      if (e == hipSuccess && out.bytes) e = hipMemcpyAsync(out.at, s.ids_at, out.bytes, hipMemcpyDeviceToHost, r.down);
+      if (e == hipSuccess) e = hipMemcpyAsync(s.h_toff(), s.ws->d_tok_offsets, ((uint64_t)nd + 1) * 8, hipMemcpyDeviceToHost, r.down);
+      if (e == hipSuccess && c.missing) e = hipMemcpyAsync(s.h_missing(), s.ws->d_doc_missing, (uint64_t)nd * 4, hipMemcpyDeviceToHost, r.down);
+      if (e == hipSuccess) e = hipEventRecord(s.dl_done, r.down);
+      if (e != hipSuccess) return hip_fail(e, "ring download");
+      // (a failure behind the enqueued download: r.down is waited for before the finisher leaves)
+      if (c.hook(PipeCall::HOOK_DOWNLOAD, k)) return PipeCall::hook_fail("download", k);
+      if (prev.slot) { const int rc = complete(prev); if (rc != TM_OK) return rc; }
+      prev = Pending{k, base, std::move(slot)};
       return TM_OK;
     };
     for (;;) {
@@ -734,67 +799,14 @@ static int pipeline_ring(PipeCall& c, const std::vector<Ring*>& rings) {
         dv.cv.wait(lk, [&] { return dv.qhead < dv.queue.size() || dv.issuer_done; });
         if (dv.qhead >= dv.queue.size()) break;
         item = dv.queue[dv.qhead++]; }
-      const size_t k = item.first;
-      const int si = item.second;
+      Held slot(item.second >= 0 ? new Lease(dv, item.second) : nullptr);
       if (rc != TM_OK || c.failed()) {              // (drain: whatever is in flight ends before the call returns)
-        if (si >= 0) (void)hipEventSynchronize(r.slots[si].comp_done);
-        give_back(si);
+        if (slot) (void)hipEventSynchronize(r.slots[slot->si].comp_done);
         continue;
       }
-      bool exact = si < 0;
-      uint64_t ntok = 0;
-      if (si >= 0) {
-        RingSlot& s = r.slots[si];
-        // The chunk's verdict is a word in page-locked memory that its last kernel writes (the issuer has set it to ~0): the finisher WATCHES it
-        // instead of sleeping in hipEventSynchronize - on some boxes every other call lost 3.2 ms right there, in the wait for its first chunk
-        // (gpurun_out/r06_probe25: every chunk of a 30.5 ms call lies 3.2 ms behind its place in a 26.9 ms call, from chunk 0 on).  The event
-        // is still asked now and then (a stream that has failed must not be waited for for ever), and the download stream waits for it on the device.
-        hipError_t e = hipSuccess;
-        {
-          const volatile uint64_t* flag = s.h_status();
-          for (uint32_t spin = 1;; spin++) {
-            if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) != ~0ull) break;
-            if ((spin & 0xFFFu) == 0) {
-              const hipError_t q = hipEventQuery(s.comp_done);
-              if (q == hipSuccess) { if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == ~0ull) e = hipEventSynchronize(s.comp_done); break; }
-              if (q != hipErrorNotReady) { e = q; break; }
-            }
-            TM_CPU_RELAX();
-          }
-        }
-        if (e != hipSuccess) { rc = hip_fail(e, "ring chunk"); fail_all(rc); give_back(si); continue; }
-        if (c.hook(PipeCall::HOOK_FINISHER, k)) { rc = PipeCall::hook_fail("finisher", k); fail_all(rc); give_back(si); continue; }
-        const uint64_t st = s.h_status()[0];
-        if (st == ~0ull) { rc = set_error(TM_E_INTERNAL, "a chunk of the ring ended without its verdict"); fail_all(rc); give_back(si); continue; }
-        if (trace) fprintf(stderr, "[ring] chunk %3zu computed at %7.2f ms: status %llu, %llu ids, %llu segments\n", k, now_ms() - c.t0, (unsigned long long)st,
-                           (unsigned long long)s.h_status()[1], (unsigned long long)s.h_status()[3]);
-        if (st != 0 || c.hook(PipeCall::HOOK_EXACT, k)) exact = true; else ntok = s.h_status()[1];
-      }
-      if (exact) {
-        if (si >= 0) { std::lock_guard<std::mutex> g(dv.mu); dv.slot_free[si] = 1; }
-        if (si >= 0) dv.cv.notify_all();
-        if (c.stats && si >= 0) { std::lock_guard<std::mutex> g(c.mu); c.stats->ring_exact_chunks++; }
-        if ((rc = chunk_exact(c, v, k)) != TM_OK) fail_all(rc);
-        continue;
-      }
-      RingSlot& s = r.slots[si];
-      uint64_t base = 0;
-      if (!c.order(k, ntok, &base)) { rc = TM_E_INTERNAL; give_back(si); continue; }
-      const uint32_t nd = c.first[k + 1] - c.first[k];
-      const uint64_t out_b = ntok * c.enc;
-      const bool fits = (base + ntok) * c.enc <= c.bytes_cap && c.bytes_out;
-      hipError_t e = hipStreamWaitEvent(r.down, s.comp_done, 0);
-      if (e == hipSuccess && fits && out_b) e = hipMemcpyAsync(c.bytes_out + base * c.enc, s.ids_at, out_b, hipMemcpyDeviceToHost, r.down);
-      if (e == hipSuccess) e = hipMemcpyAsync(s.h_toff(), s.ws->d_tok_offsets, ((uint64_t)nd + 1) * 8, hipMemcpyDeviceToHost, r.down);
-      if (e == hipSuccess && c.missing) e = hipMemcpyAsync(s.h_missing(), s.ws->d_doc_missing, (uint64_t)nd * 4, hipMemcpyDeviceToHost, r.down);
-      if (e == hipSuccess) e = hipEventRecord(s.dl_done, r.down);
-      if (e != hipSuccess) { rc = hip_fail(e, "ring download"); fail_all(rc); give_back(si); continue; }
-      // (a failure behind the enqueued download: r.down is waited for before the finisher leaves, `prev` below)
-      if (c.hook(PipeCall::HOOK_DOWNLOAD, k)) { rc = PipeCall::hook_fail("download", k); fail_all(rc); give_back(si); continue; }
-      if (prev.si >= 0 && (rc = complete(prev)) != TM_OK) { fail_all(rc); give_back(prev.si); give_back(si); prev.si = -1; continue; }
-      prev = Pending{k, si, base, ntok};
+      if ((rc = finish(item.first, slot)) != TM_OK) fail_all(rc);      // (everybody hears of it; then `slot` goes back, and the chunks behind this one are drained)
     }
-    if (prev.si >= 0) { if (rc == TM_OK && !c.failed()) { if ((rc = complete(prev)) != TM_OK) fail_all(rc); } else (void)hipEventSynchronize(r.slots[prev.si].dl_done); }
+    if (prev.slot) { if (rc == TM_OK && !c.failed()) { if ((rc = complete(prev)) != TM_OK) fail_all(rc); } else (void)hipEventSynchronize(r.slots[prev.slot->si].dl_done); }
     (void)hipStreamSynchronize(r.down);
   };
 
@@ -865,51 +877,18 @@ int tokenize_pipeline_on(const tm_vocab* const* vs, uint32_t nv, const uint8_t* 
   PipeCall c{vs, nv, text, offsets, ndocs, raw, encoding_length, chunk_bytes, lanes, bytes_out, bytes_cap, byte_offsets, missing, stats};
   c.in_pinned = is_pinned(text); c.out_pinned = is_pinned(bytes_out);
   // the ring: raw text, page-locked buffers on both sides, and a normalizer pass in the one-pass form
-  static const int ring_env = [] { const char* e = getenv("TM_RING"); return e ? atoi(e) : 1; }();
-  static const uint32_t ring_slots = [] { const char* e = getenv("TM_RING_SLOTS"); const int n = e ? atoi(e) : 0; return (uint32_t)(n >= 2 && n <= 16 ? n : 4); }();
-  static const uint32_t ring_streams = [] { const char* e = getenv("TM_RING_STREAMS"); const int n = e ? atoi(e) : 0; return (uint32_t)(n >= 1 && n <= 4 ? n : 2); }();
+  static const int ring_env = env_int("TM_RING", INT_MIN, INT_MAX, 1);
+  static const uint32_t ring_slots = (uint32_t)env_int("TM_RING_SLOTS", 2, 16, 4), ring_streams = (uint32_t)env_int("TM_RING_STREAMS", 1, 4, 2);
+  static const uint64_t ramp_pct = (uint64_t)env_int("TM_RING_RAMP", 110, 400, 150), ramp_first = (uint64_t)env_int("TM_RING_FIRST_KIB", 64, 1 << 20, 2048) << 10;
   bool use_ring = ring_env != 0 && raw && c.in_pinned && c.out_pinned && ndocs > 0;
   for (uint32_t i = 0; i < nv && use_ring; i++) use_ring = ring_supported(vs[i]);
   // (the ring's chunks: 48 MiB unless the caller says otherwise - every launch of the match kernel has a ramp and a tail of its own, 1 GiB in
   // 27.0 ms against 27.6 with 32 MiB chunks and 28.9 with 24; beyond 48 the first results come later for nothing, profiles/r06_h2h.txt)
   if (use_ring && chunk_default) c.chunk_bytes = chunk_bytes = 48ull << 20;
-  // chunks = maximal runs of whole documents of at most `limit` bytes (a longer document is a chunk of its own)
-  std::vector<uint32_t>& first = c.first;
   for (uint32_t d = 0; d < ndocs; d++) if (offsets[d + 1] < offsets[d]) return set_error(TM_E_INVALID, "offsets not monotone at document %u", d);
   const double t_entry = now_ms();
-  const size_t nramp = (size_t)lanes * nv;                          // the lanes' form: workers, if there are chunks enough
-  // The steady state of the pipeline runs near the device-resident rate; what it loses it loses at the two ends.
-  // Lanes' form: W workers that all begin with full chunks upload W chunks at once and then run their kernels in lock step, so the first W
-  // chunks grow geometrically - chunk_bytes / 2^W ... chunk_bytes / 2 - and the last ones shrink by 1 / W of what is left each.
-  // Ring: a chunk's kernels cannot begin before its upload has ended, and the link is only a fifth faster than the kernels (56 against 46 GB/s):
-  // behind a chunk of c bytes the next may have c x RAMP / 100 (default 1.5: 2, 3, 4.5 ... MiB) or the device waits for it; the tail halves
-  // (... 32, 16, 8, 4 MiB: what the end costs is the last chunk's kernels and download with nothing beside them).
-  static const uint64_t ramp_pct = [] { const char* e = getenv("TM_RING_RAMP"); const int v = e ? atoi(e) : 0; return (uint64_t)(v >= 110 && v <= 400 ? v : 150); }();
-  static const uint64_t ramp_first = [] { const char* e = getenv("TM_RING_FIRST_KIB"); const int v = e ? atoi(e) : 0; return (uint64_t)(v >= 64 && v <= (1 << 20) ? v : 2048) << 10; }();
-  uint64_t ring_limit = ramp_first;
-  for (uint32_t d = 0; d < ndocs;) {
-    first.push_back(d);
-    const size_t ci = first.size() - 1;                              // this chunk's number
-    const uint64_t left = offsets[ndocs] - offsets[d];
-    uint64_t limit = chunk_bytes;
-    if (use_ring) {
-      limit = std::min(chunk_bytes, ring_limit);
-      ring_limit = std::min<uint64_t>(chunk_bytes, ring_limit / 100 * ramp_pct);
-      if (left < 2 * (uint64_t)nv * chunk_bytes) limit = std::min(limit, std::max<uint64_t>(left / (2 * (uint64_t)nv), std::min<uint64_t>(chunk_bytes, 4u << 20)));
-    } else {
-      // (the shift count is clamped: 8 lanes on 8 devices - or on the virtual devices of a test - make nramp 64 and more)
-      if (ci < nramp) limit = std::max<uint64_t>(chunk_bytes >> std::min<size_t>(nramp - ci, 63), std::min<uint64_t>(chunk_bytes, 1u << 20));
-      // (the drain's shape - a floor of 2 / 4 / 8 / 16 MiB, a third or half of what is left instead of a quarter - was swept in round 5: every
-      // setting 30 - 37 ms per call, the same as this one: profiles/r05_h2h.txt)
-      if (left < (uint64_t)nramp * chunk_bytes) limit = std::min(limit, std::max<uint64_t>(left / nramp, std::min<uint64_t>(chunk_bytes, 2u << 20)));
-    }
-    // the last document that still ends within `limit` bytes of the chunk's first byte (at least one document)
-    const uint64_t* const lo = offsets + d + 1;
-    const uint64_t* const hi = std::upper_bound(lo, offsets + ndocs + 1, offsets[d] + limit);
-    d = std::max<uint32_t>(d + 1, (uint32_t)(hi - offsets) - 1);
-  }
-  first.push_back(ndocs);
-  c.nchunks = first.size() - 1;
+  chunk_layout(offsets, ndocs, nv, lanes, chunk_bytes, use_ring, ramp_first, ramp_pct, c.first);      // (tm_chunks.h: the ramp and the tail of every call)
+  c.nchunks = c.first.size() - 1;
   byte_offsets[0] = 0;
   if (stats) *stats = tm_pipeline_stats{};
   if (c.nchunks == 0) return TM_OK;
@@ -960,18 +939,10 @@ static int pipeline_lanes(PipeCall& c) {
       if (e == hipSuccess) e = hipEventCreateWithFlags(&l->up_done, hipEventDisableTiming);
       if (e != hipSuccess) rc = hip_fail(e, "hipStreamCreate (lane upload)");
     }
-    // the chunk with its offsets `lo` uploaded on `st` (through the pinned input staging when the caller's buffer is pageable, so that the
-    // H2D runs at link speed); *srcp = where the text was read from (for a retry)
+    // the chunk with its offsets `lo` uploaded on `st`; *srcp = where the text was read from (chunk_text; for a retry)
     auto upload = [&](const PipeCall::Chunk& ch, const std::vector<uint64_t>& lo, hipStream_t st, const uint8_t** srcp) -> int {
-      const uint8_t* src = c.text + ch.b0;
-      if (!c.in_pinned) {
-        int r = lane_pinned(&l->h_stage_in, &l->h_in_cap, ch.nb);
-        if (r != TM_OK) return r;
-        std::memcpy(l->h_stage_in, src, ch.nb);
-        src = l->h_stage_in;
-      }
-      *srcp = src;
-      return lane_upload(l, v, src, lo.data(), ch.nd, raw, st);
+      const int r = chunk_text(c, l, ch, srcp);
+      return r != TM_OK ? r : lane_upload(l, v, *srcp, lo.data(), ch.nd, raw, st);
     };
     size_t k = rc == TM_OK ? c.next.fetch_add(1) : c.nchunks;
     bool prefetched = false;
@@ -1024,8 +995,7 @@ static int pipeline_lanes(PipeCall& c) {
     }
     if (l && l->up_stream) (void)hipStreamSynchronize(l->up_stream);          // (an error may leave an upload in flight)
     if (rc != TM_OK) c.fail(rc);
-    // (... or a download into the caller's buffer, or small transfers into this thread's own arrays: they end here, not in a later call)
-    if (rc != TM_OK && l) { if (l->ws) (void)small_sync(l->ws, l->stream); else (void)hipStreamSynchronize(l->stream); }
+    if (rc != TM_OK && l) lane_quiet(l, rc);          // (... or a download, or small transfers into this thread's own arrays)
     if (l) lane_release(v, l);
   };
   std::vector<std::thread> th;

@@ -409,6 +409,27 @@ void launch_chunk_ctl(tm_batch* b, uint64_t seg_bound, hipStream_t st);
 // status bits, ids, normalized bytes, segments, device error word)
 // *ids_at: where the packed ids lie when the stream gets there - d_bytes, or the workspace's own id buffer (four-byte ids need no packing)
 int ring_enqueue_tokenize(tm_batch* b, hipStream_t st, uint32_t enc, uint8_t* d_bytes, uint64_t d_bytes_cap, uint64_t* h_status, const uint8_t** ids_at);
+// The wait for such a verdict (a chunk of the ring, a piece of tm_tokenize_document): a word in page-locked memory that the host has set to ~0
+// and the last kernel on the stream writes, `done` the event recorded behind that kernel.  The word is WATCHED instead of slept for in
+// hipEventSynchronize - on some boxes every other call lost 3.2 ms right there, in the wait for its first chunk (round 6's per-chunk
+// trace, tools/r06_probe25.sh: every chunk of a 30.5 ms call lies 3.2 ms behind its place in a 26.9 ms call, from chunk 0 on).  The event is still asked now and then: a stream
+// that has failed must not be waited for for ever.  hipSuccess with the word still ~0: the stream ended without writing it.
+#if defined(__x86_64__) || defined(__i386__)
+#define TM_CPU_RELAX() __builtin_ia32_pause()
+#else
+#define TM_CPU_RELAX() ((void)0)
+#endif
+inline hipError_t wait_verdict(const volatile uint64_t* flag, hipEvent_t done) {
+  for (uint32_t spin = 1;; spin++) {
+    if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) != ~0ull) return hipSuccess;
+    if ((spin & 0xFFFu) == 0) {
+      const hipError_t q = hipEventQuery(done);
+      if (q == hipSuccess) return __atomic_load_n(flag, __ATOMIC_ACQUIRE) == ~0ull ? hipEventSynchronize(done) : hipSuccess;
+      if (q != hipErrorNotReady) return q;
+    }
+    TM_CPU_RELAX();
+  }
+}
 // tm_decode.hip: the stages of a decode on a stream, in buffers of the caller
 constexpr uint64_t DEC_HOST = ~0ull;      // k_dec_capcode's length of a document it leaves to the host decoder (scripts beyond Latin, malformed UTF-8)
 // the arena of a decode behind `base` bytes of the caller's own: byte counts of the tiles of ids (tm_decode.hip) | first document of a tile | byte offset of a
