@@ -148,5 +148,15 @@ struct tm_vocab {
   // (Recorded at launch time, not at free time: by then the stream may have been destroyed by its owner.)
   mutable std::mutex use_mu;
   mutable std::vector<std::pair<hipStream_t, hipEvent_t>> last_use;
+  tm_vocab();                        // (tm_vocab.hip: every vocabulary that exists is on a list, for stream_destroy below)
+  ~tm_vocab();
+  tm_vocab(const tm_vocab&) = delete;
+  tm_vocab& operator=(const tm_vocab&) = delete;
 };
-namespace tmh { void note_table_use(const tm_vocab* v, hipStream_t st); }    // call AFTER the launch
+namespace tmh {
+void note_table_use(const tm_vocab* v, hipStream_t st);    // call AFTER the launch
+// hipStreamDestroy for every stream the library makes itself.  An event keeps a pointer to the stream it was last recorded on, and the runtime
+// reads the stream through it in hipEventSynchronize - freed memory once the stream is gone.  So every vocabulary first lets go of the event it
+// holds on this stream (waited for and destroyed while the stream exists); only events on a caller's own streams can outlive their stream.
+void stream_destroy(hipStream_t st);
+}  // namespace tmh

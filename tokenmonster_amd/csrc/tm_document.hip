@@ -89,15 +89,15 @@ void slot_destroy(DocSlot& s) {
   (void)hipFree(s.d_bytes);
   (void)hipHostFree(s.h_pin); (void)hipHostFree(s.h_in); (void)hipHostFree(s.h_out);
   for (hipEvent_t ev : {s.up_done, s.chain_done, s.comp_done, s.free_ev}) if (ev) (void)hipEventDestroy(ev);
-  if (s.comp) (void)hipStreamDestroy(s.comp);
+  if (s.comp) tmh::stream_destroy(s.comp);
   s = DocSlot();
 }
 void set_destroy(DocSet* d) {
   if (!d) return;
   for (DocSlot& s : d->slots) slot_destroy(s);
   (void)hipFree(d->d_cell);
-  if (d->up) (void)hipStreamDestroy(d->up);
-  if (d->down) (void)hipStreamDestroy(d->down);
+  if (d->up) tmh::stream_destroy(d->up);
+  if (d->down) tmh::stream_destroy(d->down);
   delete d;
 }
 

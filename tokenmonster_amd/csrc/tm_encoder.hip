@@ -246,7 +246,7 @@ void tm_encoder_free(tm_encoder* e) {
   tm_batch_free(e->ws);
   tm_batch_free(e->nws);
   (void)hipFree(e->d_small);
-  if (e->stream) (void)hipStreamDestroy(e->stream);
+  if (e->stream) tmh::stream_destroy(e->stream);
   delete e;
 }
 

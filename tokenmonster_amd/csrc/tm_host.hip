@@ -109,8 +109,8 @@ struct LanePool {
 static void lane_destroy(Lane* l) {
   if (!l) return;
   tm_batch_free(l->ws);
-  if (l->stream) (void)hipStreamDestroy(l->stream);
-  if (l->up_stream) (void)hipStreamDestroy(l->up_stream);
+  if (l->stream) tmh::stream_destroy(l->stream);
+  if (l->up_stream) tmh::stream_destroy(l->up_stream);
   if (l->up_done) (void)hipEventDestroy(l->up_done);
   (void)hipHostFree(l->h_stage);
   (void)hipHostFree(l->h_stage_in);
@@ -130,9 +130,9 @@ void pool_destroy(LanePool* p) {
     (void)hipHostFree(s.h_pin);
     for (hipEvent_t ev : {s.up_done, s.comp_done, s.dl_done}) if (ev) (void)hipEventDestroy(ev);
   }
-  for (hipStream_t st : r.comp) if (st) (void)hipStreamDestroy(st);
-  if (r.up) (void)hipStreamDestroy(r.up);
-  if (r.down) (void)hipStreamDestroy(r.down);
+  for (hipStream_t st : r.comp) if (st) tmh::stream_destroy(st);
+  if (r.up) tmh::stream_destroy(r.up);
+  if (r.down) tmh::stream_destroy(r.down);
   delete p;
 }
 

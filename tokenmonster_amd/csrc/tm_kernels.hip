@@ -2704,7 +2704,7 @@ void tm_batch_free(tm_batch* b) {
   for (void* p : ptrs) (void)hipFree(p);
   tmh::raw_free(b);                                    // the normalizer's and the filter pass's device buffers (tm_norm.hip)
   if (b->have_events) for (auto& ev : b->ev) (void)hipEventDestroy(ev);
-  if (b->aux_stream) (void)hipStreamDestroy(b->aux_stream);
+  if (b->aux_stream) tmh::stream_destroy(b->aux_stream);
   (void)hipHostFree(b->h_fb_raw); (void)hipHostFree(b->h_fb_norm); (void)hipHostFree(b->h_mail); (void)hipHostFree(b->h_groups);
   delete b;
 }

@@ -292,7 +292,7 @@ void tm_devices_close(tm_devices* g) {
 #endif
   for (size_t i = 0; i < g->dev.size(); i++) {
     (void)hipSetDevice(g->dev[i]);
-    if (g->stream[i]) (void)hipStreamDestroy(g->stream[i]);
+    if (g->stream[i]) tmh::stream_destroy(g->stream[i]);
     if (g->done[i]) (void)hipEventDestroy(g->done[i]);
     if (i < g->begun.size() && g->begun[i]) (void)hipEventDestroy(g->begun[i]);
     if (i < g->d_all_exits.size() && g->d_all_exits[i]) (void)hipFree(g->d_all_exits[i]);

@@ -197,7 +197,7 @@ void tm_dataset_free(tm_dataset* d) {
   tm_batch_free(d->ws);
   (void)hipFree(d->d_text); (void)hipFree(d->d_hist); (void)hipFree(d->d_tokens); (void)hipFree(d->d_missing_bits);
   (void)hipFree(d->d_vis); (void)hipFree(d->d_entry); (void)hipFree(d->d_exits);
-  if (d->stream) (void)hipStreamDestroy(d->stream);
+  if (d->stream) tmh::stream_destroy(d->stream);
   delete d;
 }
 

@@ -50,6 +50,44 @@ void note_table_use(const tm_vocab* v, hipStream_t st) {
   v->last_use.emplace_back(st, ev);
 }
 
+namespace {
+// the vocabularies that exist (never destroyed: a vocabulary may be freed as late as the exit of the process)
+struct LiveVocabs { std::mutex mu; std::vector<const tm_vocab*> all; };
+LiveVocabs& live_vocabs() { static LiveVocabs* l = new LiveVocabs(); return *l; }
+}  // namespace
+
+void stream_destroy(hipStream_t st) {
+  if (!st) return;
+  std::vector<hipEvent_t> held;
+  {
+    LiveVocabs& l = live_vocabs();
+    std::lock_guard<std::mutex> g(l.mu);
+    for (const tm_vocab* v : l.all) {
+      std::lock_guard<std::mutex> u(v->use_mu);
+      for (size_t k = 0; k < v->last_use.size(); k++)
+        if (v->last_use[k].first == st) { held.push_back(v->last_use[k].second); v->last_use.erase(v->last_use.begin() + (ptrdiff_t)k); break; }
+    }
+  }
+  for (hipEvent_t ev : held) { (void)hipEventSynchronize(ev); (void)hipEventDestroy(ev); }
+  if (!held.empty()) (void)hipGetLastError();
+  (void)hipStreamDestroy(st);
+}
+
+}  // namespace tmh
+
+tm_vocab::tm_vocab() {
+  auto& l = tmh::live_vocabs();
+  std::lock_guard<std::mutex> g(l.mu);
+  l.all.push_back(this);
+}
+tm_vocab::~tm_vocab() {
+  auto& l = tmh::live_vocabs();
+  std::lock_guard<std::mutex> g(l.mu);
+  l.all.erase(std::find(l.all.begin(), l.all.end(), this));
+}
+
+namespace tmh {
+
 int enter_device(const tm_vocab* v) {
   if (!v) return set_error(TM_E_INVALID, "null argument");
   int cur = -1;
