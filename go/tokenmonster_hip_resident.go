@@ -875,3 +875,41 @@ func (hv *HipVocab) CountNormalizedBatch(normalized [][]byte) ([]int, []int, err
 	}
 	return res, miss, nil
 }
+
+// ---- region labels: character ranges aligned to the ids on the device (tm_batch_region_labels) -------------------------------------------------
+
+// HipRegions are annotations on the documents of a batch's last run: Regions[nreg][3] (begin, end, label) and RegOffsets[ndocs + 1], both in
+// device or page-locked memory, counted in Unit of Text; ids that meet no region get IgnoreLabel (the rule: include/tokenmonster_hip.h).
+type HipRegions struct {
+	RegOffsets  unsafe.Pointer
+	Regions     unsafe.Pointer
+	Text, Unit  uint32
+	IgnoreLabel int32
+}
+
+func (r HipRegions) c() C.tm_regions {
+	return C.tm_regions{reg_offsets: (*C.uint64_t)(r.RegOffsets), regions: (*C.uint32_t)(r.Regions), text: C.uint32_t(r.Text), unit: C.uint32_t(r.Unit),
+		ignore_label: C.int32_t(r.IgnoreLabel)}
+}
+
+// RegionLabels writes one label of labelBytes (4 or 8, signed) per id of the run to `labels` (room for capIds), in the slot order of the ids;
+// regionTokens (may be nil) receives (first, last + 1) per region, bad (may be nil) the number of regions out of order.  Returns the documents
+// mapped on the host.
+func (b *HipBatch) RegionLabels(stream unsafe.Pointer, rg HipRegions, labels unsafe.Pointer, labelBytes uint32, capIds uint64, regionTokens, bad unsafe.Pointer) (uint32, error) {
+	var hostDocs C.uint32_t
+	r := rg.c()
+	_, err := locked(func() C.int {
+		return C.tm_batch_region_labels(b.h, stream, &r, labels, C.uint32_t(labelBytes), C.uint64_t(capIds), (*C.uint32_t)(regionTokens), (*C.uint32_t)(bad), &hostDocs)
+	})
+	return uint32(hostDocs), err
+}
+
+// CollateRegionLabels lays the labels out like Collate's rows for the same `how`: IgnoreLabel on BOS, EOS and padding.
+func (b *HipBatch) CollateRegionLabels(how HipCollate, stream unsafe.Pointer, rg HipRegions, labels unsafe.Pointer, labelBytes uint32, bad unsafe.Pointer) error {
+	h := how.c()
+	r := rg.c()
+	_, err := locked(func() C.int {
+		return C.tm_batch_collate_region_labels(b.h, &h, stream, &r, labels, C.uint32_t(labelBytes), (*C.uint32_t)(bad))
+	})
+	return err
+}

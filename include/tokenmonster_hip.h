@@ -460,6 +460,50 @@ int tm_tokenize_batch_spans_in(const tm_vocab* v, const uint8_t* docs, const uin
                                uint32_t text, uint32_t unit, uint32_t* tokens_out, uint64_t tokens_cap,
                                uint64_t* tok_offsets, uint32_t* spans_out, uint32_t* missing);
 
+/* ---- region labels: character ranges of the documents aligned to the ids (entities, answer spans, the parts of a loss mask) --------------- */
+/* What users of an offset mapping do next, done where the ids lie.  No counterpart in the reference.  Regions are annotations on the documents
+ * of the batch's last run, given in the `text` and `unit` of tm_batch_spans_in:
+ *  - regions[nreg][3] are uint32_t (begin, end, label); reg_offsets[ndocs + 1] is uint64_t: document d owns regions reg_offsets[d] ..
+ *    reg_offsets[d + 1].  Both arrays are device or page-locked memory (8- and 4-byte aligned).
+ *  - begin and end count from the document's start in `text` / `unit`.  label is an int32_t stored in the uint32_t slot: negative labels are allowed.
+ *  - Within a document the regions are sorted by begin and do not overlap: begin <= end and end(i) <= begin(i + 1).
+ *  - A region that reaches beyond the document's end is cut by it: begin and end become min(., the document's length in `unit`).
+ *  - An empty region (begin == end, after the cut) meets no id.  Otherwise an id with the pair (b, e) of tm_batch_spans_in(text, unit) MEETS the
+ *    region (rb, re) if
+ *      e > b:   b < re && rb < e;
+ *      e == b:  rb <= b && b < re      (forward-delete ids, steps that consume nothing).
+ *    The test is applied literally to the pairs as they are, outward rounding inside characters included.
+ *  - The id's label is that of the region with the lowest index in its document that it meets, or ignore_label (any int32_t) if it meets none.
+ *  - region_tokens_out[nreg][2] (may be NULL) receives per region (first, last + 1): the lowest and highest index, counted from the document's
+ *    first id, of the ids that meet it.  A token that lies across two regions counts for both.  No id: (0, 0).
+ *  - bad_out (may be NULL; device or page-locked) receives the number of regions that break the order rule: begin > end, or begin in front of
+ *    the end of the region before it in its document.  The labels and token ranges of such a document are unspecified, but every store stays
+ *    inside the outputs.  Nothing is validated on the host: the regions may live in device memory.
+ * tm_batch_region_labels: labels_out[labels_cap] elements of label_bytes (4 or 8, signed; device or page-locked, aligned to an element - on a
+ * 16-byte boundary four labels leave in one store), one per id in the slot order of tm_batch_device_tokens.  labels_cap smaller than the ids of the
+ * run: TM_E_NOSPACE, nothing is written.  host_docs (may be NULL) as tm_batch_spans_in.
+ * tm_batch_collate_region_labels: labels_out[ndocs * row_len] elements of label_bytes laid out like tm_batch_collate's rows for the same `how`
+ * (id_bytes is checked, not used): a content column holds the label of its id - head, TM_COLLATE_KEEP_TAIL and TM_COLLATE_PAD_LEFT exactly as for
+ * the ids -, BOS, EOS and padding columns ignore_label.  Every element is written.
+ * The pairs are produced first, on `stream`, into the batch's own buffer as for tm_batch_collate_spans_in; the documents' lengths, the token ranges
+ * under way and the ragged labels of the collated form live in a second grow-only buffer of the batch, counted in tm_batch_device_bytes.  Stream rules
+ * are those of tm_batch_spans_in / tm_batch_collate_spans_in; with region_tokens_out or bad_out the call reads reg_offsets[ndocs] back on `stream`
+ * and waits for it once.  A call changes nothing a later call reads - ids, offsets, totals stay as they are.
+ * TM_E_INVALID before any device work: a batch whose ids did not come from a walk, an unknown `text` or `unit`, TM_TEXT_RAW on a batch without raw
+ * text, label_bytes other than 4 or 8, a missing or misaligned array.
+ * Not offered for windows, text pairs and tm_batch_pack; overlapping or nested regions and B-/I- tagging are left to the caller
+ * (region_tokens_out gives the first token of every region). */
+typedef struct tm_regions {
+  const uint64_t* reg_offsets;
+  const uint32_t* regions;
+  uint32_t text, unit;         /* TM_TEXT_*, TM_UNIT_* */
+  int32_t ignore_label;
+} tm_regions;
+int tm_batch_region_labels(tm_batch* b, void* stream, const tm_regions* rg, void* labels_out, uint32_t label_bytes, uint64_t labels_cap,
+                           uint32_t* region_tokens_out, uint32_t* bad_out, uint32_t* host_docs);
+int tm_batch_collate_region_labels(tm_batch* b, const tm_collate* how, void* stream, const tm_regions* rg, void* labels_out,
+                                   uint32_t label_bytes, uint32_t* bad_out);
+
 /* ---- text pairs: two documents in one row, [bos] A [sep] B [eos] with token types (text_pair / truncation / stride of other tokenizers) ----- */
 /* The fourth layout: what rerankers, cross-encoders, NLI models and extractive QA read.  No counterpart in the reference.
  * Sides:

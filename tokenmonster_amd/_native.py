@@ -19,6 +19,11 @@ TM_TEXT_NORMALIZED, TM_TEXT_RAW = 0, 1
 TM_PAIR_LONGEST_FIRST, TM_PAIR_ONLY_FIRST, TM_PAIR_ONLY_SECOND = 0, 1, 2
 
 
+class Regions(C.Structure):
+    """tm_regions"""
+    _fields_ = [("reg_offsets", C.c_void_p), ("regions", C.c_void_p), ("text", C.c_uint32), ("unit", C.c_uint32), ("ignore_label", C.c_int32)]
+
+
 class Pair(C.Structure):
     """tm_pair"""
     _fields_ = [(n, C.c_uint32) for n in ("first_a", "first_b", "npairs", "row_len", "id_bytes", "pad_id", "bos_id", "sep_id", "eos_id", "sep_count",
@@ -107,6 +112,8 @@ SIGNATURES = {
     "tm_batch_collate_spans_in": (C.c_int, [vp, vp, vp, C.c_uint32, C.c_uint32, vp, C.c_uint32]),
     "tm_batch_windows_spans_in": (C.c_int, [vp, vp, C.c_uint32, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, C.c_uint32]),
     "tm_tokenize_batch_spans_in": (C.c_int, [vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_uint64, vp, vp, vp]),
+    "tm_batch_region_labels": (C.c_int, [vp, vp, vp, vp, C.c_uint32, C.c_uint64, vp, vp, u32p]),
+    "tm_batch_collate_region_labels": (C.c_int, [vp, vp, vp, vp, vp, C.c_uint32, vp]),
     "tm_batch_pair": (C.c_int, [vp, vp, vp, vp, vp, vp, vp]),
     "tm_batch_pair_spans_in": (C.c_int, [vp, vp, vp, C.c_uint32, C.c_uint32, vp, C.c_uint32]),
     "tm_batch_pair_window_rows": (C.c_int, [vp, vp, C.c_uint32, C.c_uint32, u64p]),

@@ -255,6 +255,8 @@ struct tm_batch {
   uint64_t units_cap[2] = {0, 0};       // ... in 256-byte blocks of text
   uint64_t units_blocks[2] = {0, 0};    // ... and the blocks of the text the planes were made for
   uint32_t units_have[2] = {0, 0};      // which planes hold the current text: bit 0 non-continuation bytes, bit 1 bytes >= 0xF0; 0 again wherever new text arrives (units_forget)
+  uint32_t* d_region = nullptr;         // tm_batch_region_labels: the documents' lengths in the regions' unit, the token ranges under way, the ragged labels of the collated form, grow-only (tm_regions.hip)
+  uint64_t region_cap = 0;              // ... in 4-byte words
   uint8_t* d_win = nullptr;             // tm_batch_windows: win_off[cap + 1] (u64) | the scan's block sums and total (u64) | windows per document (u32), grow-only (tm_windows.hip)
   uint32_t win_cap = 0;                 // ... in documents
   uint32_t* d_win_rows = nullptr;       // ... and the document of every row of the last window call, grow-only
@@ -368,11 +370,14 @@ int batch_raw_spans_on(tm_batch* b, hipStream_t st, void* out, uint64_t total, u
 // (kinds: bit 0 the normalized text, bit 1 the raw text).
 int units_args(uint32_t text, uint32_t unit, const char* who);
 int batch_spans_in_on(tm_batch* b, hipStream_t st, uint32_t text, uint32_t unit, void* out, uint64_t total, uint32_t* host_docs, float* ms);
+// ... and the length of every document of the run in `unit` of `text` into out[ndocs] (device memory) on `st`: for code points and UTF-16 units from the
+// index batch_spans_in_on has made for this text and unit (tm_regions.hip cuts the regions by it)
+int batch_doc_units_on(tm_batch* b, hipStream_t st, uint32_t text, uint32_t unit, uint32_t* out);
 inline void units_forget(tm_batch* b, uint32_t kinds) { if (kinds & 1u) b->units_have[0] = 0; if (kinds & 2u) b->units_have[1] = 0; }
 // tm_spans.hip: the bodies the span calls share (text: TM_TEXT_*, unit: TM_UNIT_*; `who` names the entry point).  batch_own_spans_on: the pairs
-// of `text` in `unit` into the batch's own buffer d_spans, grown for `total` pairs; ragged_spans_impl: tm_batch_spans, tm_batch_raw_spans(_timed)
+// of `text` in `unit` into the batch's own buffer d_spans, grown for `total` pairs (*host_docs, may be null: as tm_batch_spans_in); ragged_spans_impl: tm_batch_spans, tm_batch_raw_spans(_timed)
 // and tm_batch_spans_in; collate_spans_impl: tm_batch_collate_spans, tm_batch_collate_raw_spans and tm_batch_collate_spans_in
-int batch_own_spans_on(tm_batch* b, hipStream_t st, uint32_t text, uint32_t unit, uint64_t total);
+int batch_own_spans_on(tm_batch* b, hipStream_t st, uint32_t text, uint32_t unit, uint64_t total, uint32_t* host_docs = nullptr);
 int ragged_spans_impl(tm_batch* b, void* stream, uint32_t text, uint32_t unit, uint32_t* spans_out, uint64_t spans_cap, uint32_t* host_docs, float* ms, const char* who);
 int collate_spans_impl(tm_batch* b, const tm_collate* how, void* stream, uint32_t text, uint32_t unit, void* spans_out, uint32_t span_bytes, const char* who);
 // small device <-> host transfers that bypass the copy engines (tm_kernels.hip).  small_d2h's destination is filled by small_sync

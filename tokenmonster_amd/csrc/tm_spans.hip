@@ -297,9 +297,9 @@ int batch_raw_spans_on(tm_batch* b, hipStream_t st, void* out, uint64_t total, u
 
 // the ragged pairs of `text` into the batch's own buffer (the raw ones where the normalized ones lay), counted in `unit` (tm_units.hip): what the
 // collate and window fills and the one-shot span calls read
-int batch_own_spans_on(tm_batch* b, hipStream_t st, uint32_t text, uint32_t unit, uint64_t total) {
+int batch_own_spans_on(tm_batch* b, hipStream_t st, uint32_t text, uint32_t unit, uint64_t total, uint32_t* host_docs) {
   const int rc = spans_reserve(b, total);
-  return rc != TM_OK ? rc : batch_spans_in_on(b, st, text, unit, b->d_spans, total, nullptr, nullptr);
+  return rc != TM_OK ? rc : batch_spans_in_on(b, st, text, unit, b->d_spans, total, host_docs, nullptr);
 }
 
 template <typename T>

@@ -170,6 +170,25 @@ __global__ __launch_bounds__(256) void k_unit_spans(span_t* pairs, const uint64_
   }
 }
 
+// ---- k_unit_doc_len: the length of every document in the unit (what cuts a region, tm_regions.hip) --------------------------------------------------
+// A work-item per document: U at its end less U at its begin, each the prefix of its block plus a count over the part of the block in front of it
+// (UNIT: TM_UNIT_*; for bytes the plain difference, and nothing of the text or the index is read).
+template <uint32_t UNIT>
+__global__ __launch_bounds__(256) void k_unit_doc_len(const uint64_t* __restrict__ dbegin, const uint64_t* __restrict__ dend, uint32_t ndocs, const uint8_t* __restrict__ text,
+                                                      uint64_t n, const uint64_t* __restrict__ pre_cp, const uint64_t* __restrict__ pre_f0, uint32_t* __restrict__ out) {
+  constexpr bool F0 = UNIT == TM_UNIT_UTF16;
+  const uint32_t d = blockIdx.x * blockDim.x + threadIdx.x;
+  if (d >= ndocs) return;
+  if (UNIT == TM_UNIT_BYTES) { out[d] = (uint32_t)(dend[d] - dbegin[d]); return; }
+  auto U = [&](uint64_t p) {                          // p: an absolute position of the buffer, <= n
+    const uint64_t blk = p / UNIT_BLOCK;
+    const UnitCount c = count_range<F0>(text, blk * UNIT_BLOCK, p);
+    return pre_cp[blk] + (F0 ? pre_f0[blk] : 0ull) + c.nc + (F0 ? c.f0 : 0u);
+  };
+  const uint64_t d0 = std::min<uint64_t>(dbegin[d], n), d1 = std::min<uint64_t>(std::max<uint64_t>(dend[d], d0), n);
+  out[d] = (uint32_t)(U(d1) - U(d0));
+}
+
 // ---- host side ----------------------------------------------------------------------------------------------------------------------------------------
 // One plane of an index for `cap` blocks: pre[cap + 1] (u64, the scan's output: pre[k] = the count in front of block k) | the scan's block sums,
 // its total behind them (u64) | the counts (u32).  An index holds two planes: non-continuation bytes, bytes >= 0xF0.
@@ -246,6 +265,32 @@ static int batch_units_on(tm_batch* b, hipStream_t st, uint32_t text, uint32_t u
   (void)hipGetLastError();
   if (unit == TM_UNIT_UTF16) { const auto kern = k_unit_spans<true>; TM_LAUNCH(kern, grid_of(total), 256, 0, st, static_cast<span_t*>(pairs), b->d_tok_offsets, b->ndocs, dbegin, dend, buf, n, readable, aligned, cp.pre, f0.pre, total); }
   else { const auto kern = k_unit_spans<false>; TM_LAUNCH(kern, grid_of(total), 256, 0, st, static_cast<span_t*>(pairs), b->d_tok_offsets, b->ndocs, dbegin, dend, buf, n, readable, aligned, cp.pre, f0.pre, total); }
+  return launch_check();
+}
+
+// the documents' lengths in `unit` into out[ndocs]: the documents and the buffer as batch_units_on takes them, the index as it left it (made here
+// where a batch has not been asked for pairs of this text and unit yet)
+int batch_doc_units_on(tm_batch* b, hipStream_t st, uint32_t text, uint32_t unit, uint32_t* out) {
+  if (b->ndocs == 0) return TM_OK;
+  const int kind = text == TM_TEXT_RAW ? 1 : 0;
+  const uint64_t* dbegin = kind ? b->d_raw_off : b->d_doc_begin;
+  const uint64_t* dend = kind ? b->d_raw_off + 1 : b->d_doc_end;
+  const uint32_t grid = grid_of(b->ndocs);
+  if (unit == TM_UNIT_BYTES) {
+    (void)hipGetLastError();
+    const auto kern = k_unit_doc_len<TM_UNIT_BYTES>;
+    TM_LAUNCH(kern, grid, 256, 0, st, dbegin, dend, b->ndocs, (const uint8_t*)nullptr, 0ull, (const uint64_t*)nullptr, (const uint64_t*)nullptr, out);
+    return launch_check();
+  }
+  if (!kind) pack_text(b, st);
+  const uint8_t* buf = kind ? b->d_raw : b->d_text;
+  const uint64_t n = kind ? b->raw_bytes : b->nbytes;
+  const int rc = unit_index_on(b, st, kind, unit, buf, n);
+  if (rc != TM_OK) return rc;
+  const UnitPlane cp = unit_plane(b, kind, 0), f0 = unit_plane(b, kind, 1);
+  (void)hipGetLastError();
+  if (unit == TM_UNIT_UTF16) { const auto kern = k_unit_doc_len<TM_UNIT_UTF16>; TM_LAUNCH(kern, grid, 256, 0, st, dbegin, dend, b->ndocs, buf, n, cp.pre, f0.pre, out); }
+  else { const auto kern = k_unit_doc_len<TM_UNIT_CODEPOINTS>; TM_LAUNCH(kern, grid, 256, 0, st, dbegin, dend, b->ndocs, buf, n, cp.pre, f0.pre, out); }
   return launch_check();
 }
 

@@ -148,7 +148,7 @@ def _check_dtype(torch, dtype):
 
 
 def encode_batch(vocab, docs, max_length, *, pad_id, bos_id=None, eos_id=None, pad_left=False, keep_tail=False, dtype=None, raw=True, device=None, return_offsets=False,
-                 offset_unit="bytes"):
+                 offset_unit="bytes", regions=None, ignore_label=-100):
     """documents (bytes or str; raw=False: already normalized bytes) -> {"input_ids" [rows, max_length] of `dtype` (default int64),
     "attention_mask" [rows, max_length] bool, "lengths" [rows] int32}, CUDA tensors on the vocabulary's device.  Row r is
     [bos] ids [eos] pad...: the ids cut to max_length less the specials given (their head; keep_tail: their tail), the padding on the
@@ -157,7 +157,12 @@ def encode_batch(vocab, docs, max_length, *, pad_id, bos_id=None, eos_id=None, p
     makes of the document), and (0, 0) on BOS, EOS and padding (tm_batch_collate_spans).  return_offsets="raw" (with raw=True only): the same
     pairs counted in the bytes of the document as it was passed in (tm_batch_collate_raw_spans).  offset_unit "bytes" | "chars" | "utf16"
     (any return_offsets): what the pairs count - bytes, code points or UTF-16 units, by the rule of include/tokenmonster_hip.h
-    (tm_batch_collate_spans_in).  With str documents, return_offsets="raw" and offset_unit="chars", doc[b:e] is the text of the id."""
+    (tm_batch_collate_spans_in).  With str documents, return_offsets="raw" and offset_unit="chars", doc[b:e] is the text of the id.
+    regions=(regions, reg_offsets) adds "labels" [rows, max_length], int64 beside 8-byte ids and int32 otherwise: regions [R, 3] (begin, end,
+    label) counted in offset_unit from its document's start - in the document as passed in with raw=True, else in the normalized text -, sorted
+    and without overlap inside a document, reg_offsets [rows + 1]; both host arrays or tensors of the vocabulary's device (int64 / int32
+    regions, int64 offsets).  A column holds the label of the first region its id meets, ignore_label elsewhere and on BOS, EOS and padding
+    (tm_batch_collate_region_labels; the rule: include/tokenmonster_hip.h)."""
     unit = span_unit(offset_unit)
     if isinstance(return_offsets, str):
         if return_offsets != "raw":
@@ -185,6 +190,17 @@ def encode_batch(vocab, docs, max_length, *, pad_id, bos_id=None, eos_id=None, p
             text = N.TM_TEXT_RAW if return_offsets == "raw" else N.TM_TEXT_NORMALIZED
             N.check(N.lib.tm_batch_collate_spans_in(b, C.byref(how), st, text, unit, spans.data_ptr(), 8))
             res["offset_mapping"] = spans
+        if regions is not None:
+            # (int32 holds a region's three numbers as the library reads them: offsets are 32 bits, a label is an int32_t)
+            roff = torch.as_tensor(regions[1]).to(device=dev, dtype=torch.int64).contiguous()
+            reg = torch.as_tensor(regions[0]).to(device=dev, dtype=torch.int32).reshape(-1, 3).contiguous()
+            if roff.numel() != nd + 1:
+                raise ValueError("reg_offsets: %d entries for %d documents" % (roff.numel(), nd))
+            label_bytes = 8 if id_bytes == 8 else 4
+            labels = torch.empty((nd, max_length), dtype=torch.int64 if label_bytes == 8 else torch.int32, device=dev)
+            rg = N.Regions(roff.data_ptr(), reg.data_ptr(), N.TM_TEXT_RAW if raw else N.TM_TEXT_NORMALIZED, unit, int(ignore_label))
+            N.check(N.lib.tm_batch_collate_region_labels(b, C.byref(how), st, C.byref(rg), labels.data_ptr(), label_bytes, None))
+            res["labels"] = labels
     return res
 
 

@@ -247,6 +247,50 @@ class Vocab:
         finally:
             N.lib.tm_batch_free(b)
 
+    def tokenize_region_labels_packed(self, raw_text, raw_offsets, regions, reg_offsets, unit="chars", ignore_label=-100):
+        """RAW packed documents and regions on them -> (ids u32[T], tok_offsets u64[D+1], labels i32[T], region_tokens u32[R, 2]).  regions: [R, 3]
+        (begin, end, label) counted in `unit` from its document's start in the raw text, sorted and without overlap inside a document;
+        reg_offsets u64[D+1]: document d owns regions reg_offsets[d] .. reg_offsets[d + 1].  labels[k] is the label of the first region id k
+        meets, or ignore_label; region_tokens[r] = (first, last + 1) id of its document that meets region r, (0, 0) for none (the rule:
+        include/tokenmonster_hip.h; tm_batch_region_labels with TM_TEXT_RAW).  ValueError for regions out of order."""
+        unit = span_unit(unit)
+        raw_text = N.as_u8(raw_text)
+        raw_offsets = np.ascontiguousarray(raw_offsets, dtype=np.uint64)
+        nd = raw_offsets.size - 1
+        reg = np.ascontiguousarray(regions, dtype=np.int64).reshape(-1, 3)
+        roff = np.ascontiguousarray(reg_offsets, dtype=np.uint64)
+        if roff.size != nd + 1 or int(roff[nd]) != reg.shape[0]:
+            raise ValueError("reg_offsets: %d documents own %d regions" % (nd, reg.shape[0]))
+        nreg = reg.shape[0]
+        pin = PinnedBuffer(8 * (nd + 1) + 12 * max(nreg, 1))          # the offsets, then the regions (labels as their 32-bit patterns)
+        pin.array[:8 * (nd + 1)].view(np.uint64)[:] = roff
+        pin.array[8 * (nd + 1):8 * (nd + 1) + 12 * nreg].view(np.uint32)[:] = reg.astype(np.uint32).reshape(-1)
+        rg = N.Regions(pin.array.ctypes.data, pin.array.ctypes.data + 8 * (nd + 1), N.TM_TEXT_RAW, unit, int(ignore_label))
+        b = C.c_void_p()
+        N.check(N.lib.tm_batch_create(self._h, int(raw_text.size * 4 + 16 * nd + 1024), max(nd, 1), C.byref(b)))
+        try:
+            N.check(N.lib.tm_batch_upload_raw(b, N.ptr(raw_text), N.ptr(raw_offsets), nd))
+            N.check(N.lib.tm_batch_normalize(b, None))
+            N.check(N.lib.tm_batch_run(b, None))
+            n = C.c_uint64()
+            N.check(N.lib.tm_batch_totals(b, C.byref(n), None))
+            n = int(n.value)
+            ids = np.zeros(max(n, 1), dtype=np.uint32)
+            tok_off = np.zeros(nd + 1, dtype=np.uint64)
+            N.check(N.lib.tm_batch_download(b, N.ptr(ids), n, N.ptr(tok_off), None))
+            out = PinnedBuffer(16 + 4 * max(n, 1) + 8 * max(nreg, 1))     # the count of regions out of order, the labels, the token ranges
+            a = out.array.ctypes.data
+            out.array[:4] = 0                                                 # (a run without documents writes no count)
+            N.check(N.lib.tm_batch_region_labels(b, None, C.byref(rg), a + 16, 4, n, a + 16 + 4 * max(n, 1), a, None))
+            N.check(N.lib.tm_batch_totals(b, None, None))                     # (waits for the NULL stream)
+            if int(out.array[:4].view(np.uint32)[0]):
+                raise ValueError("%d regions out of order (sorted by begin, no overlap, begin <= end)" % int(out.array[:4].view(np.uint32)[0]))
+            labels = out.array[16:16 + 4 * n].view(np.int32).copy()
+            rtok = out.array[16 + 4 * max(n, 1):16 + 4 * max(n, 1) + 8 * nreg].view(np.uint32).reshape(nreg, 2).copy()
+            return ids[:n], tok_off, labels, rtok
+        finally:
+            N.lib.tm_batch_free(b)
+
     def tokenize_normalized(self, docs):
         """list of already-normalized documents -> list of uint32 arrays (Vocab.tokenize, go :1017)"""
         single = isinstance(docs, (bytes, bytearray, np.ndarray))

@@ -5,14 +5,15 @@
 # some: for every kernel that differs both sides are printed, `rev | tree` — vgpr_count, sgpr_count, group_segment_fixed_size (LDS),
 # private_segment_fixed_size (scratch), instructions (all, VALU, SALU) and the length, loop label to back branch, of every innermost loop that
 # reads and writes LDS: the straight-line loop of a chain walk (K4, the scoring and span walks) is one, and K4's time follows it
-# (profiles/r05_issue_model.txt).  Exit status 1 if any kernel differs.
+# (profiles/r05_issue_model.txt).  Exit status 1 if any kernel differs - a kernel that exists on one side only ("only in rev / tree") counts as a
+# difference, so against a revision from before a kernel or a whole unit was added the status is 1 although every older kernel is identical.
 set -e
 ROOT="$(cd "$(dirname "$0")/../.." && pwd)"
 REV=${1:-HEAD}
 OLD=$(mktemp -d) ; NEW=$(mktemp -d)
 trap 'rm -rf "$OLD" "$NEW"' EXIT
 git -C "$ROOT" archive "$REV" tokenmonster_amd/csrc include | tar -x -C "$OLD"
-UNITS="tm_kernels tm_norm tm_decode tm_spans tm_collate tm_windows tm_pairs tm_units"
+UNITS="tm_kernels tm_norm tm_decode tm_spans tm_collate tm_windows tm_pairs tm_units tm_regions"
 for f in $UNITS; do
   ( cd "$OLD/tokenmonster_amd/csrc" && /opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -I ../../include -I . -x hip $f.hip --cuda-device-only -S -o "$OLD/$f.s" 2>/dev/null ) &
   ( cd "$ROOT/tokenmonster_amd/csrc" && /opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -I ../../include -I . -x hip $f.hip --cuda-device-only -S -o "$NEW/$f.s" 2>/dev/null ) &
