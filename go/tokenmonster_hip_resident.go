@@ -410,6 +410,31 @@ func (b *HipBatch) Pack(how HipCollate, stream unsafe.Pointer, rowsCap uint64, i
 	return 0, err
 }
 
+// FitRows is the number of rows Fit writes for these documents: the documents packed whole into rows, in order, a row closed when the next
+// document does not fit (tm_batch_fit_rows).
+func (b *HipBatch) FitRows(how HipCollate) (uint64, error) {
+	h := how.c()
+	var rows C.uint64_t
+	_, err := locked(func() C.int { return C.tm_batch_fit_rows(b.h, &h, &rows) })
+	return uint64(rows), err
+}
+
+// Fit packs the documents whole into rows of RowLen; only a document longer than a row is cut.  ids[rows * RowLen] of IdBytes each; docIndex and
+// position (may be nil) a uint32 per id; lengths, rowDoc - the document of the row's first entry, counted from FirstDoc - and rowStart - that
+// entry's index inside its document - (each may be nil) a uint32 per row (tm_batch_fit).  With rowsCap too small nothing is written and the
+// rows needed are returned.
+func (b *HipBatch) Fit(how HipCollate, stream unsafe.Pointer, rowsCap uint64, ids, docIndex, position, lengths, rowDoc, rowStart unsafe.Pointer) (uint64, error) {
+	h := how.c()
+	rc, err := locked(func() C.int {
+		return C.tm_batch_fit(b.h, &h, stream, C.uint64_t(rowsCap), ids, (*C.uint32_t)(docIndex), (*C.uint32_t)(position), (*C.uint32_t)(lengths),
+			(*C.uint32_t)(rowDoc), (*C.uint32_t)(rowStart))
+	})
+	if err == nil && rc == C.TM_E_NOSPACE {
+		return b.FitRows(how)
+	}
+	return 0, err
+}
+
 // WindowRows is the number of rows Windows writes for these documents: a document longer than a row takes several rows, consecutive rows of a
 // document share `overlap` ids (tm_batch_window_rows).  KeepTail has no meaning here and is an error.
 func (b *HipBatch) WindowRows(how HipCollate, overlap uint32) (uint64, error) {

@@ -294,6 +294,43 @@ int tm_batch_collate(tm_batch* b, const tm_collate* how, void* stream,
 int tm_batch_pack_rows(tm_batch* b, const tm_collate* how, uint64_t* rows_needed);   /* synchronizes like tm_batch_totals */
 int tm_batch_pack(tm_batch* b, const tm_collate* how, void* stream, uint64_t rows_cap,
                   void* ids_out, uint32_t* doc_index_out, uint32_t* position_out);
+/* Whole-document packing, the fine-tuning form: the documents packed WHOLE into rows of row_len, in order; a row is closed when the next
+ * document does not fit, and only a document longer than a row is ever cut.  The same tm_collate as tm_batch_pack: bos_id and flags are
+ * not used, eos_id == TM_NONE means no separator.  Document d, counted from first_doc, has E_d = n_d + s entries, s = 1 if eos_id is
+ * given, else 0: its n_d ids followed by the separator, which is the document's last position n_d.
+ *     row = 0; fill = 0
+ *     for d in 0 .. ndocs - 1:
+ *         done = 0
+ *         while done < E_d:
+ *             take = min(E_d - done, row_len)
+ *             if fill + take > row_len: row += 1; fill = 0
+ *             entries done .. done + take - 1 of d go to columns fill .. fill + take - 1 of `row`
+ *             fill += take; done += take
+ *     rows = 0 if no document has an entry, else row + 1
+ *  - A document of at most row_len entries is never cut.
+ *  - A longer one begins a row of its own, unless nothing stands in front of it; it fills whole rows, and its remainder opens a row that
+ *    the following documents may share.
+ *  - An empty document without a separator leaves no trace.
+ *  - Every row holds at least one entry.  Rows stand in document order.
+ * tm_batch_fit_rows: the rows that takes - planned on the device (three kernels over the documents, in grow-only buffers of the batch
+ * alone, 20 bytes per document, counted in tm_batch_device_bytes), one number read back; synchronizes like tm_batch_pack_rows.
+ * tm_batch_fit does the same and then, on `stream`, writes the table of the rows (16 bytes per row in a second such buffer) and the rows:
+ * ids_out[rows * row_len] elements of id_bytes, pad_id behind a row's entries; doc_index_out (may be NULL) [rows * row_len] the entry's
+ * document, counted from first_doc, 0xFFFFFFFF on padding; position_out (may be NULL) [rows * row_len] its index inside the document, 0 on
+ * padding - a long document keeps counting across its rows; lengths_out (may be NULL) [rows] the entries of the row; row_doc_out (may be
+ * NULL) [rows] the document of the row's first entry; row_start_out (may be NULL) [rows] that entry's index inside its document.  Every
+ * element of every output is written, with 16-byte stores between an unaligned head and tail.  rows_cap smaller than the rows needed:
+ * TM_E_NOSPACE, nothing is written, tm_last_error names the number (tm_batch_fit_rows returns it); more than 2^36 elements in one output:
+ * TM_E_LIMIT; argument errors and a batch that holds no ids: TM_E_INVALID, as for tm_batch_pack.  Ids from tm_batch_load_ids are accepted.
+ * The calls change nothing a later call reads.
+ * Streams - as strict as for tm_batch_windows below: BOTH calls rewrite the plan in the batch's buffer on the stream of the batch's last run,
+ * and tm_batch_fit rewrites the table of the rows on `stream`, while its fill reads both on `stream`.  So before the next of these two
+ * calls on the batch, the last fill must have completed or have run on the stream of the batch's last run - passing that stream to every
+ * call is the simple way.  The buffers are shared with no other call. */
+int tm_batch_fit_rows(tm_batch* b, const tm_collate* how, uint64_t* rows_needed);   /* synchronizes like tm_batch_pack_rows */
+int tm_batch_fit(tm_batch* b, const tm_collate* how, void* stream, uint64_t rows_cap,
+                 void* ids_out, uint32_t* doc_index_out, uint32_t* position_out,
+                 uint32_t* lengths_out, uint32_t* row_doc_out, uint32_t* row_start_out);
 /* The reverse: rows[nrows * row_len] ids of id_bytes each (device or page-locked memory, as above) become the batch's ragged ids and
  * offsets, one document per row, and the batch is in the state a run leaves it in - ndocs = nrows, ids, offsets, totals, missing = 0 - so
  * that tm_batch_decode, tm_batch_decoded_download, tm_batch_download and tm_batch_totals (and the two calls above) work on it.  What of a
@@ -314,7 +351,7 @@ int tm_batch_load_ids(tm_batch* b, const void* rows, uint32_t nrows, uint32_t ro
  * leaves no id, hence a gap; a token may advance by 0 bytes (a one-byte alternative in a forward-delete state): its span is empty.  Begins
  * never decrease and the spans of a document never overlap.  Neither the ids nor a decode give the spans back (the "D " duplicates of a
  * capcode vocabulary, forward deletes and alternatives of another length stand in the way).  Not offered for tm_tokenize_pipeline,
- * tm_tokenize_document, the streaming encoder and tm_batch_pack.
+ * tm_tokenize_document, the streaming encoder, tm_batch_pack and tm_batch_fit.
  * tm_batch_spans: spans_out (device or page-locked memory, aligned to 8 bytes) receives uint32_t[total ids][2], the pairs (begin, end) in
  * exactly the slot order of tm_batch_device_tokens.  Waits for the batch's last run as tm_batch_collate does, is then asynchronous on `stream`.
  * spans_cap (in ids) smaller than the total: TM_E_NOSPACE, nothing is written.  A batch whose ids did not come from a walk (no completed
@@ -355,7 +392,8 @@ int tm_tokenize_batch_spans(const tm_vocab* v, const uint8_t* text, const uint64
  * nothing a later call reads.
  * Slot order, alignment, TM_E_NOSPACE (nothing written) and the errors of tm_batch_spans / tm_batch_collate_spans / tm_tokenize_batch_spans
  * apply unchanged; besides: a batch whose text did not come from tm_batch_upload_raw + tm_batch_normalize: TM_E_INVALID; a raw document of
- * 2^32 bytes or more: TM_E_LIMIT.  Not offered for tm_tokenize_pipeline, tm_tokenize_document, the streaming encoder and tm_batch_pack. */
+ * 2^32 bytes or more: TM_E_LIMIT.  Not offered for tm_tokenize_pipeline, tm_tokenize_document, the streaming encoder, tm_batch_pack
+ * and tm_batch_fit. */
 int tm_batch_raw_spans(tm_batch* b, void* stream, uint32_t* spans_out, uint64_t spans_cap, uint32_t* host_docs);
 /* As tm_batch_raw_spans, with its three parts between HIP events on `stream`: ms[0] the normalized pairs (tm_batch_spans' pass), ms[1] the
  * origin pass (with the host's share where documents are mapped there), ms[2] the map.  Synchronizes.  ms NULL: tm_batch_raw_spans. */
@@ -491,7 +529,7 @@ int tm_tokenize_batch_spans_in(const tm_vocab* v, const uint8_t* docs, const uin
  * and waits for it once.  A call changes nothing a later call reads - ids, offsets, totals stay as they are.
  * TM_E_INVALID before any device work: a batch whose ids did not come from a walk, an unknown `text` or `unit`, TM_TEXT_RAW on a batch without raw
  * text, label_bytes other than 4 or 8, a missing or misaligned array.
- * Not offered for windows, text pairs and tm_batch_pack; overlapping or nested regions and B-/I- tagging are left to the caller
+ * Not offered for windows, text pairs, tm_batch_pack and tm_batch_fit; overlapping or nested regions and B-/I- tagging are left to the caller
  * (region_tokens_out gives the first token of every region). */
 typedef struct tm_regions {
   const uint64_t* reg_offsets;

@@ -261,6 +261,10 @@ struct tm_batch {
   uint32_t win_cap = 0;                 // ... in documents
   uint32_t* d_win_rows = nullptr;       // ... and the document of every row of the last window call, grow-only
   uint64_t win_rows_cap = 0;
+  uint8_t* d_fit = nullptr;             // tm_batch_fit: exit maps | first row of every tile of documents, the row count | next opener | entry of every tile, grow-only (tm_fit.hip)
+  uint32_t fit_cap = 0;                 // ... in documents
+  uint8_t* d_fit_rows = nullptr;        // ... and the row table of the last tm_batch_fit (16 bytes per row), grow-only
+  uint64_t fit_rows_cap = 0;
   uint16_t* d_out16 = nullptr;          // set for the length of a launch: K4 writes two-byte ids here instead (a chunk of the ring, launch_emit)
   uint64_t out16_cap = 0;
   // a chunk of the host-to-host ring (tm_host.hip): what the host would have read back between the stages - the number of segments the normalizer

@@ -365,10 +365,13 @@ def encode_pair_windows(vocab, first, second, max_length, overlap, max_first, *,
     return res
 
 
-def pack_batch(vocab, docs, seq_len, *, eos_id, pad_id, dtype=None, raw=True, device=None):
+def pack_batch(vocab, docs, seq_len, *, eos_id, pad_id, dtype=None, raw=True, device=None, whole=False):
     """documents -> the stream ids(doc 0) eos ids(doc 1) eos ... cut into rows of seq_len (eos_id None: no separator), the last row filled
     with pad_id: {"input_ids" [rows, seq_len] of `dtype` (default int64), "doc_index" [rows, seq_len] int32 - the document of every
-    position, -1 on padding -, "position" [rows, seq_len] int32 - its index inside the document, the EOS being the document's last}"""
+    position, -1 on padding -, "position" [rows, seq_len] int32 - its index inside the document, the EOS being the document's last}.
+    whole=True: the documents are packed WHOLE instead - a row is closed with pad_id when the next document does not fit, only a document
+    longer than a row is cut (tm_batch_fit) - and "lengths" [rows] int32 (entries of a row), "row_doc" [rows] int32 (the document of a
+    row's first entry) and "row_start" [rows] int32 (that entry's index inside its document) come beside the three."""
     torch = _torch()
     dtype = dtype or torch.int64
     id_bytes = _check_dtype(torch, dtype)
@@ -381,13 +384,20 @@ def pack_batch(vocab, docs, seq_len, *, eos_id, pad_id, dtype=None, raw=True, de
         b, nd = _tokenize(vocab, docs, raw, st)
         how = _Collate(0, nd, seq_len, id_bytes, int(pad_id), N.TM_NONE, _special(eos_id), 0)
         rows = C.c_uint64()
-        N.check(N.lib.tm_batch_pack_rows(b, C.byref(how), C.byref(rows)))
+        N.check((N.lib.tm_batch_fit_rows if whole else N.lib.tm_batch_pack_rows)(b, C.byref(how), C.byref(rows)))
         rows = int(rows.value)
         ids = torch.empty((rows, seq_len), dtype=dtype, device=dev)
         doc_index = torch.empty((rows, seq_len), dtype=torch.int32, device=dev)
         position = torch.empty((rows, seq_len), dtype=torch.int32, device=dev)
-        N.check(N.lib.tm_batch_pack(b, C.byref(how), st, rows, ids.data_ptr(), doc_index.data_ptr(), position.data_ptr()))
-    return {"input_ids": ids, "doc_index": doc_index, "position": position}
+        res = {"input_ids": ids, "doc_index": doc_index, "position": position}
+        if whole:
+            per_row = [torch.empty((rows,), dtype=torch.int32, device=dev) for _ in range(3)]
+            if rows:
+                N.check(N.lib.tm_batch_fit(b, C.byref(how), st, rows, ids.data_ptr(), doc_index.data_ptr(), position.data_ptr(), *[x.data_ptr() for x in per_row]))
+            res.update(zip(("lengths", "row_doc", "row_start"), per_row))
+        else:
+            N.check(N.lib.tm_batch_pack(b, C.byref(how), st, rows, ids.data_ptr(), doc_index.data_ptr(), position.data_ptr()))
+    return res
 
 
 def decode_batch(vocab, ids, *, lengths=None, pad_id=None, bos_id=None, eos_id=None, device=None):

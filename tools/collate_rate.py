@@ -7,7 +7,8 @@ of the int64 rows, and text pairs and pair windows at int64 and L = 512 beside a
 first half against second half), on the ids of a --mib MiB batch of the benchmark's
 englishcode-32000 shape.  HIP events (torch's) around the launches on ONE stream; GB/s counts the bytes a call reads plus the bytes it writes;
 the yardstick is hipMemcpyAsync device to device of that many bytes (half read, half written), timed the same way.  Three warm-up calls, then
-the median of 20.  --only pairs: the pair lines alone; --append: add to --out under a dated heading instead of replacing it.  (tm_batch_collate / tm_batch_pack wait for the batch's last run before they launch and tm_batch_pack_rows fetches two
+the median of 20.  --only pairs: the pair lines alone; --only fit: whole-document packing (tm_batch_fit) beside pack on the same batch, and on
+300 000 and 1 048 576 short documents; --append: add to --out under a dated heading instead of replacing it.  (tm_batch_collate / tm_batch_pack wait for the batch's last run before they launch and tm_batch_pack_rows fetches two
 offsets: host time, outside the kernels but inside the events - with 256 MiB of text it is a few percent of a call.)"""
 import argparse
 import ctypes as C
@@ -44,7 +45,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mib", type=int, default=256)
     ap.add_argument("--out", default=os.path.join("profiles", "collate.txt"))
-    ap.add_argument("--only", choices=["pairs"], default=None)
+    ap.add_argument("--only", choices=["pairs", "fit"], default=None)
     ap.add_argument("--append", action="store_true")
     a = ap.parse_args()
     L = 2048
@@ -144,9 +145,46 @@ def main():
                 f.write("\n==== %s: tools/collate_rate.py%s ====\n" % (time.strftime("%Y-%m-%d"), " --only " + a.only if a.only else ""))
             f.write("\n".join(lines) + "\n")
 
-    if a.only == "pairs":
+    def fit_lines(bt, k, n_ids_k, LF, label):
+        """whole-document packing (tm_batch_fit) beside tm_batch_pack, uint16 + doc_index + position, on the first k documents of batch bt: the two
+        fills move the same bytes but for the padding of the rows fit closes early.  A fit call = tm_batch_fit_rows' work (k_fit_next, k_fit_tiles,
+        k_fit_resolve, one 8-byte read-back, a wait for the stream), then the row table (k_fit_rows) and the fill"""
+        howf = torch_api._Collate(0, k, LF, 2, pad, N.TM_NONE, eos, 0)
+        need = C.c_uint64()
+        N.check(N.lib.tm_batch_pack_rows(bt, C.byref(howf), C.byref(need)))
+        rp = int(need.value)
+        N.check(N.lib.tm_batch_fit_rows(bt, C.byref(howf), C.byref(need)))
+        rf = int(need.value)
+        fids = torch.empty((rf, LF), dtype=torch.int16, device="cuda")
+        fdi, fpo = (torch.empty((rf, LF), dtype=torch.int32, device="cuda") for _ in range(2))
+        med, lo, hi = timed(lambda: N.check(N.lib.tm_batch_pack(bt, C.byref(howf), st, rp, fids.data_ptr(), fdi.data_ptr(), fpo.data_ptr())), stream)
+        report("pack uint16 + doc_index + position%s" % label, n_ids_k * 4 + rp * LF * 10, med, lo, hi)
+        med, lo, hi = timed(lambda: N.check(N.lib.tm_batch_fit(bt, C.byref(howf), st, rf, fids.data_ptr(), fdi.data_ptr(), fpo.data_ptr(), None, None, None)), stream)
+        report("fit uint16 + doc_index + position%s" % label, n_ids_k * 4 + rf * LF * 10, med, lo, hi)
+        rmed, rlo, rhi = timed(lambda: N.check(N.lib.tm_batch_fit_rows(bt, C.byref(howf), C.byref(need))), stream)
+        lines.append("  fit_rows alone%s  %8.3f ms (%.3f .. %.3f)  -> row table + fill: fit less fit_rows = %.3f ms  (%d documents -> %d rows of %d; pack: %d rows)" % (
+            label, rmed, rlo, rhi, med - rmed, k, rf, LF, rp))
+        print(lines[-1], flush=True)
+
+    def fit_many(k):
+        """... and on k documents of 0 .. 255 ids each (tm_batch_load_ids of random rows): what the planning stages cost where the documents are many"""
+        rng = np.random.default_rng(k)
+        lens_h = rng.integers(0, 256, size=k).astype(np.int32)
+        src = torch.from_numpy(rng.integers(0, 30000, size=(k, 256)).astype(np.int32)).cuda()
+        bk = C.c_void_p()
+        N.check(N.lib.tm_batch_create(v.handle, 4096, k, C.byref(bk)))
+        N.check(N.lib.tm_batch_load_ids(bk, src.data_ptr(), k, 256, 4, torch.from_numpy(lens_h).cuda().data_ptr(), N.TM_NONE, N.TM_NONE, N.TM_NONE, st))
+        fit_lines(bk, k, int(lens_h.sum()), L, ", %d documents" % k)
+        N.lib.tm_batch_free(bk)
+
+    if a.only in ("pairs", "fit"):
         with torch.cuda.stream(stream):
-            pairs_lines()
+            if a.only == "pairs":
+                pairs_lines()
+            else:
+                fit_lines(b, nd, n_ids, L, "")
+                fit_many(300000)
+                fit_many(1048576)
         N.lib.tm_batch_free(b)
         write_out()
         return
@@ -213,6 +251,7 @@ def main():
         med, lo, hi = timed(lambda: N.check(N.lib.tm_batch_load_ids(b2, ids.data_ptr(), nd, L, 8, lens.data_ptr(), pad, N.TM_NONE, N.TM_NONE, st)), stream)
         report("load_ids int64 rows", nd * L * 8 + kept * 12 + nd * 16, med, lo, hi)
         pairs_lines()
+        fit_lines(b, nd, n_ids, L, "")
     N.lib.tm_batch_free(b2)
     N.lib.tm_batch_free(b)
     write_out()
