@@ -348,6 +348,31 @@ func (b *HipBatch) Collate(how HipCollate, stream, ids, mask, lengths unsafe.Poi
 	return err
 }
 
+// CollateSelect is Collate through a list of document numbers: how.Docs rows, row r the row Collate writes for document docIndex[r] of the last
+// run (how.FirstDoc must be 0).  docIndex: how.Docs uint32 in device or page-locked memory; a document may stand in any number of rows.  An index
+// that is no document of the run gives a row of padding; bad (may be nil, one uint32) receives the number of such rows (tm_batch_collate_select).
+func (b *HipBatch) CollateSelect(how HipCollate, docIndex, stream, ids, mask, lengths, bad unsafe.Pointer) error {
+	h := how.c()
+	_, err := locked(func() C.int {
+		return C.tm_batch_collate_select(b.h, &h, (*C.uint32_t)(docIndex), stream, ids, (*C.uint8_t)(mask), (*C.uint32_t)(lengths), (*C.uint32_t)(bad))
+	})
+	return err
+}
+
+// LengthOrder writes the documents firstDoc .. firstDoc + docs - 1 of the last run to order (docs uint32, device or page-locked memory) as absolute
+// document numbers in the order of their id counts - ascending, descending if asked - documents of equal count in ascending document number;
+// counts (may be nil) receives the count of order[i].  What CollateSelect takes as its docIndex (tm_batch_length_order).
+func (b *HipBatch) LengthOrder(firstDoc, docs uint32, descending bool, stream, order, counts unsafe.Pointer) error {
+	var flags C.uint32_t
+	if descending {
+		flags = C.TM_ORDER_DESCENDING
+	}
+	_, err := locked(func() C.int {
+		return C.tm_batch_length_order(b.h, C.uint32_t(firstDoc), C.uint32_t(docs), flags, stream, (*C.uint32_t)(order), (*C.uint32_t)(counts))
+	})
+	return err
+}
+
 // Spans writes the byte span of every id of the last run to spans: uint32 [total ids][2], (begin, end) in the slot order of the ids, counted
 // from each document's start in the normalized text (tm_batch_spans).  spans: device or page-locked memory, aligned to 8 bytes, room for capIds pairs.
 func (b *HipBatch) Spans(stream, spans unsafe.Pointer, capIds uint64) error {

@@ -285,6 +285,34 @@ typedef struct tm_collate {
  * [ndocs * row_len] bytes, 1 on an entry and 0 on padding; lengths_out (may be NULL) [ndocs]: entries of a row, specials included. */
 int tm_batch_collate(tm_batch* b, const tm_collate* how, void* stream,
                      void* ids_out, uint8_t* mask_out, uint32_t* lengths_out);
+/* Batches by index: tokenize once, draw batches many times - a shuffled batch per step, a new permutation per epoch, batches of documents of
+ * similar length padded to their own maximum - without re-tokenizing and without an id or an index crossing the host link.
+ * tm_batch_collate_select: tm_batch_collate through a list of document numbers.  how->ndocs is the number of ROWS, the length of doc_index
+ * (device or page-locked memory); how->first_doc must be 0 (else TM_E_INVALID): the indices are document numbers of the last run.  Row r is
+ * exactly the row tm_batch_collate writes for document doc_index[r] - the specials, the cut to row_len, TM_COLLATE_PAD_LEFT,
+ * TM_COLLATE_KEEP_TAIL and id_bytes 2 / 4 / 8 as there.  A document may stand in any number of rows, and there may be more rows than the run
+ * has documents; the identity list gives tm_batch_collate's bytes.  An index that is no document of the last run gives a row of pad_id
+ * only, mask 0, length 0; bad_out (may be NULL; ONE uint32_t, device or page-locked) is overwritten with the number of such rows (also with
+ * no rows at all: 0).  Every element of every output is written, with 16-byte stores between an unaligned head and tail; argument errors,
+ * the limit of 2^36 elements and the wait for the batch's last run are tm_batch_collate's; a NULL doc_index with rows: TM_E_INVALID.  The
+ * call keeps nothing in the batch: calls on different streams may overlap. */
+int tm_batch_collate_select(tm_batch* b, const tm_collate* how, const uint32_t* doc_index, void* stream,
+                            void* ids_out, uint8_t* mask_out, uint32_t* lengths_out, uint32_t* bad_out);
+/* tm_batch_length_order: the documents first_doc .. first_doc + ndocs - 1 of the last run in the order of their id counts
+ * n_d = tok_offsets[d + 1] - tok_offsets[d] (one of 2^32 ids or more counts as 2^32 - 1), ascending, under TM_ORDER_DESCENDING descending.
+ * STABLE in both directions: documents of equal count stand in ascending document number.  order_out[ndocs] (device or page-locked memory)
+ * receives ABSOLUTE document numbers - what tm_batch_collate_select takes; counts_out[ndocs] (may be NULL) the count of order_out[i].
+ * A batch that holds no ids, a range beyond the run, flag bits other than TM_ORDER_DESCENDING, a NULL order_out with ndocs > 0:
+ * TM_E_INVALID.  ndocs == 0: TM_OK, nothing is written.  Ids from tm_batch_load_ids are accepted.  Waits for the batch's last run as
+ * tm_batch_collate does; after that everything is asynchronous on `stream` and nothing is read back: a radix sort of (count, document)
+ * pairs, 8 bits a pass, that runs only the passes the largest count asks for, in a grow-only buffer of the batch alone (about 18 bytes per
+ * document, counted in tm_batch_device_bytes).  Nothing in it reads the ids themselves.
+ * Streams - as strict as for tm_batch_fit below: the call rewrites the pairs in the batch's buffer on `stream` and its last kernel reads
+ * them on `stream`.  So before the next call of it on the batch, the last one must have completed or have run on the same stream - passing
+ * the stream of the batch's last run to every call is the simple way.  The buffer is shared with no other call. */
+#define TM_ORDER_DESCENDING 1u
+int tm_batch_length_order(tm_batch* b, uint32_t first_doc, uint32_t ndocs, uint32_t flags, void* stream,
+                          uint32_t* order_out, uint32_t* counts_out);
 /* The pre-training form: the stream ids(first_doc) [eos] ids(first_doc + 1) [eos] ... (no separator with eos_id == TM_NONE: an empty
  * document then leaves no trace; bos_id and flags are not used) cut into rows of row_len, the last one filled up with pad_id.
  * tm_batch_pack_rows: the rows that takes, ceil(stream length / row_len) (synchronizes like tm_batch_totals).  tm_batch_pack writes them:

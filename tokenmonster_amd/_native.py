@@ -104,6 +104,8 @@ SIGNATURES = {
     "tm_batch_raw_spans_timed": (C.c_int, [vp, vp, vp, C.c_uint64, u32p, f32p]),
     "tm_batch_collate_raw_spans": (C.c_int, [vp, vp, vp, vp, C.c_uint32]),
     "tm_tokenize_batch_raw_spans": (C.c_int, [vp, vp, vp, C.c_uint32, vp, C.c_uint64, vp, vp, vp]),
+    "tm_batch_collate_select": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp]),
+    "tm_batch_length_order": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp]),
     "tm_batch_fit_rows": (C.c_int, [vp, vp, u64p]),
     "tm_batch_fit": (C.c_int, [vp, vp, vp, C.c_uint64, vp, vp, vp, vp, vp, vp]),
     "tm_batch_window_rows": (C.c_int, [vp, vp, C.c_uint32, u64p]),

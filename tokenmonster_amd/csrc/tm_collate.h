@@ -67,7 +67,19 @@ __device__ __forceinline__ RowPlan row_plan(const CollateArgs& a, uint64_t r) {
   return p;
 }
 
-// ---- the fill of rows: what k_collate_rows / k_window_rows and k_collate_spans / k_window_spans do with work-item t ------------------------------
+// ---- one document per row through a list of document numbers (tm_batch_collate_select) -------------------------------------------------------
+// row r holds document doc_index[r] of the run: two dependent loads per plan where row_plan has one.  a.toff: tok_offsets of the whole run.
+struct SelectArgs {
+  CollateArgs a;
+  const uint32_t* doc_index;  // [a.rows]
+  uint32_t run_docs;          // documents of the run: an index at or beyond it gives a row of padding
+};
+__device__ __forceinline__ RowPlan select_plan(const SelectArgs& s, uint64_t r) {
+  const uint32_t d = s.doc_index[r];
+  return d < s.run_docs ? row_plan(s.a, d) : RowPlan{0, 0, 0};      // (no entries: every column is padding, under either flag)
+}
+
+// ---- the fill of rows: what k_collate_rows / k_collate_select / k_window_rows and k_collate_spans / k_window_spans do with work-item t ------------------------------
 // Args: CollateArgs or WindowArgs (L, pad, bos, eos, ids); plan(r): the RowPlan of row r - row_plan, or win_plan's.  The row of the work-item's
 // first element is a division; when its vector crosses a row end the next row's plan is asked for.
 // MASK: the element is 1 inside the row's entries and 0 on padding (T = uint8_t); else the id.

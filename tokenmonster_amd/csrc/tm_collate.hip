@@ -1,8 +1,9 @@
 // tm_collate.hip — fixed-shape id tensors from the ragged ids a batch holds, and back: tm_batch_collate (one document per row, padded or
-// truncated, BOS / EOS, mask, lengths), tm_batch_pack (one EOS-separated stream cut into rows, with document numbers and positions) and
+// truncated, BOS / EOS, mask, lengths), tm_batch_collate_select (the same rows for a LIST of document numbers: any order, repeats, a shuffled
+// or length-grouped batch), tm_batch_pack (one EOS-separated stream cut into rows, with document numbers and positions) and
 // tm_batch_load_ids (a [rows, L] tensor of ids -> the batch's ragged ids and offsets, ready for tm_batch_decode).
 //
-// All three are streaming kernels: no table, no LDS, a few bytes read per byte written.  Every output is treated as ONE flat run of
+// All are streaming kernels: no table, a few bytes read per byte written (LDS only where the selection stages its rows' plans).  Every output is treated as ONE flat run of
 // elements (a [rows, L] tensor is contiguous): the elements in front of the first 16-byte boundary and behind the last whole 16 bytes are
 // stored one by one, everything between as 16-byte vectors, one per work-item, so that a wavefront writes 1 KiB of consecutive bytes per
 // store instruction whatever L and the element size are.  A work-item finds the row (the document) of its first element once - a division,
@@ -25,6 +26,49 @@ __global__ __launch_bounds__(256) void k_collate_rows(CollateArgs a, Flat f, T* 
   const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (!MASK && lengths && t < a.rows) lengths[t] = row_plan(a, t).len;
   fill_rows<T, MASK>(a, f, out, t, [&](uint64_t r) { return row_plan(a, r); });
+}
+
+// ---- k_collate_select: document doc_index[r] in row r ---------------------------------------------------------------------------------------------
+// The same fill with select_plan.  A workgroup takes SEL_VECS vectors per work-item, 256 consecutive ones at a time; they cover consecutive
+// elements, so few rows - one or two at the row lengths of a model: their plans (doc_index[r], then that document's two offsets) are staged
+// in LDS by one work-item each, once per workgroup, and the fill reads them there.  A row outside the staged run - beyond SEL_STAGE rows
+// where rows are a few ids long, or the single elements in front of and behind the vectors - is planned from global memory as before.
+constexpr uint32_t SEL_STAGE = 256, SEL_VECS = 4;
+template <typename T, bool MASK>
+__global__ __launch_bounds__(256) void k_collate_select(SelectArgs s, Flat f, T* __restrict__ out, uint32_t* __restrict__ lengths) {
+  constexpr uint32_t PER = 16 / sizeof(T);
+  __shared__ RowPlan plans[SEL_STAGE];
+  const uint64_t t0 = (uint64_t)blockIdx.x * (256 * SEL_VECS);
+  uint64_t r0 = 0;
+  uint32_t staged = 0;
+  if (t0 < f.nvec) {                                   // rows of the first and the last element of this workgroup's vectors
+    const uint64_t e0 = f.head + t0 * PER, e1 = f.head + std::min<uint64_t>(t0 + 256 * SEL_VECS, f.nvec) * PER - 1;
+    uint64_t r1;
+    if (f.n <= 0xFFFFFFFFull) { r0 = (uint32_t)e0 / s.a.L; r1 = (uint32_t)e1 / s.a.L; }      // (as in fill_rows: no 64-bit division where 32 bits do)
+    else { r0 = e0 / s.a.L; r1 = e1 / s.a.L; }
+    staged = (uint32_t)std::min<uint64_t>(r1 - r0 + 1, SEL_STAGE);
+  }
+  if (threadIdx.x < staged) plans[threadIdx.x] = select_plan(s, r0 + threadIdx.x);      // (rows of elements of the output)
+  __syncthreads();
+#pragma unroll
+  for (uint32_t k = 0; k < SEL_VECS; k++) {
+    const uint64_t t = t0 + k * 256 + threadIdx.x;
+    if (!MASK && lengths && t < s.a.rows) lengths[t] = select_plan(s, t).len;
+    fill_rows<T, MASK>(s.a, f, out, t, [&](uint64_t r) { return r - r0 < staged ? plans[r - r0] : select_plan(s, r); });
+  }
+}
+// the rows whose index is no document of the run: one workgroup, one plain store (bad_out may be page-locked host memory)
+__global__ __launch_bounds__(1024) void k_select_bad(const uint32_t* __restrict__ doc_index, uint32_t rows, uint32_t run_docs, uint32_t* __restrict__ bad) {
+  __shared__ uint32_t wsum[16];
+  uint32_t c = 0;
+  for (uint64_t r = threadIdx.x; r < rows; r += blockDim.x) c += doc_index[r] >= run_docs ? 1u : 0u;
+  for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off);
+  if ((threadIdx.x & 63u) == 0) wsum[threadIdx.x >> 6] = c;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (uint32_t w = 1; w < blockDim.x / 64; w++) c += wsum[w];
+    *bad = c;
+  }
 }
 
 // ---- k_pack_stream: ids(doc0) [eos] ids(doc1) [eos] ... cut into rows -------------------------------------------------------------------------------------
@@ -153,6 +197,14 @@ static void launch_collate(const CollateArgs& a, void* ids_out, uint32_t* length
   const auto kern = k_collate_rows<T, false>;
   TM_LAUNCH(kern, grid_of(items), 256, 0, st, a, f, static_cast<T*>(ids_out), lengths_out);
 }
+static uint32_t select_grid(uint64_t items) { return (uint32_t)((items + 256 * SEL_VECS - 1) / (256 * SEL_VECS)); }
+template <typename T>
+static void launch_select(const SelectArgs& s, void* ids_out, uint32_t* lengths_out, hipStream_t st) {
+  const Flat f = flat_of(ids_out, (uint64_t)s.a.rows * s.a.L, sizeof(T));
+  const uint64_t items = std::max<uint64_t>(flat_items(f, sizeof(T)), lengths_out ? s.a.rows : 0);
+  const auto kern = k_collate_select<T, false>;
+  TM_LAUNCH(kern, select_grid(items), 256, 0, st, s, f, static_cast<T*>(ids_out), lengths_out);
+}
 template <typename T>
 static void launch_pack_ids(const PackArgs& a, void* ids_out, uint64_t n, hipStream_t st) {
   const Flat f = flat_of(ids_out, n, sizeof(T));
@@ -205,6 +257,36 @@ int tm_batch_collate(tm_batch* b, const tm_collate* how, void* stream, void* ids
     const Flat f = flat_of(mask_out, (uint64_t)a.rows * a.L, 1);
     const auto kern = k_collate_rows<uint8_t, true>;
     TM_LAUNCH(kern, grid_of(flat_items(f, 1)), 256, 0, st, a, f, mask_out, (uint32_t*)nullptr);
+  }
+  return launch_check();
+}
+
+int tm_batch_collate_select(tm_batch* b, const tm_collate* how, const uint32_t* doc_index, void* stream, void* ids_out, uint8_t* mask_out, uint32_t* lengths_out,
+                            uint32_t* bad_out) {
+  static const char who[] = "tm_batch_collate_select";
+  if (!how) return set_error(TM_E_INVALID, "%s: null argument", who);
+  tm_collate any = *how;                               // (ndocs counts rows here, not documents of the run: nothing of it for check_how's range)
+  any.ndocs = 0;
+  int rc = check_how(b, &any, ids_out, who);
+  if (rc != TM_OK) return rc;
+  if (how->first_doc != 0) return set_error(TM_E_INVALID, "%s: first_doc %u (the indices count from the run's first document: 0)", who, how->first_doc);
+  if (how->ndocs && !doc_index) return set_error(TM_E_INVALID, "%s: null doc_index", who);
+  const uint32_t ns = (how->bos_id != TM_NONE ? 1u : 0u) + (how->eos_id != TM_NONE ? 1u : 0u);
+  if (how->row_len < ns) return set_error(TM_E_INVALID, "%s: row_len %u holds no %u specials", who, how->row_len, ns);
+  if ((uint64_t)how->ndocs * how->row_len > COLLATE_MAX_ELEMS) return set_error(TM_E_LIMIT, "%s: %u rows of %u ids in one call (split the rows)", who, how->ndocs, how->row_len);
+  if ((rc = enter_device(b->vocab)) != TM_OK || (rc = ensure_output(b)) != TM_OK) return rc;      // (waits for the run: the ids are all there)
+  hipStream_t st = (hipStream_t)stream;
+  (void)hipGetLastError();
+  if (bad_out) TM_LAUNCH(k_select_bad, 1, 1024, 0, st, doc_index, how->ndocs, b->ndocs, bad_out);
+  if (how->ndocs == 0) return bad_out ? launch_check() : TM_OK;
+  const SelectArgs s{CollateArgs{b->d_out, b->d_tok_offsets, how->ndocs, how->row_len, how->pad_id, how->bos_id, how->eos_id, how->flags}, doc_index, b->ndocs};
+  if (how->id_bytes == 2) launch_select<uint16_t>(s, ids_out, lengths_out, st);
+  else if (how->id_bytes == 4) launch_select<uint32_t>(s, ids_out, lengths_out, st);
+  else launch_select<uint64_t>(s, ids_out, lengths_out, st);
+  if (mask_out) {
+    const Flat f = flat_of(mask_out, (uint64_t)s.a.rows * s.a.L, 1);
+    const auto kern = k_collate_select<uint8_t, true>;
+    TM_LAUNCH(kern, select_grid(flat_items(f, 1)), 256, 0, st, s, f, mask_out, (uint32_t*)nullptr);
   }
   return launch_check();
 }

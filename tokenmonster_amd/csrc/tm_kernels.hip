@@ -2700,7 +2700,7 @@ void tm_batch_free(tm_batch* b) {
   void* ptrs[] = {b->text_borrowed ? nullptr : (void*)b->d_text, b->d_offsets, b->d_doc_nseg, b->d_doc_seg_start, b->d_seg_doc, b->d_R0, b->d_R1, b->d_side, b->d_exitmap, b->d_exit16, b->d_seg_entry,
                   b->d_seg_tokbase, b->d_seg_par, b->d_doc_ntok, b->d_doc_events, b->d_doc_missing, b->d_doc_fd, b->d_tok_offsets, b->d_scan_tmp, b->d_totals,
                   b->d_out, b->d_groups, b->d_longs, b->d_gmap, b->d_group_entry, b->d_group_base,
-                  b->d_ctl_store, b->d_dec_a, b->d_dec_b, b->d_spans, b->d_own, b->d_own_tmp, b->d_win, b->d_win_rows, b->d_fit, b->d_fit_rows, b->d_units[0], b->d_units[1], b->d_region};
+                  b->d_ctl_store, b->d_dec_a, b->d_dec_b, b->d_spans, b->d_own, b->d_own_tmp, b->d_win, b->d_win_rows, b->d_fit, b->d_fit_rows, b->d_order, b->d_units[0], b->d_units[1], b->d_region};
   for (void* p : ptrs) (void)hipFree(p);
   tmh::raw_free(b);                                    // the normalizer's and the filter pass's device buffers (tm_norm.hip)
   if (b->have_events) for (auto& ev : b->ev) (void)hipEventDestroy(ev);

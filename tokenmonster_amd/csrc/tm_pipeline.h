@@ -265,6 +265,8 @@ struct tm_batch {
   uint32_t fit_cap = 0;                 // ... in documents
   uint8_t* d_fit_rows = nullptr;        // ... and the row table of the last tm_batch_fit (16 bytes per row), grow-only
   uint64_t fit_rows_cap = 0;
+  uint8_t* d_order = nullptr;           // tm_batch_length_order: the digit bases and their scan's sums | two planes of (key, document) | digit counts per tile | the tiles' largest counts, the largest of all, grow-only (tm_order.hip)
+  uint32_t order_cap = 0;               // ... in documents
   uint16_t* d_out16 = nullptr;          // set for the length of a launch: K4 writes two-byte ids here instead (a chunk of the ring, launch_emit)
   uint64_t out16_cap = 0;
   // a chunk of the host-to-host ring (tm_host.hip): what the host would have read back between the stages - the number of segments the normalizer

@@ -7,6 +7,7 @@ without an id crossing the host link (tm_batch_collate / tm_batch_windows / tm_b
     encode_pair_windows   the QA form: A in every row, B slides over several rows that overlap
     pack_batch     the pre-training form: one EOS-separated id stream cut into rows, with document numbers and positions
     decode_batch   a [rows, L] tensor of ids -> list of bytes
+    tokenize_resident   tokenize once, draw batches many times: the documents' length order and encode_batch's rows by document number
 
 torch is imported on first use; nothing else in the package imports this module.  A program that uses it imports torch BEFORE
 tokenmonster_amd: torch ships a HIP runtime of its own, the one loaded first serves the whole process, and only torch's serves both.  The kernels run on torch's CURRENT stream of the
@@ -398,6 +399,105 @@ def pack_batch(vocab, docs, seq_len, *, eos_id, pad_id, dtype=None, raw=True, de
         else:
             N.check(N.lib.tm_batch_pack(b, C.byref(how), st, rows, ids.data_ptr(), doc_index.data_ptr(), position.data_ptr()))
     return res
+
+
+class ResidentBatch:
+    """What tokenize_resident returns: the ids of `docs` resident on the device, in a workspace of its own (no other call of this module
+    touches it), to draw batches from by document number until close().
+        ndocs                      the documents
+        counts()                   [ndocs] int64: the id count of every document
+        length_order(descending)   [ndocs] int64: the document numbers in a stable order of their id counts (tm_batch_length_order)
+        collate(indices, ...)      the rows of encode_batch for the documents `indices` names (tm_batch_collate_select)
+    Everything runs on torch's current stream of the device and nothing is read back: no id and no index crosses the host link."""
+
+    def __init__(self, vocab, docs, raw, device):
+        torch = _torch()
+        docs = [d.encode("utf-8") if isinstance(d, str) else d for d in docs]
+        text, offsets = pack_documents(docs)
+        self.vocab, self.ndocs, self.dev = vocab, offsets.size - 1, _device(vocab, device)
+        self.handle = C.c_void_p()
+        self._order_stream = None
+        with torch.cuda.device(self.dev):
+            st = _stream(self.dev)
+            N.check(N.lib.tm_batch_create(vocab.handle, _pow2(int(text.size) * (4 if raw else 1) + 16 * self.ndocs + 1024), max(self.ndocs, 1), C.byref(self.handle)))
+            try:
+                if raw:
+                    N.check(N.lib.tm_batch_upload_raw(self.handle, N.ptr(text), N.ptr(offsets), self.ndocs))
+                    N.check(N.lib.tm_batch_normalize(self.handle, st))
+                else:
+                    N.check(N.lib.tm_batch_upload(self.handle, N.ptr(text), N.ptr(offsets), self.ndocs))
+                N.check(N.lib.tm_batch_run(self.handle, st))
+            except Exception:
+                self.close()
+                raise
+
+    def _order(self, descending):
+        """(order, counts of the order's documents), both int64, by one tm_batch_length_order"""
+        torch = _torch()
+        with torch.cuda.device(self.dev):
+            st = _stream(self.dev)
+            if self._order_stream not in (None, st.value):      # the last order's kernels may still use the scratch this one rewrites
+                torch.cuda.synchronize()
+            self._order_stream = st.value
+            order, counts = (torch.empty((self.ndocs,), dtype=torch.int32, device=self.dev) for _ in range(2))
+            N.check(N.lib.tm_batch_length_order(self.handle, 0, self.ndocs, 1 if descending else 0, st, order.data_ptr(), counts.data_ptr()))
+            return order.to(torch.int64) & 0xFFFFFFFF, counts.to(torch.int64) & 0xFFFFFFFF
+
+    def counts(self):
+        order, sorted_counts = self._order(False)
+        out = _torch().empty_like(sorted_counts)
+        out[order] = sorted_counts
+        return out
+
+    def length_order(self, descending=False):
+        return self._order(descending)[0]
+
+    def collate(self, indices, max_length, *, pad_id, bos_id=None, eos_id=None, pad_left=False, keep_tail=False, dtype=None):
+        """row r = the row encode_batch gives document indices[r]: {"input_ids" [rows, max_length] of `dtype` (default int64), "attention_mask"
+        [rows, max_length] bool, "lengths" [rows] int32, "bad_indices" int32 scalar on the device: the entries of `indices` that name no
+        document - their rows are padding only}.  indices: an integer tensor (moved to the device if it is not there) or a sequence; a
+        document may stand in any number of rows."""
+        torch = _torch()
+        dtype = dtype or torch.int64
+        id_bytes = _check_dtype(torch, dtype)
+        max_length = int(max_length)
+        if max_length < (bos_id is not None) + (eos_id is not None) or max_length < 1:
+            raise ValueError("max_length %d holds no row" % max_length)
+        with torch.cuda.device(self.dev):
+            st = _stream(self.dev)
+            idx = torch.as_tensor(indices).to(device=self.dev).reshape(-1)
+            if idx.numel() and (idx.dtype.is_floating_point or idx.dtype.is_complex or idx.dtype == torch.bool):      # (an empty list has no dtype to speak of)
+                raise ValueError("indices of dtype %s: an integer tensor or a sequence of integers" % (idx.dtype,))
+            idx = idx.to(torch.int64)
+            idx = torch.where((idx < 0) | (idx > 0xFFFFFFFF), torch.full_like(idx, 0xFFFFFFFF), idx).to(torch.int32).contiguous()      # (the bits of a uint32)
+            rows = idx.numel()
+            ids = torch.empty((rows, max_length), dtype=dtype, device=self.dev)
+            mask = torch.empty((rows, max_length), dtype=torch.uint8, device=self.dev)
+            lengths = torch.empty((rows,), dtype=torch.int32, device=self.dev)
+            bad = torch.empty((), dtype=torch.int32, device=self.dev)
+            how = _Collate(0, rows, max_length, id_bytes, int(pad_id), _special(bos_id), _special(eos_id), (PAD_LEFT if pad_left else 0) | (KEEP_TAIL if keep_tail else 0))
+            if rows:
+                N.check(N.lib.tm_batch_collate_select(self.handle, C.byref(how), idx.data_ptr(), st, ids.data_ptr(), mask.data_ptr(), lengths.data_ptr(), bad.data_ptr()))
+            else:
+                bad.zero_()
+        return {"input_ids": ids, "attention_mask": mask.view(torch.bool), "lengths": lengths, "bad_indices": bad}
+
+    def close(self):
+        if self.handle:
+            N.lib.tm_batch_free(self.handle)
+            self.handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def tokenize_resident(vocab, docs, *, raw=True, device=None):
+    """documents (bytes or str; raw=False: already normalized bytes) tokenized ONCE, their ids kept on the device -> ResidentBatch: batches in
+    any order, as often as wanted - a shuffled batch per step, batches of documents of similar length padded to their own maximum."""
+    return ResidentBatch(vocab, docs, raw, device)
 
 
 def decode_batch(vocab, ids, *, lengths=None, pad_id=None, bos_id=None, eos_id=None, device=None):

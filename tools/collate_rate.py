@@ -8,7 +8,9 @@ first half against second half), on the ids of a --mib MiB batch of the benchmar
 englishcode-32000 shape.  HIP events (torch's) around the launches on ONE stream; GB/s counts the bytes a call reads plus the bytes it writes;
 the yardstick is hipMemcpyAsync device to device of that many bytes (half read, half written), timed the same way.  Three warm-up calls, then
 the median of 20.  --only pairs: the pair lines alone; --only fit: whole-document packing (tm_batch_fit) beside pack on the same batch, and on
-300 000 and 1 048 576 short documents; --append: add to --out under a dated heading instead of replacing it.  (tm_batch_collate / tm_batch_pack wait for the batch's last run before they launch and tm_batch_pack_rows fetches two
+300 000 and 1 048 576 short documents; --only select: tm_batch_collate_select through the identity, the length order and a random
+permutation beside tm_batch_collate of the same documents, and tm_batch_length_order beside torch.sort(stable=True) on 300 000 and 1 048 576
+documents and on either side of a digit boundary of the largest count; --append: add to --out under a dated heading instead of replacing it.  (tm_batch_collate / tm_batch_pack wait for the batch's last run before they launch and tm_batch_pack_rows fetches two
 offsets: host time, outside the kernels but inside the events - with 256 MiB of text it is a few percent of a call.)"""
 import argparse
 import ctypes as C
@@ -45,7 +47,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mib", type=int, default=256)
     ap.add_argument("--out", default=os.path.join("profiles", "collate.txt"))
-    ap.add_argument("--only", choices=["pairs", "fit"], default=None)
+    ap.add_argument("--only", choices=["pairs", "fit", "select"], default=None)
     ap.add_argument("--append", action="store_true")
     a = ap.parse_args()
     L = 2048
@@ -177,10 +179,52 @@ def main():
         fit_lines(bk, k, int(lens_h.sum()), L, ", %d documents" % k)
         N.lib.tm_batch_free(bk)
 
-    if a.only in ("pairs", "fit"):
+    def select_lines():
+        """tm_batch_collate_select, int64 + mask + lengths, every document once: through the identity list, the length order and a random permutation,
+        beside tm_batch_collate of the same documents and the copy yardstick of report().  The selection reads 4 bytes per row more (the list)."""
+        ids = torch.empty((nd, L), dtype=torch.int64, device="cuda")
+        mask = torch.empty((nd, L), dtype=torch.uint8, device="cuda")
+        lens, order = (torch.empty((nd,), dtype=torch.int32, device="cuda") for _ in range(2))
+        how = torch_api._Collate(0, nd, L, 8, pad, N.TM_NONE, N.TM_NONE, 0)
+        med, lo, hi = timed(lambda: N.check(N.lib.tm_batch_collate(b, C.byref(how), st, ids.data_ptr(), mask.data_ptr(), lens.data_ptr())), stream)
+        nbytes = int(lens.to(torch.int64).sum().item()) * 4 + nd * L * 9 + nd * 4
+        report("collate int64 + mask + lengths", nbytes, med, lo, hi)
+        lines.append("  (collate's spread over its 20 repetitions: %.3f ms)" % (hi - lo))
+        N.check(N.lib.tm_batch_length_order(b, 0, nd, 0, st, order.data_ptr(), None))
+        for name, idx in (("identity", torch.arange(nd, dtype=torch.int32, device="cuda")), ("length order", order),
+                          ("random permutation", torch.randperm(nd, device="cuda").to(torch.int32))):
+            smed, lo, hi = timed(lambda: N.check(N.lib.tm_batch_collate_select(b, C.byref(how), idx.data_ptr(), st, ids.data_ptr(), mask.data_ptr(), lens.data_ptr(), None)), stream)
+            report("select, %s" % name, nbytes + nd * 4, smed, lo, hi)
+            lines.append("  (less collate: %+.3f ms)" % (smed - med))
+
+    def order_lines(k, W, top):
+        """tm_batch_length_order on k documents of 0 .. 255 ids each, one of them of `top` ids (tm_batch_load_ids of rows of W two-byte ids), beside
+        torch.sort(stable=True) of the same counts on the same device; the order is checked against torch's"""
+        lens_h = np.random.default_rng(k).integers(0, 256, size=k).astype(np.int32)
+        lens_h[k // 2] = top
+        lens_d, src = torch.from_numpy(lens_h).cuda(), torch.zeros((k, W), dtype=torch.int16, device="cuda")
+        bk = C.c_void_p()
+        N.check(N.lib.tm_batch_create(v.handle, 4096, k, C.byref(bk)))
+        N.check(N.lib.tm_batch_load_ids(bk, src.data_ptr(), k, W, 2, lens_d.data_ptr(), N.TM_NONE, N.TM_NONE, N.TM_NONE, st))
+        N.check(N.lib.tm_batch_totals(bk, None, None))
+        order, cnt = (torch.empty((k,), dtype=torch.int32, device="cuda") for _ in range(2))
+        med, lo, hi = timed(lambda: N.check(N.lib.tm_batch_length_order(bk, 0, k, 0, st, order.data_ptr(), cnt.data_ptr())), stream)
+        tmed, tlo, thi = timed(lambda: torch.sort(lens_d, stable=True), stream)
+        ref = torch.sort(lens_d, stable=True)
+        assert torch.equal(order.to(torch.int64), ref.indices) and torch.equal(cnt, ref.values)
+        lines.append("length_order, %7d documents, largest count %5d  %8.3f ms (%.3f .. %.3f) | torch.sort(stable=True) of the counts: %8.3f ms (%.3f .. %.3f) | ratio %.2f" % (
+            k, top, med, lo, hi, tmed, tlo, thi, tmed / med))
+        print(lines[-1], flush=True)
+        N.lib.tm_batch_free(bk)
+
+    if a.only in ("pairs", "fit", "select"):
         with torch.cuda.stream(stream):
             if a.only == "pairs":
                 pairs_lines()
+            elif a.only == "select":
+                select_lines()
+                for k, W, top in ((300000, 256, 255), (1048576, 256, 255), (1048576, 257, 256), (4096, 65537, 65535), (4096, 65537, 65536)):
+                    order_lines(k, W, top)
             else:
                 fit_lines(b, nd, n_ids, L, "")
                 fit_many(300000)
