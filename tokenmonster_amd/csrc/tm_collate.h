@@ -1,9 +1,11 @@
 // tm_collate.h - what the fixed-shape outputs share (tm_collate.hip: ids, masks, streams; tm_windows.hip: overlapping windows; tm_spans.hip: the
 // spans of the ids in either layout): an output as one flat run of elements with 16-byte stores between an unaligned head and tail, the plan of a
-// row of tm_batch_collate and of tm_batch_windows, the ONE fill body each for ids / mask and for pairs that both layouts' kernels call with their
-// plan, the searches from an id or a stream position to its document, and two documents per row (tm_pairs.hip): its plan and its fill bodies.
+// row of tm_batch_collate and of tm_batch_windows, the ONE walk of rows (fill_walk) that every layout's kernels call with their plan and a value rule, the value
+// rules, the searches from an id or a stream position to its document, and two documents per row (tm_pairs.hip): its plan and its value rules.
 #pragma once
 #include <algorithm>
+#include <initializer_list>
+#include <type_traits>
 
 #include "tm_pipeline.h"
 
@@ -79,71 +81,69 @@ __device__ __forceinline__ RowPlan select_plan(const SelectArgs& s, uint64_t r) 
   return d < s.run_docs ? row_plan(s.a, d) : RowPlan{0, 0, 0};      // (no entries: every column is padding, under either flag)
 }
 
-// ---- the fill of rows: what k_collate_rows / k_collate_select / k_window_rows and k_collate_spans / k_window_spans do with work-item t ------------------------------
-// Args: CollateArgs or WindowArgs (L, pad, bos, eos, ids); plan(r): the RowPlan of row r - row_plan, or win_plan's.  The row of the work-item's
-// first element is a division; when its vector crosses a row end the next row's plan is asked for.
-// MASK: the element is 1 inside the row's entries and 0 on padding (T = uint8_t); else the id.
-template <typename T, bool MASK, typename Args, typename Plan>
-__device__ __forceinline__ void fill_rows(const Args& a, const Flat& f, T* __restrict__ out, uint64_t t, Plan plan) {
+// ---- the walk of rows: what every fill of a [rows, W] output does with work-item t ---------------------------------------------------------------------
+// The ONE skeleton of k_collate_rows / k_collate_select / k_window_rows, k_collate_spans / k_window_spans and the pair kernels (tm_pairs.hip);
+// k_collate_labels (tm_regions.hip) and k_fit_fill (tm_fit.hip) spell the same walk out.  W: the row's width in
+// elements, 32 or 64 bits wide (L, or 2 L for pairs of offsets); plan(r): what the layout knows of row r, of any type; value(p, c): element c
+// of a row whose plan is p.  The row of the work-item's first element is a division; when its vector crosses a row end the next row's plan
+// is asked for.
+template <typename T, uint32_t COMPS = 1, typename Plan, typename Value>
+__device__ __forceinline__ void fill_walk(const Flat& f, const uint32_t& L, T* __restrict__ out, uint64_t t, Plan plan, Value value) {
   constexpr uint32_t PER = 16 / sizeof(T);
+  using W = typename std::conditional<COMPS == 1, uint32_t, uint64_t>::type;
   uint64_t e0;
   uint32_t cnt;
   if (!flat_span<T>(f, t, e0, cnt)) return;
+  const W width = (W)COMPS * L;
   uint64_t r;
-  uint32_t c;
-  if (f.n <= 0xFFFFFFFFull) { r = (uint32_t)e0 / a.L; c = (uint32_t)e0 - (uint32_t)r * a.L; }      // (a 64-bit division costs more than the store it is for)
-  else { r = e0 / a.L; c = (uint32_t)(e0 - r * a.L); }
-  RowPlan p = plan(r);                                 // (r is a row: e0 is an element of the output)
-  const uint32_t hb = a.bos != TM_NONE ? 1u : 0u;
+  W c;
+  if (f.n <= 0xFFFFFFFFull && width <= 0xFFFFFFFFull) { r = (uint32_t)e0 / (uint32_t)width; c = (uint32_t)e0 - (uint32_t)r * (uint32_t)width; }      // (a 64-bit division costs more than the store it is for)
+  else { r = e0 / width; c = (W)(e0 - r * width); }
+  auto p = plan(r);                                    // (r is a row: e0 is an element of the output)
   T vals[PER];
 #pragma unroll
   for (uint32_t k = 0; k < PER; k++) {
     if (k < cnt) {
-      const uint32_t j = c - p.lo;                     // (wraps to a large number left of the entries)
-      uint32_t v;
-      if (MASK) v = j < p.len ? 1u : 0u;
-      else if (j >= p.len) v = a.pad;
-      else if (hb && j == 0) v = a.bos;
-      else if (a.eos != TM_NONE && j == p.len - 1) v = a.eos;
-      else v = a.ids[p.src + (j - hb)];
-      vals[k] = (T)v;
-      if (++c == a.L && k + 1 < cnt) { c = 0; r++; p = plan(r); }      // (another element follows: r is a row)
+      vals[k] = (T)value(p, c);
+      if (++c == width && k + 1 < cnt) { c = 0; r++; p = plan(r); }      // (another element follows: r is a row)
     } else {
       vals[k] = 0;
     }
   }
   flat_store<T>(out, e0, cnt, vals);
 }
-// The pairs of the ids laid out like the rows: the output [rows, L, 2] is one flat run of 2 * rows * L elements of T, element e is component
-// e & 1 of column (e >> 1) % L of row (e >> 1) / L.  A column that holds a content id gets that id's pair; BOS, EOS and padding get (0, 0).
-template <typename T, typename Args, typename Plan>
-__device__ __forceinline__ void fill_spans(const Args& a, const Flat& f, const uint32_t* __restrict__ spans, T* __restrict__ out, uint64_t t, Plan plan) {
-  constexpr uint32_t PER = 16 / sizeof(T);
-  uint64_t e0;
-  uint32_t cnt;
-  if (!flat_span<T>(f, t, e0, cnt)) return;
-  const uint64_t L2 = 2ull * a.L;
-  uint64_t r;
-  uint64_t c;                                         // element of the row: 2 * column + component
-  if (f.n <= 0xFFFFFFFFull && L2 <= 0xFFFFFFFFull) { r = (uint32_t)e0 / (uint32_t)L2; c = (uint32_t)e0 - (uint32_t)r * (uint32_t)L2; }
-  else { r = e0 / L2; c = e0 - r * L2; }
-  RowPlan p = plan(r);
-  const uint32_t hb = a.bos != TM_NONE ? 1u : 0u;
-  T vals[PER];
-#pragma unroll
-  for (uint32_t k = 0; k < PER; k++) {
-    if (k < cnt) {
-      const uint32_t j = (uint32_t)(c >> 1) - p.lo;      // (wraps to a large number left of the entries)
-      uint32_t v = 0;
-      if (j < p.len && !(hb && j == 0) && !(a.eos != TM_NONE && j == p.len - 1)) v = spans[2 * (p.src + (j - hb)) + (c & 1u)];
-      vals[k] = (T)v;
-      if (++c == L2 && k + 1 < cnt) { c = 0; r++; p = plan(r); }
-    } else {
-      vals[k] = 0;
-    }
+
+// The value rules of a RowPlan (k_collate_rows, k_collate_select, k_window_rows; k_collate_spans, k_window_spans).  Args: CollateArgs or
+// WindowArgs (pad, bos, eos, ids).  MASK: the element is 1 inside the row's entries and 0 on padding (T = uint8_t); else the id.
+template <bool MASK, typename Args>
+struct RowValue {
+  const Args& a;
+  __device__ __forceinline__ uint32_t operator()(const RowPlan p, uint32_t c) const {
+    const uint32_t hb = a.bos != TM_NONE ? 1u : 0u;
+    const uint32_t j = c - p.lo;                       // (wraps to a large number left of the entries)
+    uint32_t v;
+    if (MASK) v = j < p.len ? 1u : 0u;
+    else if (j >= p.len) v = a.pad;
+    else if (hb && j == 0) v = a.bos;
+    else if (a.eos != TM_NONE && j == p.len - 1) v = a.eos;
+    else v = a.ids[p.src + (j - hb)];
+    return v;
   }
-  flat_store<T>(out, e0, cnt, vals);
-}
+};
+// The pairs of the ids laid out like the rows: the output [rows, L, 2] is one flat run of rows of 2 L elements of T, element c of a row is
+// component c & 1 of column c >> 1.  A column that holds a content id gets that id's pair; BOS, EOS and padding get (0, 0).
+template <typename Args>
+struct SpanValue {
+  const Args& a;
+  const uint32_t* __restrict__ spans;
+  __device__ __forceinline__ uint32_t operator()(const RowPlan p, const uint64_t& c) const {
+    const uint32_t hb = a.bos != TM_NONE ? 1u : 0u;
+    const uint32_t j = (uint32_t)(c >> 1) - p.lo;      // (wraps to a large number left of the entries)
+    uint32_t v = 0;
+    if (j < p.len && !(hb && j == 0) && !(a.eos != TM_NONE && j == p.len - 1)) v = spans[2 * (p.src + (j - hb)) + (c & 1u)];
+    return v;
+  }
+};
 
 // ---- an id of a run -> its document ----------------------------------------------------------------------------------------------------------------
 // the last document whose first id is not behind id t, over tok_offsets[0 .. ndocs) (documents without ids share their offset with the next)
@@ -258,80 +258,60 @@ __device__ __forceinline__ PairWinPlan pair_win_plan(const PairArgs& a, uint64_t
   return w;
 }
 
-// The fill of pair rows: fill_rows above with a PairPlan.  plan(r): pair_plan, or pair_win_plan's.  A column's value follows from its offset
+// The value rules of a PairPlan (k_pair_rows, k_pair_window_rows; k_pair_spans, k_pair_window_spans).  A column's value follows from its offset
 // j = c - lo inside the entries and the boundaries bos | A | separators | B | eos.
 // WHAT: 0 = the id (T of 2, 4 or 8 bytes); 1 = the mask, 1 on an entry; 2 = the type, 1 on B's ids and eos (T = uint8_t)
-template <typename T, int WHAT, typename Plan>
-__device__ __forceinline__ void fill_pair_rows(const PairArgs& a, const Flat& f, T* __restrict__ out, uint64_t t, Plan plan) {
-  constexpr uint32_t PER = 16 / sizeof(T);
-  uint64_t e0;
-  uint32_t cnt;
-  if (!flat_span<T>(f, t, e0, cnt)) return;
-  uint64_t r;
-  uint32_t c;
-  if (f.n <= 0xFFFFFFFFull) { r = (uint32_t)e0 / a.L; c = (uint32_t)e0 - (uint32_t)r * a.L; }      // (a 64-bit division costs more than the store it is for)
-  else { r = e0 / a.L; c = (uint32_t)(e0 - r * a.L); }
-  PairPlan p = plan(r);                                // (r is a row: e0 is an element of the output)
-  const uint32_t hb = a.bos != TM_NONE ? 1u : 0u;
-  T vals[PER];
-#pragma unroll
-  for (uint32_t k = 0; k < PER; k++) {
-    if (k < cnt) {
-      const uint32_t j = c - p.lo;                     // (wraps to a large number left of the entries)
-      const uint32_t ea = hb + p.na, eb = ea + a.nsep; // (the ends of A and of the separators)
-      uint32_t v;
-      if (WHAT == 1) v = j < p.len ? 1u : 0u;
-      else if (WHAT == 2) v = (j >= eb && j < p.len) ? 1u : 0u;
-      else if (j >= p.len) v = a.pad;
-      else if (j < hb) v = a.bos;
-      else if (j < ea) v = a.ids[p.src_a + (j - hb)];
-      else if (j < eb) v = a.sep;
-      else if (j < eb + p.nb) v = a.ids[p.src_b + (j - eb)];
-      else v = a.eos;
-      vals[k] = (T)v;
-      if (++c == a.L && k + 1 < cnt) { c = 0; r++; p = plan(r); }      // (another element follows: r is a row)
-    } else {
-      vals[k] = 0;
-    }
+template <int WHAT>
+struct PairValue {
+  const PairArgs& a;
+  __device__ __forceinline__ uint32_t operator()(const PairPlan p, uint32_t c) const {
+    const uint32_t hb = a.bos != TM_NONE ? 1u : 0u;
+    const uint32_t j = c - p.lo;                       // (wraps to a large number left of the entries)
+    const uint32_t ea = hb + p.na, eb = ea + a.nsep;   // (the ends of A and of the separators)
+    uint32_t v;
+    if (WHAT == 1) v = j < p.len ? 1u : 0u;
+    else if (WHAT == 2) v = (j >= eb && j < p.len) ? 1u : 0u;
+    else if (j >= p.len) v = a.pad;
+    else if (j < hb) v = a.bos;
+    else if (j < ea) v = a.ids[p.src_a + (j - hb)];
+    else if (j < eb) v = a.sep;
+    else if (j < eb + p.nb) v = a.ids[p.src_b + (j - eb)];
+    else v = a.eos;
+    return v;
   }
-  flat_store<T>(out, e0, cnt, vals);
-}
-// The pairs of the ids laid out like the pair rows (the flat output of fill_spans): a content column of either side gets its id's pair, which
+};
+// The pairs of the ids laid out like the pair rows (the flat output of SpanValue): a content column of either side gets its id's pair, which
 // counts from that side's own document; specials and padding get (0, 0).
-template <typename T, typename Plan>
-__device__ __forceinline__ void fill_pair_spans(const PairArgs& a, const Flat& f, const uint32_t* __restrict__ spans, T* __restrict__ out, uint64_t t, Plan plan) {
-  constexpr uint32_t PER = 16 / sizeof(T);
-  uint64_t e0;
-  uint32_t cnt;
-  if (!flat_span<T>(f, t, e0, cnt)) return;
-  const uint64_t L2 = 2ull * a.L;
-  uint64_t r;
-  uint64_t c;                                         // element of the row: 2 * column + component
-  if (f.n <= 0xFFFFFFFFull && L2 <= 0xFFFFFFFFull) { r = (uint32_t)e0 / (uint32_t)L2; c = (uint32_t)e0 - (uint32_t)r * (uint32_t)L2; }
-  else { r = e0 / L2; c = e0 - r * L2; }
-  PairPlan p = plan(r);
-  const uint32_t hb = a.bos != TM_NONE ? 1u : 0u;
-  T vals[PER];
-#pragma unroll
-  for (uint32_t k = 0; k < PER; k++) {
-    if (k < cnt) {
-      const uint32_t j = (uint32_t)(c >> 1) - p.lo;      // (wraps to a large number left of the entries)
-      const uint32_t ea = hb + p.na, eb = ea + a.nsep;
-      uint32_t v = 0;
-      if (j >= hb && j < ea) v = spans[2 * (p.src_a + (j - hb)) + (c & 1u)];
-      else if (j >= eb && j < eb + p.nb) v = spans[2 * (p.src_b + (j - eb)) + (c & 1u)];
-      vals[k] = (T)v;
-      if (++c == L2 && k + 1 < cnt) { c = 0; r++; p = plan(r); }
-    } else {
-      vals[k] = 0;
-    }
+struct PairSpanValue {
+  const PairArgs& a;
+  const uint32_t* __restrict__ spans;
+  __device__ __forceinline__ uint32_t operator()(const PairPlan p, const uint64_t& c) const {
+    const uint32_t hb = a.bos != TM_NONE ? 1u : 0u;
+    const uint32_t j = (uint32_t)(c >> 1) - p.lo;      // (wraps to a large number left of the entries)
+    const uint32_t ea = hb + p.na, eb = ea + a.nsep;
+    uint32_t v = 0;
+    if (j >= hb && j < ea) v = spans[2 * (p.src_a + (j - hb)) + (c & 1u)];
+    else if (j >= eb && j < eb + p.nb) v = spans[2 * (p.src_b + (j - eb)) + (c & 1u)];
+    return v;
   }
-  flat_store<T>(out, e0, cnt, vals);
-}
+};
 
 constexpr uint64_t COLLATE_MAX_ELEMS = 1ull << 36;       // elements of one output: keeps every grid below 2^31 workgroups
 
 inline uint32_t grid_of(uint64_t items) { return (uint32_t)((items + 255) / 256); }
+// The launch of a flat fill: kern(a, f, rest...) over the n elements of T at `out` - their Flat, one work-item per vector or single element
+// and at least min_items (the rows, where the first work-items write per-row outputs), GROUP work-items per workgroup of 256.
+template <uint32_t GROUP = 256, typename K, typename T, typename A, typename... Rest>
+inline void launch_flat(K kern, hipStream_t st, const T* out, uint64_t n, uint64_t min_items, const A& a, Rest... rest) {
+  const Flat f = flat_of(out, n, sizeof(T));
+  const uint64_t items = std::max<uint64_t>(flat_items(f, sizeof(T)), min_items);
+  TM_LAUNCH(kern, (uint32_t)((items + GROUP - 1) / GROUP), 256, 0, st, a, f, rest...);
+}
+// id_bytes (2, 4 or 8: checked) -> f(T{}) with T the id type; span_bytes / label_bytes (4 or 8: checked) -> f(T4{}) or f(T8{})
+template <typename F>
+inline void with_id_type(uint32_t id_bytes, F f) { if (id_bytes == 2) f(uint16_t{}); else if (id_bytes == 4) f(uint32_t{}); else f(uint64_t{}); }
+template <typename T4, typename T8, typename F>
+inline void with_wide_type(uint32_t bytes, F f) { if (bytes == 4) f(T4{}); else f(T8{}); }
 inline int launch_check() {
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? TM_OK : hip_fail(e, "kernel launch");
@@ -339,6 +319,13 @@ inline int launch_check() {
 
 // the arguments every layout shares (ids_out: only that it is there)
 int check_how(const tm_batch* b, const tm_collate* how, const void* ids_out, const char* who);
+// ... and its parts in front of and behind a layout's own flags, for the pairs (given: no argument is null; specials: pad, bos, [sep,] eos)
+int check_row_shape(bool given, uint32_t id_bytes, uint32_t row_len, uint32_t pad_id, const char* who);
+int check_ids_fit(const tm_batch* b, uint32_t id_bytes, std::initializer_list<uint32_t> specials, const char* who);
+// a row holds its ns specials, and `rows` rows stay below COLLATE_MAX_ELEMS (what: the documents, pairs or rows to split).  Where an entry
+// point makes the two checks apart, or only the second, it asks for one at a time: rows = 0, or ns = 0, switches the other off.
+int check_row_room(const char* who, uint32_t row_len, uint32_t ns, uint64_t rows, const char* what);
+int check_rows_cap(const char* who, uint64_t rows_cap, uint64_t rows);
 // tm_spans.hip: no document of the run is 2^32 bytes or longer (offsets are 32 bits)
 int spans_check_lengths(tm_batch* b, const char* who);
 // tm_windows.hip: the batch's window buffer for nd documents (or pairs) - win_off[cap + 1] | block sums of the scan, its total behind them |

@@ -19,13 +19,13 @@
 namespace tmh {
 
 // ---- k_collate_rows: one document per row (the flat output and the plan of a row: tm_collate.h) ------------------------------------------------
-// The fill is fill_rows (tm_collate.h) with the plan of one document per row.  lengths (ids launch only, may be null): the first `rows`
+// The fill is fill_walk (tm_collate.h) with the plan of one document per row and RowValue.  lengths (ids launch only, may be null): the first `rows`
 // work-items write a row's length each.
 template <typename T, bool MASK>
 __global__ __launch_bounds__(256) void k_collate_rows(CollateArgs a, Flat f, T* __restrict__ out, uint32_t* __restrict__ lengths) {
   const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (!MASK && lengths && t < a.rows) lengths[t] = row_plan(a, t).len;
-  fill_rows<T, MASK>(a, f, out, t, [&](uint64_t r) { return row_plan(a, r); });
+  fill_walk<T>(f, a.L, out, t, [&](uint64_t r) { return row_plan(a, r); }, RowValue<MASK, CollateArgs>{a});
 }
 
 // ---- k_collate_select: document doc_index[r] in row r ---------------------------------------------------------------------------------------------
@@ -44,7 +44,7 @@ __global__ __launch_bounds__(256) void k_collate_select(SelectArgs s, Flat f, T*
   if (t0 < f.nvec) {                                   // rows of the first and the last element of this workgroup's vectors
     const uint64_t e0 = f.head + t0 * PER, e1 = f.head + std::min<uint64_t>(t0 + 256 * SEL_VECS, f.nvec) * PER - 1;
     uint64_t r1;
-    if (f.n <= 0xFFFFFFFFull) { r0 = (uint32_t)e0 / s.a.L; r1 = (uint32_t)e1 / s.a.L; }      // (as in fill_rows: no 64-bit division where 32 bits do)
+    if (f.n <= 0xFFFFFFFFull) { r0 = (uint32_t)e0 / s.a.L; r1 = (uint32_t)e1 / s.a.L; }      // (as in fill_walk: no 64-bit division where 32 bits do)
     else { r0 = e0 / s.a.L; r1 = e1 / s.a.L; }
     staged = (uint32_t)std::min<uint64_t>(r1 - r0 + 1, SEL_STAGE);
   }
@@ -54,7 +54,7 @@ __global__ __launch_bounds__(256) void k_collate_select(SelectArgs s, Flat f, T*
   for (uint32_t k = 0; k < SEL_VECS; k++) {
     const uint64_t t = t0 + k * 256 + threadIdx.x;
     if (!MASK && lengths && t < s.a.rows) lengths[t] = select_plan(s, t).len;
-    fill_rows<T, MASK>(s.a, f, out, t, [&](uint64_t r) { return r - r0 < staged ? plans[r - r0] : select_plan(s, r); });
+    fill_walk<T>(f, s.a.L, out, t, [&](uint64_t r) { return r - r0 < staged ? plans[r - r0] : select_plan(s, r); }, RowValue<MASK, CollateArgs>{s.a});
   }
 }
 // the rows whose index is no document of the run: one workgroup, one plain store (bad_out may be page-locked host memory)
@@ -173,43 +173,54 @@ __global__ __launch_bounds__(256) void k_ids_from_rows(LoadArgs a, const uint64_
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------------------------------
 // the arguments both layouts share (ids_out: only that it is there)
-int check_how(const tm_batch* b, const tm_collate* how, const void* ids_out, const char* who) {
-  if (!b || !how || !ids_out) return set_error(TM_E_INVALID, "%s: null argument", who);
-  if (how->id_bytes != 2 && how->id_bytes != 4 && how->id_bytes != 8) return set_error(TM_E_INVALID, "%s: id_bytes %u (2, 4 or 8)", who, how->id_bytes);
-  if (how->row_len == 0) return set_error(TM_E_INVALID, "%s: row_len 0", who);
-  if (how->pad_id == TM_NONE) return set_error(TM_E_INVALID, "%s: pad_id must be given", who);
-  if (how->flags & ~(TM_COLLATE_PAD_LEFT | TM_COLLATE_KEEP_TAIL)) return set_error(TM_E_INVALID, "%s: unknown flags %#x", who, how->flags);
-  if (how->id_bytes == 2) {
+// ... in the two parts a layout's own checks (its flags) stand between: the shape of a row, and that the batch's ids fit the output
+int check_row_shape(bool given, uint32_t id_bytes, uint32_t row_len, uint32_t pad_id, const char* who) {
+  if (!given) return set_error(TM_E_INVALID, "%s: null argument", who);
+  if (id_bytes != 2 && id_bytes != 4 && id_bytes != 8) return set_error(TM_E_INVALID, "%s: id_bytes %u (2, 4 or 8)", who, id_bytes);
+  if (row_len == 0) return set_error(TM_E_INVALID, "%s: row_len 0", who);
+  if (pad_id == TM_NONE) return set_error(TM_E_INVALID, "%s: pad_id must be given", who);
+  return TM_OK;
+}
+int check_ids_fit(const tm_batch* b, uint32_t id_bytes, std::initializer_list<uint32_t> specials, const char* who) {
+  if (id_bytes == 2) {
     if (b->vocab->host.n_ids > 65536u) return set_error(TM_E_INVALID, "%s: two-byte ids with a vocabulary of %u ids", who, b->vocab->host.n_ids);
-    for (uint32_t s : {how->pad_id, how->bos_id, how->eos_id})
+    for (uint32_t s : specials)
       if (s != TM_NONE && s >= 65536u) return set_error(TM_E_INVALID, "%s: special id %u does not fit two bytes", who, s);
   }
   if (!b->has_output) return set_error(TM_E_INVALID, "%s: the batch holds no ids (no completed tm_batch_run or tm_batch_load_ids since the last upload)", who);
+  return TM_OK;
+}
+int check_how(const tm_batch* b, const tm_collate* how, const void* ids_out, const char* who) {
+  int rc = check_row_shape(b && how && ids_out, how ? how->id_bytes : 0, how ? how->row_len : 0, how ? how->pad_id : 0, who);
+  if (rc != TM_OK) return rc;
+  if (how->flags & ~(TM_COLLATE_PAD_LEFT | TM_COLLATE_KEEP_TAIL)) return set_error(TM_E_INVALID, "%s: unknown flags %#x", who, how->flags);
+  if ((rc = check_ids_fit(b, how->id_bytes, {how->pad_id, how->bos_id, how->eos_id}, who)) != TM_OK) return rc;
   if ((uint64_t)how->first_doc + how->ndocs > b->ndocs)
     return set_error(TM_E_INVALID, "%s: documents %u .. %llu of a run of %u", who, how->first_doc, (unsigned long long)how->first_doc + how->ndocs, b->ndocs);
   return TM_OK;
 }
+int check_row_room(const char* who, uint32_t row_len, uint32_t ns, uint64_t rows, const char* what) {
+  if (row_len < ns) return set_error(TM_E_INVALID, "%s: row_len %u holds no %u specials", who, row_len, ns);
+  if (rows * row_len > COLLATE_MAX_ELEMS) return set_error(TM_E_LIMIT, "%s: %llu rows of %u ids in one call (split the %s)", who, (unsigned long long)rows, row_len, what);
+  return TM_OK;
+}
+int check_rows_cap(const char* who, uint64_t rows_cap, uint64_t rows) {
+  if (rows > rows_cap) return set_error(TM_E_NOSPACE, "%s: rows_cap %llu < %llu rows required", who, (unsigned long long)rows_cap, (unsigned long long)rows);
+  return TM_OK;
+}
 
-template <typename T>
-static void launch_collate(const CollateArgs& a, void* ids_out, uint32_t* lengths_out, hipStream_t st) {
-  const Flat f = flat_of(ids_out, (uint64_t)a.rows * a.L, sizeof(T));
-  const uint64_t items = std::max<uint64_t>(flat_items(f, sizeof(T)), lengths_out ? a.rows : 0);
-  const auto kern = k_collate_rows<T, false>;
-  TM_LAUNCH(kern, grid_of(items), 256, 0, st, a, f, static_cast<T*>(ids_out), lengths_out);
+// the launches: ids (lengths_out may be given) or, MASK, the mask; a workgroup of the selection takes 256 * SEL_VECS work-items
+template <typename T, bool MASK>
+static void launch_collate(const CollateArgs& a, void* out, hipStream_t st, uint32_t* lengths_out = nullptr) {
+  launch_flat(k_collate_rows<T, MASK>, st, static_cast<T*>(out), (uint64_t)a.rows * a.L, lengths_out ? a.rows : 0, a, static_cast<T*>(out), lengths_out);
 }
-static uint32_t select_grid(uint64_t items) { return (uint32_t)((items + 256 * SEL_VECS - 1) / (256 * SEL_VECS)); }
-template <typename T>
-static void launch_select(const SelectArgs& s, void* ids_out, uint32_t* lengths_out, hipStream_t st) {
-  const Flat f = flat_of(ids_out, (uint64_t)s.a.rows * s.a.L, sizeof(T));
-  const uint64_t items = std::max<uint64_t>(flat_items(f, sizeof(T)), lengths_out ? s.a.rows : 0);
-  const auto kern = k_collate_select<T, false>;
-  TM_LAUNCH(kern, select_grid(items), 256, 0, st, s, f, static_cast<T*>(ids_out), lengths_out);
+template <typename T, bool MASK>
+static void launch_select(const SelectArgs& s, void* out, hipStream_t st, uint32_t* lengths_out = nullptr) {
+  launch_flat<256 * SEL_VECS>(k_collate_select<T, MASK>, st, static_cast<T*>(out), (uint64_t)s.a.rows * s.a.L, lengths_out ? s.a.rows : 0, s, static_cast<T*>(out), lengths_out);
 }
-template <typename T>
-static void launch_pack_ids(const PackArgs& a, void* ids_out, uint64_t n, hipStream_t st) {
-  const Flat f = flat_of(ids_out, n, sizeof(T));
-  const auto kern = k_pack_stream<T, 0>;
-  TM_LAUNCH(kern, grid_of(flat_items(f, sizeof(T))), 256, 0, st, a, f, static_cast<T*>(ids_out));
+template <typename T, int WHAT>
+static void launch_pack(const PackArgs& a, void* out, uint64_t n, hipStream_t st) {
+  launch_flat(k_pack_stream<T, WHAT>, st, static_cast<T*>(out), n, 0, a, static_cast<T*>(out));
 }
 
 // stream length of the documents [first, first + nd) with `sep` separators each: two offsets from the device (synchronizes like tm_batch_totals)
@@ -229,8 +240,7 @@ static int pack_rows(tm_batch* b, const tm_collate* how, const void* ids_out, co
   if (rc != TM_OK) return rc;
   if ((rc = enter_device(b->vocab)) != TM_OK || (rc = ensure_output(b)) != TM_OK || (rc = pack_stream_len(b, how, stream_len)) != TM_OK) return rc;
   *rows = (*stream_len + how->row_len - 1) / how->row_len;
-  if (*rows * how->row_len > COLLATE_MAX_ELEMS) return set_error(TM_E_LIMIT, "%s: %llu rows of %u ids in one call (split the documents)", who, (unsigned long long)*rows, how->row_len);
-  return TM_OK;
+  return check_row_room(who, how->row_len, 0, *rows, "documents");
 }
 
 }  // namespace tmh
@@ -243,21 +253,14 @@ int tm_batch_collate(tm_batch* b, const tm_collate* how, void* stream, void* ids
   int rc = check_how(b, how, ids_out, "tm_batch_collate");
   if (rc != TM_OK) return rc;
   const uint32_t ns = (how->bos_id != TM_NONE ? 1u : 0u) + (how->eos_id != TM_NONE ? 1u : 0u);
-  if (how->row_len < ns) return set_error(TM_E_INVALID, "tm_batch_collate: row_len %u holds no %u specials", how->row_len, ns);
-  if ((uint64_t)how->ndocs * how->row_len > COLLATE_MAX_ELEMS) return set_error(TM_E_LIMIT, "tm_batch_collate: %u rows of %u ids in one call (split the documents)", how->ndocs, how->row_len);
+  if ((rc = check_row_room("tm_batch_collate", how->row_len, ns, how->ndocs, "documents")) != TM_OK) return rc;
   if ((rc = enter_device(b->vocab)) != TM_OK || (rc = ensure_output(b)) != TM_OK) return rc;      // (waits for the run: the ids are all there)
   if (how->ndocs == 0) return TM_OK;
   hipStream_t st = (hipStream_t)stream;
   (void)hipGetLastError();
   const CollateArgs a{b->d_out, b->d_tok_offsets + how->first_doc, how->ndocs, how->row_len, how->pad_id, how->bos_id, how->eos_id, how->flags};
-  if (how->id_bytes == 2) launch_collate<uint16_t>(a, ids_out, lengths_out, st);
-  else if (how->id_bytes == 4) launch_collate<uint32_t>(a, ids_out, lengths_out, st);
-  else launch_collate<uint64_t>(a, ids_out, lengths_out, st);
-  if (mask_out) {
-    const Flat f = flat_of(mask_out, (uint64_t)a.rows * a.L, 1);
-    const auto kern = k_collate_rows<uint8_t, true>;
-    TM_LAUNCH(kern, grid_of(flat_items(f, 1)), 256, 0, st, a, f, mask_out, (uint32_t*)nullptr);
-  }
+  with_id_type(how->id_bytes, [&](auto z) { launch_collate<decltype(z), false>(a, ids_out, st, lengths_out); });
+  if (mask_out) launch_collate<uint8_t, true>(a, mask_out, st);
   return launch_check();
 }
 
@@ -272,22 +275,15 @@ int tm_batch_collate_select(tm_batch* b, const tm_collate* how, const uint32_t* 
   if (how->first_doc != 0) return set_error(TM_E_INVALID, "%s: first_doc %u (the indices count from the run's first document: 0)", who, how->first_doc);
   if (how->ndocs && !doc_index) return set_error(TM_E_INVALID, "%s: null doc_index", who);
   const uint32_t ns = (how->bos_id != TM_NONE ? 1u : 0u) + (how->eos_id != TM_NONE ? 1u : 0u);
-  if (how->row_len < ns) return set_error(TM_E_INVALID, "%s: row_len %u holds no %u specials", who, how->row_len, ns);
-  if ((uint64_t)how->ndocs * how->row_len > COLLATE_MAX_ELEMS) return set_error(TM_E_LIMIT, "%s: %u rows of %u ids in one call (split the rows)", who, how->ndocs, how->row_len);
+  if ((rc = check_row_room(who, how->row_len, ns, how->ndocs, "rows")) != TM_OK) return rc;
   if ((rc = enter_device(b->vocab)) != TM_OK || (rc = ensure_output(b)) != TM_OK) return rc;      // (waits for the run: the ids are all there)
   hipStream_t st = (hipStream_t)stream;
   (void)hipGetLastError();
   if (bad_out) TM_LAUNCH(k_select_bad, 1, 1024, 0, st, doc_index, how->ndocs, b->ndocs, bad_out);
   if (how->ndocs == 0) return bad_out ? launch_check() : TM_OK;
   const SelectArgs s{CollateArgs{b->d_out, b->d_tok_offsets, how->ndocs, how->row_len, how->pad_id, how->bos_id, how->eos_id, how->flags}, doc_index, b->ndocs};
-  if (how->id_bytes == 2) launch_select<uint16_t>(s, ids_out, lengths_out, st);
-  else if (how->id_bytes == 4) launch_select<uint32_t>(s, ids_out, lengths_out, st);
-  else launch_select<uint64_t>(s, ids_out, lengths_out, st);
-  if (mask_out) {
-    const Flat f = flat_of(mask_out, (uint64_t)s.a.rows * s.a.L, 1);
-    const auto kern = k_collate_select<uint8_t, true>;
-    TM_LAUNCH(kern, select_grid(flat_items(f, 1)), 256, 0, st, s, f, mask_out, (uint32_t*)nullptr);
-  }
+  with_id_type(how->id_bytes, [&](auto z) { launch_select<decltype(z), false>(s, ids_out, st, lengths_out); });
+  if (mask_out) launch_select<uint8_t, true>(s, mask_out, st);
   return launch_check();
 }
 
@@ -301,26 +297,15 @@ int tm_batch_pack_rows(tm_batch* b, const tm_collate* how, uint64_t* rows_needed
 int tm_batch_pack(tm_batch* b, const tm_collate* how, void* stream, uint64_t rows_cap, void* ids_out, uint32_t* doc_index_out, uint32_t* position_out) {
   uint64_t stream_len = 0, rows = 0;
   int rc = pack_rows(b, how, ids_out, "tm_batch_pack", &stream_len, &rows);
-  if (rc != TM_OK) return rc;
-  if (rows > rows_cap) return set_error(TM_E_NOSPACE, "tm_batch_pack: rows_cap %llu < %llu rows required", (unsigned long long)rows_cap, (unsigned long long)rows);
+  if (rc != TM_OK || (rc = check_rows_cap("tm_batch_pack", rows_cap, rows)) != TM_OK) return rc;
   if (rows == 0) return TM_OK;
   hipStream_t st = (hipStream_t)stream;
   (void)hipGetLastError();
   const uint64_t n = rows * how->row_len;
   const PackArgs a{b->d_out, b->d_tok_offsets + how->first_doc, how->ndocs, how->pad_id, how->eos_id, stream_len};
-  if (how->id_bytes == 2) launch_pack_ids<uint16_t>(a, ids_out, n, st);
-  else if (how->id_bytes == 4) launch_pack_ids<uint32_t>(a, ids_out, n, st);
-  else launch_pack_ids<uint64_t>(a, ids_out, n, st);
-  if (doc_index_out) {
-    const Flat f = flat_of(doc_index_out, n, 4);
-    const auto kern = k_pack_stream<uint32_t, 1>;
-    TM_LAUNCH(kern, grid_of(flat_items(f, 4)), 256, 0, st, a, f, doc_index_out);
-  }
-  if (position_out) {
-    const Flat f = flat_of(position_out, n, 4);
-    const auto kern = k_pack_stream<uint32_t, 2>;
-    TM_LAUNCH(kern, grid_of(flat_items(f, 4)), 256, 0, st, a, f, position_out);
-  }
+  with_id_type(how->id_bytes, [&](auto z) { launch_pack<decltype(z), 0>(a, ids_out, n, st); });
+  if (doc_index_out) launch_pack<uint32_t, 1>(a, doc_index_out, n, st);
+  if (position_out) launch_pack<uint32_t, 2>(a, position_out, n, st);
   return launch_check();
 }
 
@@ -360,14 +345,10 @@ int tm_batch_load_ids(tm_batch* b, const void* rows, uint32_t nrows, uint32_t ro
     return TM_OK;
   }
   const uint32_t g1 = (nrows + 3) / 4;
-  if (id_bytes == 2) TM_LAUNCH(k_row_extents<uint16_t>, g1, 256, 0, st, a, b->d_doc_ntok, b->d_doc_events, b->d_doc_missing, b->d_totals, b->d_error);
-  else if (id_bytes == 4) TM_LAUNCH(k_row_extents<uint32_t>, g1, 256, 0, st, a, b->d_doc_ntok, b->d_doc_events, b->d_doc_missing, b->d_totals, b->d_error);
-  else TM_LAUNCH(k_row_extents<uint64_t>, g1, 256, 0, st, a, b->d_doc_ntok, b->d_doc_events, b->d_doc_missing, b->d_totals, b->d_error);
+  with_id_type(id_bytes, [&](auto z) { TM_LAUNCH(k_row_extents<decltype(z)>, g1, 256, 0, st, a, b->d_doc_ntok, b->d_doc_events, b->d_doc_missing, b->d_totals, b->d_error); });
   scan_u32(b->d_doc_ntok, nrows, b->d_scan_tmp, b->d_totals + 1, b->d_tok_offsets, st);
   const uint32_t g2 = grid_of((bound + 3) / 4);
-  if (id_bytes == 2) TM_LAUNCH(k_ids_from_rows<uint16_t>, g2, 256, 0, st, a, b->d_tok_offsets, b->d_doc_events, b->d_out);
-  else if (id_bytes == 4) TM_LAUNCH(k_ids_from_rows<uint32_t>, g2, 256, 0, st, a, b->d_tok_offsets, b->d_doc_events, b->d_out);
-  else TM_LAUNCH(k_ids_from_rows<uint64_t>, g2, 256, 0, st, a, b->d_tok_offsets, b->d_doc_events, b->d_out);
+  with_id_type(id_bytes, [&](auto z) { TM_LAUNCH(k_ids_from_rows<decltype(z)>, g2, 256, 0, st, a, b->d_tok_offsets, b->d_doc_events, b->d_out); });
   int rc = launch_check();
   if (rc == TM_OK) b->has_output = true;
   return rc;

@@ -15,8 +15,8 @@
 //      every tile's entry opener and first row (a tile the chain jumps over has none), and the number of rows.
 //   4. k_fit_rows: per tile with an entry, the chain inside the tile walked in LDS; the row table (stream position of the row's first entry,
 //      entries, document) of every row its openers open, the whole rows of a long document written by the whole workgroup.
-//   5. k_fit_fill: tm_collate.hip's streaming fill - the output one flat run of elements, one 16-byte vector per work-item - where element
-//      (r, c) is stream position P_r + c, its document found by a DocCursor that starts at the row's own document.
+//   5. k_fit_fill: the walk of rows of tm_collate.h's fill_walk, spelled out (says why), with a FitRow of the table as
+//      the plan of a row and the value rule: element (r, c) is stream position P_r + c, its document found by a DocCursor that starts at the row's own document.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -230,13 +230,7 @@ static FitBuf fit_buf(const tm_batch* b) {
   return w;
 }
 static int fit_reserve(tm_batch* b, uint32_t nd) {
-  if (b->d_fit && nd <= b->fit_cap) return TM_OK;
-  const uint32_t cap = (uint32_t)std::min<uint64_t>((uint64_t)nd + nd / 4 + 1024, 0xFFFFFFFFull);
-  const uint64_t old_bytes = b->d_fit ? fit_bytes(b->fit_cap) : 0;
-  b->fit_cap = 0;
-  const int rc = batch_replace(b, (void**)&b->d_fit, old_bytes, fit_bytes(nd), fit_bytes(cap), "fit plan");
-  if (rc == TM_OK) b->fit_cap = cap;
-  return rc;
+  return batch_reserve_docs(b, (void**)&b->d_fit, &b->fit_cap, nd, fit_bytes, "fit plan");
 }
 
 // what both calls share: the arguments, stages 1 to 3 on the stream of the batch's last run, and the number of rows read back from it
@@ -259,16 +253,14 @@ static int fit_plan(tm_batch* b, const tm_collate* how, const void* out, const c
   TM_LAUNCH(k_fit_resolve, 1, 64, 0, st, fa, w.exits, ntiles, w.tile_entry, w.tile_row, w.total);
   if ((rc = launch_check()) != TM_OK) return rc;
   if ((rc = small_d2h(b, rows, w.total, 8, st)) != TM_OK || (rc = small_sync(b, st)) != TM_OK) return rc;
-  if (*rows * how->row_len > COLLATE_MAX_ELEMS) return set_error(TM_E_LIMIT, "%s: %llu rows of %u ids in one call (split the documents)", who, (unsigned long long)*rows, how->row_len);
-  return TM_OK;
+  return check_row_room(who, how->row_len, 0, *rows, "documents");
 }
 
-template <typename T>
-static void launch_fit_ids(const FitFill& a, void* ids_out, uint32_t* lengths_out, uint32_t* row_doc_out, uint32_t* row_start_out, hipStream_t st) {
-  const Flat f = flat_of(ids_out, a.rows * a.L, sizeof(T));
-  const uint64_t items = std::max<uint64_t>(flat_items(f, sizeof(T)), (lengths_out || row_doc_out || row_start_out) ? a.rows : 0);
-  const auto kern = k_fit_fill<T, 0>;
-  TM_LAUNCH(kern, grid_of(items), 256, 0, st, a, f, static_cast<T*>(ids_out), lengths_out, row_doc_out, row_start_out);
+// WHAT 0 = ids (the per-row outputs may be given), 1 = doc_index, 2 = position
+template <typename T, int WHAT>
+static void launch_fit(const FitFill& a, void* out, hipStream_t st, uint32_t* lengths_out = nullptr, uint32_t* row_doc_out = nullptr, uint32_t* row_start_out = nullptr) {
+  launch_flat(k_fit_fill<T, WHAT>, st, static_cast<T*>(out), a.rows * a.L, (lengths_out || row_doc_out || row_start_out) ? a.rows : 0, a, static_cast<T*>(out), lengths_out,
+              row_doc_out, row_start_out);
 }
 
 }  // namespace tmh
@@ -292,8 +284,7 @@ int tm_batch_fit(tm_batch* b, const tm_collate* how, void* stream, uint64_t rows
   FitArgs a{};
   uint64_t rows = 0;
   int rc = fit_plan(b, how, ids_out, "tm_batch_fit", &a, &rows);
-  if (rc != TM_OK) return rc;
-  if (rows > rows_cap) return set_error(TM_E_NOSPACE, "tm_batch_fit: rows_cap %llu < %llu rows required", (unsigned long long)rows_cap, (unsigned long long)rows);
+  if (rc != TM_OK || (rc = check_rows_cap("tm_batch_fit", rows_cap, rows)) != TM_OK) return rc;
   if (rows == 0) return TM_OK;
   hipStream_t st = (hipStream_t)stream;
   if ((rc = grow_batch(b, (void**)&b->d_fit_rows, &b->fit_rows_cap, rows, rows + rows / 4 + 1024, sizeof(FitRow), "fit rows")) != TM_OK) return rc;
@@ -302,20 +293,9 @@ int tm_batch_fit(tm_batch* b, const tm_collate* how, void* stream, uint64_t rows
   (void)hipGetLastError();
   TM_LAUNCH(k_fit_rows, (uint32_t)fit_tiles(how->ndocs), FIT_T, 0, st, a, w.next, w.tile_entry, w.tile_row, table);
   const FitFill fa{b->d_out, a.toff, table, rows, how->ndocs, how->row_len, how->pad_id, how->eos_id};
-  if (how->id_bytes == 2) launch_fit_ids<uint16_t>(fa, ids_out, lengths_out, row_doc_out, row_start_out, st);
-  else if (how->id_bytes == 4) launch_fit_ids<uint32_t>(fa, ids_out, lengths_out, row_doc_out, row_start_out, st);
-  else launch_fit_ids<uint64_t>(fa, ids_out, lengths_out, row_doc_out, row_start_out, st);
-  const uint64_t n = rows * how->row_len;
-  if (doc_index_out) {
-    const Flat f = flat_of(doc_index_out, n, 4);
-    const auto kern = k_fit_fill<uint32_t, 1>;
-    TM_LAUNCH(kern, grid_of(flat_items(f, 4)), 256, 0, st, fa, f, doc_index_out, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr);
-  }
-  if (position_out) {
-    const Flat f = flat_of(position_out, n, 4);
-    const auto kern = k_fit_fill<uint32_t, 2>;
-    TM_LAUNCH(kern, grid_of(flat_items(f, 4)), 256, 0, st, fa, f, position_out, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr);
-  }
+  with_id_type(how->id_bytes, [&](auto z) { launch_fit<decltype(z), 0>(fa, ids_out, st, lengths_out, row_doc_out, row_start_out); });
+  if (doc_index_out) launch_fit<uint32_t, 1>(fa, doc_index_out, st);
+  if (position_out) launch_fit<uint32_t, 2>(fa, position_out, st);
   return launch_check();
 }
 

@@ -2555,6 +2555,15 @@ int batch_replace(tm_batch* b, void** p, uint64_t old_bytes, uint64_t need_bytes
   if (e != hipSuccess) { *p = nullptr; return hip_fail(e, what); }
   return TM_OK;
 }
+int batch_reserve_docs(tm_batch* b, void** p, uint32_t* cap, uint32_t nd, uint64_t (*bytes)(uint32_t cap), const char* what) {
+  if (*p && nd <= *cap) return TM_OK;
+  const uint32_t want = (uint32_t)std::min<uint64_t>((uint64_t)nd + nd / 4 + 1024, 0xFFFFFFFFull);
+  const uint64_t old_bytes = *p ? bytes(*cap) : 0;
+  *cap = 0;
+  const int rc = batch_replace(b, p, old_bytes, bytes(nd), bytes(want), what);
+  if (rc == TM_OK) *cap = want;
+  return rc;
+}
 int grow_batch(tm_batch* b, void** p, uint64_t* cap, uint64_t need, uint64_t alloc, uint32_t elem_bytes, const char* what) {
   if (*cap >= need) return TM_OK;
   const uint64_t old_bytes = *cap * elem_bytes;

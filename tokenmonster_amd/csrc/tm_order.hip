@@ -201,13 +201,7 @@ static OrderBuf order_buf(const tm_batch* b) {
   return w;
 }
 static int order_reserve(tm_batch* b, uint32_t nd) {
-  if (b->d_order && nd <= b->order_cap) return TM_OK;
-  const uint32_t cap = (uint32_t)std::min<uint64_t>((uint64_t)nd + nd / 4 + 1024, 0xFFFFFFFFull);
-  const uint64_t old_bytes = b->d_order ? order_bytes(b->order_cap) : 0;
-  b->order_cap = 0;
-  const int rc = batch_replace(b, (void**)&b->d_order, old_bytes, order_bytes(nd), order_bytes(cap), "length order");
-  if (rc == TM_OK) b->order_cap = cap;
-  return rc;
+  return batch_reserve_docs(b, (void**)&b->d_order, &b->order_cap, nd, [](uint32_t cap) { return order_bytes(cap); }, "length order");
 }
 
 }  // namespace tmh

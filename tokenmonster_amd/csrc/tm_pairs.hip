@@ -3,8 +3,8 @@
 // laid out the same way (tm_batch_pair_spans_in, tm_batch_pair_windows_spans_in).  The rule: include/tokenmonster_hip.h.
 //
 // Streaming kernels like tm_collate.hip's and tm_windows.hip's: no table, no LDS, the output one flat run of elements, one 16-byte vector per
-// work-item.  The plan of a row is four token offsets (pair_plan, tm_collate.h) and the fill bodies are fill_pair_rows / fill_pair_spans
-// there.  The window form counts the rows of every pair (k_pair_window_counts: the room for B differs from pair to pair, with the ids A keeps),
+// work-item.  The plan of a row is four token offsets (pair_plan, tm_collate.h) and the fill is the one walk of rows there (fill_walk)
+// with the value rules PairValue / PairSpanValue.  The window form counts the rows of every pair (k_pair_window_counts: the room for B differs from pair to pair, with the ids A keeps),
 // and then goes the way of tm_windows.hip through the batch's window buffers: scan_u32 into win_off, the pair of every row once per row
 // (k_window_row_docs), the fill with pair_win_plan.
 #include <hip/hip_runtime.h>
@@ -18,7 +18,7 @@
 namespace tmh {
 
 // ---- k_pair_rows: one pair per row -------------------------------------------------------------------------------------------------------------
-// The fill is fill_pair_rows (tm_collate.h) with the plan of one pair per row.  kept (ids launch only, may be null): the first `rows`
+// The fill is fill_walk (tm_collate.h) with the plan of one pair per row and PairValue.  kept (ids launch only, may be null): the first `rows`
 // work-items write a row's (a', b') each.
 template <typename T, int WHAT>
 __global__ __launch_bounds__(256) void k_pair_rows(PairArgs a, Flat f, T* __restrict__ out, uint32_t* __restrict__ kept) {
@@ -28,14 +28,14 @@ __global__ __launch_bounds__(256) void k_pair_rows(PairArgs a, Flat f, T* __rest
     kept[2 * t] = p.na;
     kept[2 * t + 1] = p.nb;
   }
-  fill_pair_rows<T, WHAT>(a, f, out, t, [&](uint64_t r) { return pair_plan(a, r); });
+  fill_walk<T>(f, a.L, out, t, [&](uint64_t r) { return pair_plan(a, r); }, PairValue<WHAT>{a});
 }
 
 // ---- k_pair_spans: the pairs of the ids laid out like the rows ---------------------------------------------------------------------------------
 template <typename T>
 __global__ __launch_bounds__(256) void k_pair_spans(PairArgs a, Flat f, const uint32_t* __restrict__ spans, T* __restrict__ out) {
   const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  fill_pair_spans<T>(a, f, spans, out, t, [&](uint64_t r) { return pair_plan(a, r); });
+  fill_walk<T, 2>(f, a.L, out, t, [&](uint64_t r) { return pair_plan(a, r); }, PairSpanValue{a, spans});
 }
 
 // ---- k_pair_window_counts: the rows of every pair (k_window_counts with a room per pair) -------------------------------------------------------
@@ -60,37 +60,30 @@ __global__ __launch_bounds__(256) void k_pair_window_rows(PairArgs a, Flat f, T*
     if (row_pair) row_pair[t] = w.pair;
     if (row_start) row_start[t] = (uint32_t)w.start;
   }
-  fill_pair_rows<T, WHAT>(a, f, out, t, [&](uint64_t r) { return pair_win_plan(a, r).p; });
+  fill_walk<T>(f, a.L, out, t, [&](uint64_t r) { return pair_win_plan(a, r).p; }, PairValue<WHAT>{a});
 }
 template <typename T>
 __global__ __launch_bounds__(256) void k_pair_window_spans(PairArgs a, Flat f, const uint32_t* __restrict__ spans, T* __restrict__ out) {
   const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  fill_pair_spans<T>(a, f, spans, out, t, [&](uint64_t r) { return pair_win_plan(a, r).p; });
+  fill_walk<T, 2>(f, a.L, out, t, [&](uint64_t r) { return pair_win_plan(a, r).p; }, PairSpanValue{a, spans});
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------------------------------
 // the arguments every pair call shares (out: only that it is there); fills all of *a but the window fields
 static int check_pair(const tm_batch* b, const tm_pair* how, const void* out, const char* who, PairArgs* a) {
-  if (!b || !how || !out) return set_error(TM_E_INVALID, "%s: null argument", who);
-  if (how->id_bytes != 2 && how->id_bytes != 4 && how->id_bytes != 8) return set_error(TM_E_INVALID, "%s: id_bytes %u (2, 4 or 8)", who, how->id_bytes);
-  if (how->row_len == 0) return set_error(TM_E_INVALID, "%s: row_len 0", who);
-  if (how->pad_id == TM_NONE) return set_error(TM_E_INVALID, "%s: pad_id must be given", who);
+  int rc = check_row_shape(b && how && out, how ? how->id_bytes : 0, how ? how->row_len : 0, how ? how->pad_id : 0, who);
+  if (rc != TM_OK) return rc;
   if (how->flags & ~TM_COLLATE_PAD_LEFT)
     return set_error(TM_E_INVALID, "%s: flags %#x (TM_COLLATE_PAD_LEFT only: both sides keep their heads, no TM_COLLATE_KEEP_TAIL)", who, how->flags);
   if (how->truncation > TM_PAIR_ONLY_SECOND) return set_error(TM_E_INVALID, "%s: unknown truncation %u", who, how->truncation);
   if (how->sep_id == TM_NONE ? how->sep_count != 0 : (how->sep_count != 1 && how->sep_count != 2))
     return set_error(TM_E_INVALID, "%s: sep_count %u (1 or 2 with a sep_id, 0 without)", who, how->sep_count);
-  if (how->id_bytes == 2) {
-    if (b->vocab->host.n_ids > 65536u) return set_error(TM_E_INVALID, "%s: two-byte ids with a vocabulary of %u ids", who, b->vocab->host.n_ids);
-    for (uint32_t s : {how->pad_id, how->bos_id, how->sep_id, how->eos_id})
-      if (s != TM_NONE && s >= 65536u) return set_error(TM_E_INVALID, "%s: special id %u does not fit two bytes", who, s);
-  }
-  if (!b->has_output) return set_error(TM_E_INVALID, "%s: the batch holds no ids (no completed tm_batch_run or tm_batch_load_ids since the last upload)", who);
+  if ((rc = check_ids_fit(b, how->id_bytes, {how->pad_id, how->bos_id, how->sep_id, how->eos_id}, who)) != TM_OK) return rc;
   for (uint32_t first : {how->first_a, how->first_b})
     if ((uint64_t)first + how->npairs > b->ndocs)
       return set_error(TM_E_INVALID, "%s: documents %u .. %llu of a run of %u", who, first, (unsigned long long)first + how->npairs, b->ndocs);
   const uint32_t ns = (how->bos_id != TM_NONE ? 1u : 0u) + how->sep_count + (how->eos_id != TM_NONE ? 1u : 0u);
-  if (how->row_len < ns) return set_error(TM_E_INVALID, "%s: row_len %u holds no %u specials", who, how->row_len, ns);
+  if ((rc = check_row_room(who, how->row_len, ns, 0, "pairs")) != TM_OK) return rc;
   *a = PairArgs{b->d_out, b->d_tok_offsets + how->first_a, b->d_tok_offsets + how->first_b, nullptr, nullptr, how->npairs, how->npairs, how->row_len,
                 how->row_len - ns, how->pad_id, how->bos_id, how->sep_id, how->eos_id, how->sep_count, how->truncation, 0u, 0u, how->flags};
   return TM_OK;
@@ -104,25 +97,21 @@ static int check_pair_spans(const tm_batch* b, uint32_t text, uint32_t unit, uin
   return TM_OK;
 }
 
-template <typename T>
-static void launch_pair_ids(const PairArgs& a, void* ids_out, uint32_t* kept_out, hipStream_t st) {
-  const Flat f = flat_of(ids_out, a.rows * a.L, sizeof(T));
-  const uint64_t items = std::max<uint64_t>(flat_items(f, sizeof(T)), kept_out ? a.rows : 0);
-  const auto kern = k_pair_rows<T, 0>;
-  TM_LAUNCH(kern, grid_of(items), 256, 0, st, a, f, static_cast<T*>(ids_out), kept_out);
+// the launches: WHAT 0 = ids (the per-row outputs may be given), 1 = mask, 2 = types
+template <typename T, int WHAT>
+static void launch_pair_rows(const PairArgs& a, void* out, hipStream_t st, uint32_t* kept_out = nullptr) {
+  launch_flat(k_pair_rows<T, WHAT>, st, static_cast<T*>(out), a.rows * a.L, kept_out ? a.rows : 0, a, static_cast<T*>(out), kept_out);
 }
-template <typename T>
-static void launch_pair_window_ids(const PairArgs& a, void* ids_out, uint32_t* kept_out, uint32_t* row_pair_out, uint32_t* row_start_out, hipStream_t st) {
-  const Flat f = flat_of(ids_out, a.rows * a.L, sizeof(T));
-  const uint64_t items = std::max<uint64_t>(flat_items(f, sizeof(T)), (kept_out || row_pair_out || row_start_out) ? a.rows : 0);
-  const auto kern = k_pair_window_rows<T, 0>;
-  TM_LAUNCH(kern, grid_of(items), 256, 0, st, a, f, static_cast<T*>(ids_out), kept_out, row_pair_out, row_start_out);
+template <typename T, int WHAT>
+static void launch_pair_window_rows(const PairArgs& a, void* out, hipStream_t st, uint32_t* kept_out = nullptr, uint32_t* row_pair_out = nullptr, uint32_t* row_start_out = nullptr) {
+  launch_flat(k_pair_window_rows<T, WHAT>, st, static_cast<T*>(out), a.rows * a.L, (kept_out || row_pair_out || row_start_out) ? a.rows : 0, a, static_cast<T*>(out), kept_out,
+              row_pair_out, row_start_out);
 }
-template <typename T>
-static void launch_pair_spans(const PairArgs& a, bool windows, const uint32_t* spans, void* out, hipStream_t st) {
-  const Flat f = flat_of(out, 2ull * a.rows * a.L, sizeof(T));
-  const auto kern = windows ? k_pair_window_spans<T> : k_pair_spans<T>;
-  TM_LAUNCH(kern, grid_of(flat_items(f, sizeof(T))), 256, 0, st, a, f, spans, static_cast<T*>(out));
+static void launch_pair_spans(const PairArgs& a, bool windows, const uint32_t* spans, void* out, uint32_t span_bytes, hipStream_t st) {
+  with_wide_type<uint32_t, uint64_t>(span_bytes, [&](auto z) {
+    using T = decltype(z);
+    launch_flat(windows ? k_pair_window_spans<T> : k_pair_spans<T>, st, static_cast<T*>(out), 2ull * a.rows * a.L, 0, a, spans, static_cast<T*>(out));
+  });
 }
 
 // what the three window calls share: the arguments, the rows per pair and their scan on the stream of the batch's last run, and the number
@@ -149,8 +138,7 @@ static int pair_window_plan(tm_batch* b, const tm_pair* how, uint32_t overlap, u
   if ((rc = launch_check()) != TM_OK) return rc;
   if ((rc = small_d2h(b, &a->rows, w.win_off + how->npairs, 8, st)) != TM_OK || (rc = small_sync(b, st)) != TM_OK) return rc;
   a->win_off = w.win_off;
-  if (a->rows * how->row_len > COLLATE_MAX_ELEMS) return set_error(TM_E_LIMIT, "%s: %llu rows of %u ids in one call (split the pairs)", who, (unsigned long long)a->rows, how->row_len);
-  return TM_OK;
+  return check_row_room(who, how->row_len, 0, a->rows, "pairs");
 }
 
 }  // namespace tmh
@@ -163,24 +151,14 @@ int tm_batch_pair(tm_batch* b, const tm_pair* how, void* stream, void* ids_out, 
   PairArgs a{};
   int rc = check_pair(b, how, ids_out, "tm_batch_pair", &a);
   if (rc != TM_OK) return rc;
-  if ((uint64_t)how->npairs * how->row_len > COLLATE_MAX_ELEMS) return set_error(TM_E_LIMIT, "tm_batch_pair: %u rows of %u ids in one call (split the pairs)", how->npairs, how->row_len);
+  if ((rc = check_row_room("tm_batch_pair", how->row_len, 0, how->npairs, "pairs")) != TM_OK) return rc;
   if ((rc = enter_device(b->vocab)) != TM_OK || (rc = ensure_output(b)) != TM_OK) return rc;      // (waits for the run: the ids are all there)
   if (how->npairs == 0) return TM_OK;
   hipStream_t st = (hipStream_t)stream;
   (void)hipGetLastError();
-  if (how->id_bytes == 2) launch_pair_ids<uint16_t>(a, ids_out, kept_out, st);
-  else if (how->id_bytes == 4) launch_pair_ids<uint32_t>(a, ids_out, kept_out, st);
-  else launch_pair_ids<uint64_t>(a, ids_out, kept_out, st);
-  if (mask_out) {
-    const Flat f = flat_of(mask_out, a.rows * a.L, 1);
-    const auto kern = k_pair_rows<uint8_t, 1>;
-    TM_LAUNCH(kern, grid_of(flat_items(f, 1)), 256, 0, st, a, f, mask_out, (uint32_t*)nullptr);
-  }
-  if (type_out) {
-    const Flat f = flat_of(type_out, a.rows * a.L, 1);
-    const auto kern = k_pair_rows<uint8_t, 2>;
-    TM_LAUNCH(kern, grid_of(flat_items(f, 1)), 256, 0, st, a, f, type_out, (uint32_t*)nullptr);
-  }
+  with_id_type(how->id_bytes, [&](auto z) { launch_pair_rows<decltype(z), 0>(a, ids_out, st, kept_out); });
+  if (mask_out) launch_pair_rows<uint8_t, 1>(a, mask_out, st);
+  if (type_out) launch_pair_rows<uint8_t, 2>(a, type_out, st);
   return launch_check();
 }
 
@@ -189,7 +167,7 @@ int tm_batch_pair_spans_in(tm_batch* b, const tm_pair* how, void* stream, uint32
   PairArgs a{};
   int rc = check_pair(b, how, spans_out, who, &a);
   if (rc != TM_OK || (rc = check_pair_spans(b, text, unit, span_bytes, who)) != TM_OK) return rc;
-  if ((uint64_t)how->npairs * how->row_len > COLLATE_MAX_ELEMS) return set_error(TM_E_LIMIT, "%s: %u rows of %u ids in one call (split the pairs)", who, how->npairs, how->row_len);
+  if ((rc = check_row_room(who, how->row_len, 0, how->npairs, "pairs")) != TM_OK) return rc;
   if ((rc = enter_device(b->vocab)) != TM_OK || (rc = ensure_output(b)) != TM_OK) return rc;      // (waits for the run: the rows are all there)
   if (how->npairs == 0) return TM_OK;
   const uint64_t total = b->last_totals[1];
@@ -197,8 +175,7 @@ int tm_batch_pair_spans_in(tm_batch* b, const tm_pair* how, void* stream, uint32
   if ((rc = spans_check_lengths(b, who)) != TM_OK || (rc = batch_own_spans_on(b, st, text, unit, total)) != TM_OK) return rc;
   (void)hipGetLastError();
   a.ids = nullptr;
-  if (span_bytes == 4) launch_pair_spans<uint32_t>(a, false, reinterpret_cast<const uint32_t*>(b->d_spans), spans_out, st);
-  else launch_pair_spans<uint64_t>(a, false, reinterpret_cast<const uint32_t*>(b->d_spans), spans_out, st);
+  launch_pair_spans(a, false, reinterpret_cast<const uint32_t*>(b->d_spans), spans_out, span_bytes, st);
   return launch_check();
 }
 
@@ -215,26 +192,15 @@ int tm_batch_pair_windows(tm_batch* b, const tm_pair* how, uint32_t overlap, uin
                           uint8_t* type_out, uint32_t* kept_out, uint32_t* row_pair_out, uint32_t* row_start_out) {
   PairArgs a{};
   int rc = pair_window_plan(b, how, overlap, max_first, ids_out, "tm_batch_pair_windows", false, 0, 0, 0, &a);
-  if (rc != TM_OK) return rc;
-  if (a.rows > rows_cap) return set_error(TM_E_NOSPACE, "tm_batch_pair_windows: rows_cap %llu < %llu rows required", (unsigned long long)rows_cap, (unsigned long long)a.rows);
+  if (rc != TM_OK || (rc = check_rows_cap("tm_batch_pair_windows", rows_cap, a.rows)) != TM_OK) return rc;
   if (a.rows == 0) return TM_OK;
   hipStream_t st = (hipStream_t)stream;
   if ((rc = win_row_docs(b, a.win_off, a.np, a.rows, st)) != TM_OK) return rc;
   a.row_doc = b->d_win_rows;
   (void)hipGetLastError();
-  if (how->id_bytes == 2) launch_pair_window_ids<uint16_t>(a, ids_out, kept_out, row_pair_out, row_start_out, st);
-  else if (how->id_bytes == 4) launch_pair_window_ids<uint32_t>(a, ids_out, kept_out, row_pair_out, row_start_out, st);
-  else launch_pair_window_ids<uint64_t>(a, ids_out, kept_out, row_pair_out, row_start_out, st);
-  if (mask_out) {
-    const Flat f = flat_of(mask_out, a.rows * a.L, 1);
-    const auto kern = k_pair_window_rows<uint8_t, 1>;
-    TM_LAUNCH(kern, grid_of(flat_items(f, 1)), 256, 0, st, a, f, mask_out, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr);
-  }
-  if (type_out) {
-    const Flat f = flat_of(type_out, a.rows * a.L, 1);
-    const auto kern = k_pair_window_rows<uint8_t, 2>;
-    TM_LAUNCH(kern, grid_of(flat_items(f, 1)), 256, 0, st, a, f, type_out, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr);
-  }
+  with_id_type(how->id_bytes, [&](auto z) { launch_pair_window_rows<decltype(z), 0>(a, ids_out, st, kept_out, row_pair_out, row_start_out); });
+  if (mask_out) launch_pair_window_rows<uint8_t, 1>(a, mask_out, st);
+  if (type_out) launch_pair_window_rows<uint8_t, 2>(a, type_out, st);
   return launch_check();
 }
 
@@ -243,8 +209,7 @@ int tm_batch_pair_windows_spans_in(tm_batch* b, const tm_pair* how, uint32_t ove
   const char* who = "tm_batch_pair_windows_spans_in";
   PairArgs a{};
   int rc = pair_window_plan(b, how, overlap, max_first, spans_out, who, true, text, unit, span_bytes, &a);
-  if (rc != TM_OK) return rc;
-  if (a.rows > rows_cap) return set_error(TM_E_NOSPACE, "%s: rows_cap %llu < %llu rows required", who, (unsigned long long)rows_cap, (unsigned long long)a.rows);
+  if (rc != TM_OK || (rc = check_rows_cap(who, rows_cap, a.rows)) != TM_OK) return rc;
   if (a.rows == 0) return TM_OK;
   const uint64_t total = b->last_totals[1];
   hipStream_t st = (hipStream_t)stream;
@@ -253,8 +218,7 @@ int tm_batch_pair_windows_spans_in(tm_batch* b, const tm_pair* how, uint32_t ove
   a.row_doc = b->d_win_rows;
   (void)hipGetLastError();
   a.ids = nullptr;
-  if (span_bytes == 4) launch_pair_spans<uint32_t>(a, true, reinterpret_cast<const uint32_t*>(b->d_spans), spans_out, st);
-  else launch_pair_spans<uint64_t>(a, true, reinterpret_cast<const uint32_t*>(b->d_spans), spans_out, st);
+  launch_pair_spans(a, true, reinterpret_cast<const uint32_t*>(b->d_spans), spans_out, span_bytes, st);
   return launch_check();
 }
 

@@ -403,6 +403,9 @@ int grow_pinned(uint8_t** buf, uint64_t* cap, uint64_t need, uint64_t alloc, con
 // its capacity (windows, the unit index): *p of old_bytes, too small for need_bytes, replaced by one of alloc_bytes; the caller keeps the capacity.
 int grow_batch(tm_batch* b, void** p, uint64_t* cap, uint64_t need, uint64_t alloc, uint32_t elem_bytes, const char* what);
 int batch_replace(tm_batch* b, void** p, uint64_t old_bytes, uint64_t need_bytes, uint64_t alloc_bytes, const char* what);
+// ... and batch_replace for a scratch buffer laid out per document (windows, fit plan, length order): *p holds bytes(*cap), too small for nd
+// documents it is replaced by one for nd + 25 % + 1024 of them
+int batch_reserve_docs(tm_batch* b, void** p, uint32_t* cap, uint32_t nd, uint64_t (*bytes)(uint32_t cap), const char* what);
 // ... and a workspace of `v` for `bytes` of text in `docs` documents: a smaller one (or another vocabulary's) is replaced by one of alloc_bytes and docs + 25 %
 int grow_workspace(tm_batch** ws, const tm_vocab* v, uint64_t bytes, uint32_t docs, uint64_t alloc_bytes, const char* what);
 int batch_upload_on(tm_batch* b, const uint8_t* text, const uint64_t* offsets, uint32_t ndocs, hipStream_t st);

@@ -15,7 +15,7 @@
 // tile costs two atomics per wavefront.  The atomics work on pairs in the batch's own buffer (the caller's array may be page-locked host memory):
 // k_region_init sets them to (0xFFFFFFFF, 0) and counts the regions that break the order rule, a ballot and one atomic add per wavefront;
 // k_region_finish writes (first, last + 1), or (0, 0), to the caller.
-// k_collate_labels: the ragged labels laid out like tm_batch_collate's rows - the fill of tm_collate.h with the specials as FLAGS (any ignore_label is
+// k_collate_labels: the ragged labels laid out like tm_batch_collate's rows - the walk of tm_collate.h's fill_walk with the specials as FLAGS (any ignore_label is
 // a label, TM_NONE's bit pattern too) and a store that sign-extends.
 #include <hip/hip_runtime.h>
 
@@ -226,7 +226,7 @@ __global__ __launch_bounds__(256) void k_region_finish(const uint32_t* __restric
   rtok_out[2u * r + 1u] = none ? 0u : last + 1u;
 }
 
-// ---- k_collate_labels: fill_rows (tm_collate.h) over the ragged labels -------------------------------------------------------------------------------
+// ---- k_collate_labels: the walk of rows of fill_walk (tm_collate.h), spelled out, over the ragged labels ------------------------------------------------
 // The plan of a row is row_plan's, asked with a CollateArgs whose bos / eos only say whether the special is there.
 struct LabelRows {
   CollateArgs c;              // toff, rows, L, flags; bos / eos: 0 = given, TM_NONE = none; ids and pad unused
@@ -317,13 +317,6 @@ static int region_labels_on(tm_batch* b, hipStream_t st, const tm_regions* rg, T
   return launch_check();
 }
 
-template <typename T>
-static void launch_collate_labels(const LabelRows& a, void* out, hipStream_t st) {
-  const Flat f = flat_of(out, (uint64_t)a.c.rows * a.c.L, sizeof(T));
-  const auto kern = k_collate_labels<T>;
-  TM_LAUNCH(kern, grid_of(flat_items(f, sizeof(T))), 256, 0, st, a, f, static_cast<T*>(out));
-}
-
 }  // namespace tmh
 
 using namespace tmh;
@@ -354,8 +347,7 @@ int tm_batch_collate_region_labels(tm_batch* b, const tm_collate* how, void* str
   int rc = check_how(b, how, labels_out, who);
   if (rc != TM_OK || (rc = region_args(b, rg, label_bytes, who)) != TM_OK) return rc;
   const uint32_t ns = (how->bos_id != TM_NONE ? 1u : 0u) + (how->eos_id != TM_NONE ? 1u : 0u);
-  if (how->row_len < ns) return set_error(TM_E_INVALID, "%s: row_len %u holds no %u specials", who, how->row_len, ns);
-  if ((uint64_t)how->ndocs * how->row_len > COLLATE_MAX_ELEMS) return set_error(TM_E_LIMIT, "%s: %u rows of %u ids in one call (split the documents)", who, how->ndocs, how->row_len);
+  if ((rc = check_row_room(who, how->row_len, ns, how->ndocs, "documents")) != TM_OK) return rc;
   if ((rc = enter_device(b->vocab)) != TM_OK || (rc = ensure_output(b)) != TM_OK) return rc;      // (waits for the run: the rows are all there)
   if (how->ndocs == 0) return TM_OK;
   const uint64_t total = b->last_totals[1];
@@ -367,8 +359,10 @@ int tm_batch_collate_region_labels(tm_batch* b, const tm_collate* how, void* str
   const LabelRows a{CollateArgs{nullptr, b->d_tok_offsets + how->first_doc, how->ndocs, how->row_len, 0u, how->bos_id != TM_NONE ? 0u : TM_NONE,
                                 how->eos_id != TM_NONE ? 0u : TM_NONE, how->flags},
                     ragged, rg->ignore_label};
-  if (label_bytes == 4) launch_collate_labels<int32_t>(a, labels_out, st);
-  else launch_collate_labels<int64_t>(a, labels_out, st);
+  with_wide_type<int32_t, int64_t>(label_bytes, [&](auto z) {
+    using T = decltype(z);
+    launch_flat(k_collate_labels<T>, st, static_cast<T*>(labels_out), (uint64_t)a.c.rows * a.c.L, 0, a, static_cast<T*>(labels_out));
+  });
   return launch_check();
 }
 

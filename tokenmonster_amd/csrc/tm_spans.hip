@@ -7,8 +7,8 @@
 // output slot K4 wrote an id to, the position the walk stood on and that position plus the advance.  It reads only the advance / flag byte of
 // a position, never an id, adds to no counter and writes nothing but its output.
 //
-// The collated form is tm_collate.h's fill body for pairs (fill_spans) with the plan of one document per row; tm_windows.hip runs the same body
-// with the plan of a window.  The host side holds the bodies the span calls share: ragged_spans_impl (the ragged calls, tm_units.hip's
+// The collated form is tm_collate.h's walk of rows (fill_walk) with the value rule for pairs (SpanValue) and the plan of one document per row;
+// tm_windows.hip runs the same with the plan of a window.  The host side holds the bodies the span calls share: ragged_spans_impl (the ragged calls, tm_units.hip's
 // included), batch_own_spans_on (the pairs into the batch's own buffer: the collate and window span calls, the one-shot calls of tm_host.hip)
 // and collate_spans_impl.
 #include <hip/hip_runtime.h>
@@ -198,11 +198,11 @@ __global__ __launch_bounds__(64) void k_span_list(const uint32_t* __restrict__ R
   }
 }
 
-// ---- k_collate_spans: the pairs laid out like tm_batch_collate's rows (fill_spans, tm_collate.h, with the plan of one document per row) -------------
+// ---- k_collate_spans: the pairs laid out like tm_batch_collate's rows (fill_walk / SpanValue, tm_collate.h, with the plan of one document per row) ---
 template <typename T>
 __global__ __launch_bounds__(256) void k_collate_spans(CollateArgs a, Flat f, const uint32_t* __restrict__ spans, T* __restrict__ out) {
   const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  fill_spans<T>(a, f, spans, out, t, [&](uint64_t r) { return row_plan(a, r); });
+  fill_walk<T, 2>(f, a.L, out, t, [&](uint64_t r) { return row_plan(a, r); }, SpanValue<CollateArgs>{a, spans});
 }
 
 // ---- k_raw_spans: the pairs mapped back through the normalizer ----------------------------------------------------------------------------------------
@@ -302,13 +302,6 @@ int batch_own_spans_on(tm_batch* b, hipStream_t st, uint32_t text, uint32_t unit
   return rc != TM_OK ? rc : batch_spans_in_on(b, st, text, unit, b->d_spans, total, host_docs, nullptr);
 }
 
-template <typename T>
-static void launch_collate_spans(const CollateArgs& a, const uint32_t* spans, void* out, hipStream_t st) {
-  const Flat f = flat_of(out, 2ull * a.rows * a.L, sizeof(T));
-  const auto kern = k_collate_spans<T>;
-  TM_LAUNCH(kern, grid_of(flat_items(f, sizeof(T))), 256, 0, st, a, f, spans, static_cast<T*>(out));
-}
-
 // the one body of tm_batch_collate_spans, tm_batch_collate_raw_spans and tm_batch_collate_spans_in: the ragged pairs of `text` into the batch's own
 // buffer, counted in `unit` (tm_units.hip), then the fill
 int collate_spans_impl(tm_batch* b, const tm_collate* how, void* stream, uint32_t text, uint32_t unit, void* spans_out, uint32_t span_bytes, const char* who) {
@@ -317,8 +310,7 @@ int collate_spans_impl(tm_batch* b, const tm_collate* how, void* stream, uint32_
   const bool raw = text == TM_TEXT_RAW;
   if (span_bytes != 4 && span_bytes != 8) return set_error(TM_E_INVALID, "%s: span_bytes %u (4 or 8)", who, span_bytes);
   const uint32_t ns = (how->bos_id != TM_NONE ? 1u : 0u) + (how->eos_id != TM_NONE ? 1u : 0u);
-  if (how->row_len < ns) return set_error(TM_E_INVALID, "%s: row_len %u holds no %u specials", who, how->row_len, ns);
-  if ((uint64_t)how->ndocs * how->row_len > COLLATE_MAX_ELEMS) return set_error(TM_E_LIMIT, "%s: %u rows of %u ids in one call (split the documents)", who, how->ndocs, how->row_len);
+  if ((rc = check_row_room(who, how->row_len, ns, how->ndocs, "documents")) != TM_OK) return rc;
   if ((rc = spans_ready(b, who)) != TM_OK || (raw && (rc = origin_ready(b, who)) != TM_OK)) return rc;
   if ((rc = enter_device(b->vocab)) != TM_OK || (rc = ensure_output(b)) != TM_OK) return rc;      // (waits for the run: the rows are all there)
   if (how->ndocs == 0) return TM_OK;
@@ -327,8 +319,10 @@ int collate_spans_impl(tm_batch* b, const tm_collate* how, void* stream, uint32_
   if ((rc = spans_check_lengths(b, who)) != TM_OK || (rc = batch_own_spans_on(b, st, text, unit, total)) != TM_OK) return rc;
   (void)hipGetLastError();
   const CollateArgs a{nullptr, b->d_tok_offsets + how->first_doc, how->ndocs, how->row_len, how->pad_id, how->bos_id, how->eos_id, how->flags};
-  if (span_bytes == 4) launch_collate_spans<uint32_t>(a, reinterpret_cast<const uint32_t*>(b->d_spans), spans_out, st);
-  else launch_collate_spans<uint64_t>(a, reinterpret_cast<const uint32_t*>(b->d_spans), spans_out, st);
+  with_wide_type<uint32_t, uint64_t>(span_bytes, [&](auto z) {
+    using T = decltype(z);
+    launch_flat(k_collate_spans<T>, st, static_cast<T*>(spans_out), 2ull * a.rows * a.L, 0, a, reinterpret_cast<const uint32_t*>(b->d_spans), static_cast<T*>(spans_out));
+  });
   return launch_check();
 }
 

@@ -4,7 +4,7 @@
 //
 // Four steps: the windows of every document from two token offsets (k_window_counts), their scan into win_off (scan_u32; the host reads
 // win_off[nd], the number of rows), the document of every row - a binary search over win_off, a DocCursor with win_off as its keys, once per
-// ROW (k_window_row_docs) - and the fill: the fill bodies tm_collate.hip's kernels run (fill_rows / fill_spans, tm_collate.h: no table, no LDS,
+// ROW (k_window_row_docs) - and the fill: the walk of rows tm_collate.hip's kernels run (fill_walk with RowValue / SpanValue, tm_collate.h: no table, no LDS,
 // the output one flat run of elements, one 16-byte vector per work-item), here with the plan of a window.  The row of a work-item's first
 // element is a division, the row's document one load; when the vector crosses a row end the next row's document is looked up the same way - the
 // next window of the document, or any number of documents on.  (One search per row, not one per 16-byte vector in the fill, where its
@@ -38,7 +38,7 @@ __global__ __launch_bounds__(256) void k_window_row_docs(const uint64_t* __restr
 }
 
 // ---- k_window_rows: the ids (or the mask) of the rows ------------------------------------------------------------------------------------------
-// The fill is fill_rows (tm_collate.h) with the plan of a window.  The per-row outputs (ids launch only, each may be null): the first `rows`
+// The fill is fill_walk (tm_collate.h) with the plan of a window and RowValue.  The per-row outputs (ids launch only, each may be null): the first `rows`
 // work-items write a row's length, document and start each.
 template <typename T, bool MASK>
 __global__ __launch_bounds__(256) void k_window_rows(WindowArgs a, Flat f, T* __restrict__ out, uint32_t* __restrict__ lengths, uint32_t* __restrict__ row_doc,
@@ -50,14 +50,14 @@ __global__ __launch_bounds__(256) void k_window_rows(WindowArgs a, Flat f, T* __
     if (row_doc) row_doc[t] = w.d;
     if (row_start) row_start[t] = (uint32_t)w.start;
   }
-  fill_rows<T, MASK>(a, f, out, t, [&](uint64_t r) { return win_plan(a, r).p; });
+  fill_walk<T>(f, a.L, out, t, [&](uint64_t r) { return win_plan(a, r).p; }, RowValue<MASK, WindowArgs>{a});
 }
 
-// ---- k_window_spans: the pairs of the ids laid out like the rows (fill_spans, tm_collate.h, with the plan of a window) ------------------------------
+// ---- k_window_spans: the pairs of the ids laid out like the rows (fill_walk / SpanValue, tm_collate.h, with the plan of a window) --------------------
 template <typename T>
 __global__ __launch_bounds__(256) void k_window_spans(WindowArgs a, Flat f, const uint32_t* __restrict__ spans, T* __restrict__ out) {
   const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  fill_spans<T>(a, f, spans, out, t, [&](uint64_t r) { return win_plan(a, r).p; });
+  fill_walk<T, 2>(f, a.L, out, t, [&](uint64_t r) { return win_plan(a, r).p; }, SpanValue<WindowArgs>{a, spans});
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------------------------------
@@ -71,16 +71,8 @@ WinBuf win_buf(const tm_batch* b) {
   w.counts = reinterpret_cast<uint32_t*>(w.total + 1);
   return w;
 }
-int win_reserve(tm_batch* b, uint32_t nd) {
-  if (b->d_win && nd <= b->win_cap) return TM_OK;
-  auto bytes = [](uint32_t cap) { return ((uint64_t)cap + 1 + win_sum_words(cap)) * 8 + (uint64_t)cap * 4; };
-  const uint32_t cap = (uint32_t)std::min<uint64_t>((uint64_t)nd + nd / 4 + 1024, 0xFFFFFFFFull);
-  const uint64_t old_bytes = b->d_win ? bytes(b->win_cap) : 0;
-  b->win_cap = 0;
-  const int rc = batch_replace(b, (void**)&b->d_win, old_bytes, bytes(nd), bytes(cap), "windows");
-  if (rc == TM_OK) b->win_cap = cap;
-  return rc;
-}
+static uint64_t win_bytes(uint32_t cap) { return ((uint64_t)cap + 1 + win_sum_words(cap)) * 8 + (uint64_t)cap * 4; }
+int win_reserve(tm_batch* b, uint32_t nd) { return batch_reserve_docs(b, (void**)&b->d_win, &b->win_cap, nd, win_bytes, "windows"); }
 
 // what the four calls share: the arguments, the rows per document and their scan on the stream of the batch's last run, and the number of
 // rows read back from it (synchronizes like tm_batch_totals).  spans: 0 = an ids call, 1 = normalized spans, 2 = raw spans.
@@ -108,8 +100,7 @@ static int window_plan(tm_batch* b, const tm_collate* how, uint32_t overlap, con
   if ((rc = launch_check()) != TM_OK) return rc;
   if ((rc = small_d2h(b, &a->rows, w.win_off + how->ndocs, 8, st)) != TM_OK || (rc = small_sync(b, st)) != TM_OK) return rc;
   a->win_off = w.win_off;
-  if (a->rows * how->row_len > COLLATE_MAX_ELEMS) return set_error(TM_E_LIMIT, "%s: %llu rows of %u ids in one call (split the documents)", who, (unsigned long long)a->rows, how->row_len);
-  return TM_OK;
+  return check_row_room(who, how->row_len, 0, a->rows, "documents");
 }
 
 // the document of every row into the batch's own buffer, on the stream of the fill behind it
@@ -126,26 +117,17 @@ static int window_row_docs(tm_batch* b, WindowArgs* a, hipStream_t st) {
   return rc;
 }
 
-template <typename T>
-static void launch_window_ids(const WindowArgs& a, void* ids_out, uint32_t* lengths_out, uint32_t* row_doc_out, uint32_t* row_start_out, hipStream_t st) {
-  const Flat f = flat_of(ids_out, a.rows * a.L, sizeof(T));
-  const uint64_t items = std::max<uint64_t>(flat_items(f, sizeof(T)), (lengths_out || row_doc_out || row_start_out) ? a.rows : 0);
-  const auto kern = k_window_rows<T, false>;
-  TM_LAUNCH(kern, grid_of(items), 256, 0, st, a, f, static_cast<T*>(ids_out), lengths_out, row_doc_out, row_start_out);
-}
-template <typename T>
-static void launch_window_spans(const WindowArgs& a, const uint32_t* spans, void* out, hipStream_t st) {
-  const Flat f = flat_of(out, 2ull * a.rows * a.L, sizeof(T));
-  const auto kern = k_window_spans<T>;
-  TM_LAUNCH(kern, grid_of(flat_items(f, sizeof(T))), 256, 0, st, a, f, spans, static_cast<T*>(out));
+template <typename T, bool MASK>
+static void launch_window_rows(const WindowArgs& a, void* out, hipStream_t st, uint32_t* lengths_out = nullptr, uint32_t* row_doc_out = nullptr, uint32_t* row_start_out = nullptr) {
+  launch_flat(k_window_rows<T, MASK>, st, static_cast<T*>(out), a.rows * a.L, (lengths_out || row_doc_out || row_start_out) ? a.rows : 0, a, static_cast<T*>(out), lengths_out,
+              row_doc_out, row_start_out);
 }
 
 static int windows_spans(tm_batch* b, const tm_collate* how, uint32_t overlap, void* stream, uint64_t rows_cap, void* spans_out, uint32_t span_bytes, bool raw,
                          uint32_t unit, const char* who) {
   WindowArgs a{};
   int rc = window_plan(b, how, overlap, spans_out, who, raw ? 2 : 1, span_bytes, &a);
-  if (rc != TM_OK) return rc;
-  if (a.rows > rows_cap) return set_error(TM_E_NOSPACE, "%s: rows_cap %llu < %llu rows required", who, (unsigned long long)rows_cap, (unsigned long long)a.rows);
+  if (rc != TM_OK || (rc = check_rows_cap(who, rows_cap, a.rows)) != TM_OK) return rc;
   if (a.rows == 0) return TM_OK;
   const uint64_t total = b->last_totals[1];
   hipStream_t st = (hipStream_t)stream;
@@ -153,8 +135,10 @@ static int windows_spans(tm_batch* b, const tm_collate* how, uint32_t overlap, v
   if ((rc = window_row_docs(b, &a, st)) != TM_OK) return rc;
   (void)hipGetLastError();
   a.ids = nullptr;
-  if (span_bytes == 4) launch_window_spans<uint32_t>(a, reinterpret_cast<const uint32_t*>(b->d_spans), spans_out, st);
-  else launch_window_spans<uint64_t>(a, reinterpret_cast<const uint32_t*>(b->d_spans), spans_out, st);
+  with_wide_type<uint32_t, uint64_t>(span_bytes, [&](auto z) {
+    using T = decltype(z);
+    launch_flat(k_window_spans<T>, st, static_cast<T*>(spans_out), 2ull * a.rows * a.L, 0, a, reinterpret_cast<const uint32_t*>(b->d_spans), static_cast<T*>(spans_out));
+  });
   return launch_check();
 }
 
@@ -177,20 +161,13 @@ int tm_batch_windows(tm_batch* b, const tm_collate* how, uint32_t overlap, void*
                      uint32_t* lengths_out, uint32_t* row_doc_out, uint32_t* row_start_out) {
   WindowArgs a{};
   int rc = window_plan(b, how, overlap, ids_out, "tm_batch_windows", 0, 0, &a);
-  if (rc != TM_OK) return rc;
-  if (a.rows > rows_cap) return set_error(TM_E_NOSPACE, "tm_batch_windows: rows_cap %llu < %llu rows required", (unsigned long long)rows_cap, (unsigned long long)a.rows);
+  if (rc != TM_OK || (rc = check_rows_cap("tm_batch_windows", rows_cap, a.rows)) != TM_OK) return rc;
   if (a.rows == 0) return TM_OK;
   hipStream_t st = (hipStream_t)stream;
   if ((rc = window_row_docs(b, &a, st)) != TM_OK) return rc;
   (void)hipGetLastError();
-  if (how->id_bytes == 2) launch_window_ids<uint16_t>(a, ids_out, lengths_out, row_doc_out, row_start_out, st);
-  else if (how->id_bytes == 4) launch_window_ids<uint32_t>(a, ids_out, lengths_out, row_doc_out, row_start_out, st);
-  else launch_window_ids<uint64_t>(a, ids_out, lengths_out, row_doc_out, row_start_out, st);
-  if (mask_out) {
-    const Flat f = flat_of(mask_out, a.rows * a.L, 1);
-    const auto kern = k_window_rows<uint8_t, true>;
-    TM_LAUNCH(kern, grid_of(flat_items(f, 1)), 256, 0, st, a, f, mask_out, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr);
-  }
+  with_id_type(how->id_bytes, [&](auto z) { launch_window_rows<decltype(z), false>(a, ids_out, st, lengths_out, row_doc_out, row_start_out); });
+  if (mask_out) launch_window_rows<uint8_t, true>(a, mask_out, st);
   return launch_check();
 }
 

@@ -13,7 +13,7 @@ REV=${1:-HEAD}
 OLD=$(mktemp -d) ; NEW=$(mktemp -d)
 trap 'rm -rf "$OLD" "$NEW"' EXIT
 git -C "$ROOT" archive "$REV" tokenmonster_amd/csrc include | tar -x -C "$OLD"
-UNITS="tm_kernels tm_norm tm_decode tm_spans tm_collate tm_windows tm_pairs tm_units tm_regions"
+UNITS="tm_kernels tm_norm tm_decode tm_spans tm_collate tm_windows tm_pairs tm_units tm_regions tm_fit tm_order"
 for f in $UNITS; do
   ( cd "$OLD/tokenmonster_amd/csrc" && /opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -I ../../include -I . -x hip $f.hip --cuda-device-only -S -o "$OLD/$f.s" 2>/dev/null ) &
   ( cd "$ROOT/tokenmonster_amd/csrc" && /opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -I ../../include -I . -x hip $f.hip --cuda-device-only -S -o "$NEW/$f.s" 2>/dev/null ) &
