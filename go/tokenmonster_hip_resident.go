@@ -359,6 +359,32 @@ func (b *HipBatch) CollateSelect(how HipCollate, docIndex, stream, ids, mask, le
 	return err
 }
 
+// HipMasking is tm_masking: which content ids of a row are replaced and by what (the rule: include/tokenmonster_hip.h).  The thresholds count
+// in units of 2^-32: an id opens a span with probability StartThr / 2^32, a selected id becomes MaskId with MaskThr / 2^32 and one of
+// RandomLo .. RandomLo + RandomN - 1 with RandomThr / 2^32.
+type HipMasking struct {
+	Seed               uint64
+	StartThr           uint64
+	SpanMin, SpanMax   uint32
+	MaskThr, RandomThr uint64
+	MaskId             uint32
+	RandomLo, RandomN  uint32
+	LabelIgnore        int32
+}
+
+// CollateMasked is Collate (docIndex nil) or CollateSelect with masked-LM corruption: labels (may be nil, elements of IdBytes) receives the
+// original id of every replaced or kept-but-selected column and LabelIgnore elsewhere (tm_batch_collate_masked).
+func (b *HipBatch) CollateMasked(how HipCollate, m HipMasking, docIndex, stream, ids, labels, mask, lengths, bad unsafe.Pointer) error {
+	h := how.c()
+	cm := C.tm_masking{seed: C.uint64_t(m.Seed), start_thr: C.uint64_t(m.StartThr), span_min: C.uint32_t(m.SpanMin), span_max: C.uint32_t(m.SpanMax),
+		mask_thr: C.uint64_t(m.MaskThr), random_thr: C.uint64_t(m.RandomThr), mask_id: C.uint32_t(m.MaskId), random_lo: C.uint32_t(m.RandomLo),
+		random_n: C.uint32_t(m.RandomN), label_ignore: C.int32_t(m.LabelIgnore)}
+	_, err := locked(func() C.int {
+		return C.tm_batch_collate_masked(b.h, &h, &cm, (*C.uint32_t)(docIndex), stream, ids, labels, (*C.uint8_t)(mask), (*C.uint32_t)(lengths), (*C.uint32_t)(bad))
+	})
+	return err
+}
+
 // LengthOrder writes the documents firstDoc .. firstDoc + docs - 1 of the last run to order (docs uint32, device or page-locked memory) as absolute
 // document numbers in the order of their id counts - ascending, descending if asked - documents of equal count in ascending document number;
 // counts (may be nil) receives the count of order[i].  What CollateSelect takes as its docIndex (tm_batch_length_order).

@@ -298,6 +298,36 @@ int tm_batch_collate(tm_batch* b, const tm_collate* how, void* stream,
  * call keeps nothing in the batch: calls on different streams may overlap. */
 int tm_batch_collate_select(tm_batch* b, const tm_collate* how, const uint32_t* doc_index, void* stream,
                             void* ids_out, uint8_t* mask_out, uint32_t* lengths_out, uint32_t* bad_out);
+/* Masked-LM rows: the rows of tm_batch_collate (doc_index == NULL; bad_out is then written as 0) or of tm_batch_collate_select (doc_index
+ * given) with a share of their CONTENT ids replaced by mask_id or by a random id, and the originals in labels_out - BERT / RoBERTa dynamic
+ * masking, or SpanBERT-style spans.  The layout, mask_out and lengths_out are exactly those calls'.  The rule is stateless and keyed by
+ * the place of an id in the run, not in a row: one seed masks a document the same way whatever row, padding side, cut or batch it lands
+ * in, and a new seed per step gives dynamic masking.  Let g be the index of a content id in the batch's id buffer and [t0, t1) its document:
+ *  1. (w0, w1, w2, w3) = Philox4x32-10 of counter (g & 0xFFFFFFFF, g >> 32, 0, 0) under key (seed & 0xFFFFFFFF, seed >> 32): the published
+ *     round function, multipliers 0xD2511F53 and 0xCD9E8D57, key increments 0x9E3779B9 and 0xBB67AE85, ten rounds, the key bumped before
+ *     every round but the first;
+ *  2. reach(g) = w0 < start_thr ? span_min + mulhi32(w1, span_max - span_min + 1) : 0      (mulhi32: the high half of the 64-bit product);
+ *  3. rem(g) = max(reach(g), rem(g - 1) - 1), rem(t0 - 1) = 0; g is SELECTED iff rem(g) >= 1 - some g - k >= t0, k < span_max, has
+ *     reach(g - k) > k.  Spans never cross a document's start or end, but do reach into a row from ids of its document the row cut off;
+ *  4. a selected id becomes mask_id if w2 < mask_thr, random_lo + mulhi32(w3, random_n) if w2 < mask_thr + random_thr, and else stays;
+ *  5. labels_out ([rows * row_len] elements of id_bytes, may be NULL): the original id in a selected content column, label_ignore
+ *     sign-extended everywhere else - unselected ids, BOS, EOS, padding, the rows of a bad index.
+ * TM_E_INVALID: a NULL m; spans outside 1 <= span_min <= span_max <= 32; a threshold, or mask_thr + random_thr, above 2^32; random_n == 0
+ * with random_thr > 0; mask_id or random_lo + random_n - 1 beyond id_bytes or 32 bits; with id_bytes == 2 a label_ignore outside
+ * 0 .. 65535.  Everything else - argument errors, the limit of 2^36 elements, the wait for the batch's last run, nothing kept in the batch,
+ * every element of every given output written, any base that is a multiple of the element size - is tm_batch_collate_select's.  Ids from
+ * tm_batch_load_ids are accepted.  Not covered: the window, pair, pack and fit layouts; whole-word masking; T5 sentinel compaction. */
+typedef struct tm_masking {
+  uint64_t seed;
+  uint64_t start_thr;            /* 0 .. 2^32: an id opens a span iff w0 < start_thr                      */
+  uint32_t span_min, span_max;   /* 1 <= span_min <= span_max <= 32; (1,1) = token masking                */
+  uint64_t mask_thr, random_thr; /* mask_thr + random_thr <= 2^32; the rest of a selected id is kept      */
+  uint32_t mask_id;
+  uint32_t random_lo, random_n;  /* random ids are random_lo .. random_lo + random_n - 1 (n >= 1 if random_thr > 0) */
+  int32_t  label_ignore;         /* sign-extended to id_bytes, e.g. -100                                  */
+} tm_masking;
+int tm_batch_collate_masked(tm_batch* b, const tm_collate* how, const tm_masking* m, const uint32_t* doc_index, void* stream,
+                            void* ids_out, void* labels_out, uint8_t* mask_out, uint32_t* lengths_out, uint32_t* bad_out);
 /* tm_batch_length_order: the documents first_doc .. first_doc + ndocs - 1 of the last run in the order of their id counts
  * n_d = tok_offsets[d + 1] - tok_offsets[d] (one of 2^32 ids or more counts as 2^32 - 1), ascending, under TM_ORDER_DESCENDING descending.
  * STABLE in both directions: documents of equal count stand in ascending document number.  order_out[ndocs] (device or page-locked memory)

@@ -326,6 +326,8 @@ int check_ids_fit(const tm_batch* b, uint32_t id_bytes, std::initializer_list<ui
 // point makes the two checks apart, or only the second, it asks for one at a time: rows = 0, or ns = 0, switches the other off.
 int check_row_room(const char* who, uint32_t row_len, uint32_t ns, uint64_t rows, const char* what);
 int check_rows_cap(const char* who, uint64_t rows_cap, uint64_t rows);
+// tm_collate.hip: the rows of a list whose index is no document of the run, counted into *bad_out on `st` (k_select_bad; no rows: 0)
+void launch_select_bad(const uint32_t* doc_index, uint32_t rows, uint32_t run_docs, uint32_t* bad_out, hipStream_t st);
 // tm_spans.hip: no document of the run is 2^32 bytes or longer (offsets are 32 bits)
 int spans_check_lengths(tm_batch* b, const char* who);
 // tm_windows.hip: the batch's window buffer for nd documents (or pairs) - win_off[cap + 1] | block sums of the scan, its total behind them |

@@ -218,6 +218,9 @@ template <typename T, bool MASK>
 static void launch_select(const SelectArgs& s, void* out, hipStream_t st, uint32_t* lengths_out = nullptr) {
   launch_flat<256 * SEL_VECS>(k_collate_select<T, MASK>, st, static_cast<T*>(out), (uint64_t)s.a.rows * s.a.L, lengths_out ? s.a.rows : 0, s, static_cast<T*>(out), lengths_out);
 }
+void launch_select_bad(const uint32_t* doc_index, uint32_t rows, uint32_t run_docs, uint32_t* bad_out, hipStream_t st) {
+  TM_LAUNCH(k_select_bad, 1, 1024, 0, st, doc_index, rows, run_docs, bad_out);
+}
 template <typename T, int WHAT>
 static void launch_pack(const PackArgs& a, void* out, uint64_t n, hipStream_t st) {
   launch_flat(k_pack_stream<T, WHAT>, st, static_cast<T*>(out), n, 0, a, static_cast<T*>(out));
@@ -279,7 +282,7 @@ int tm_batch_collate_select(tm_batch* b, const tm_collate* how, const uint32_t* 
   if ((rc = enter_device(b->vocab)) != TM_OK || (rc = ensure_output(b)) != TM_OK) return rc;      // (waits for the run: the ids are all there)
   hipStream_t st = (hipStream_t)stream;
   (void)hipGetLastError();
-  if (bad_out) TM_LAUNCH(k_select_bad, 1, 1024, 0, st, doc_index, how->ndocs, b->ndocs, bad_out);
+  if (bad_out) launch_select_bad(doc_index, how->ndocs, b->ndocs, bad_out, st);
   if (how->ndocs == 0) return bad_out ? launch_check() : TM_OK;
   const SelectArgs s{CollateArgs{b->d_out, b->d_tok_offsets, how->ndocs, how->row_len, how->pad_id, how->bos_id, how->eos_id, how->flags}, doc_index, b->ndocs};
   with_id_type(how->id_bytes, [&](auto z) { launch_select<decltype(z), false>(s, ids_out, st, lengths_out); });

@@ -8,6 +8,7 @@ without an id crossing the host link (tm_batch_collate / tm_batch_windows / tm_b
     pack_batch     the pre-training form: one EOS-separated id stream cut into rows, with document numbers and positions
     decode_batch   a [rows, L] tensor of ids -> list of bytes
     tokenize_resident   tokenize once, draw batches many times: the documents' length order and encode_batch's rows by document number
+    Masking        masked-LM corruption of encode_batch's and ResidentBatch.collate's rows on the device, with "labels" (masking=..., seed=...)
 
 torch is imported on first use; nothing else in the package imports this module.  A program that uses it imports torch BEFORE
 tokenmonster_amd: torch ships a HIP runtime of its own, the one loaded first serves the whole process, and only torch's serves both.  The kernels run on torch's CURRENT stream of the
@@ -28,6 +29,33 @@ PAD_LEFT, KEEP_TAIL = 1, 2
 class _Collate(C.Structure):
     """tm_collate"""
     _fields_ = [(n, C.c_uint32) for n in ("first_doc", "ndocs", "row_len", "id_bytes", "pad_id", "bos_id", "eos_id", "flags")]
+
+
+class Masking:
+    """Masked-LM corruption for encode_batch(masking=...) and ResidentBatch.collate(masking=...) (tm_batch_collate_masked; the rule:
+    include/tokenmonster_hip.h).  An id of a document opens a span with probability `probability` / mean span length, a span covers
+    span[0] .. span[1] ids (uniform; (1, 1): token masking as BERT and RoBERTa do it, (1, 10) or so: SpanBERT-like), and an id a span covers
+    becomes mask_id with probability mask_share, a random id of random_ids = (lo, n) - lo .. lo + n - 1; None: every id of the vocabulary -
+    with random_share, and else stays as it is.  "labels" holds the original id in every covered column and `ignore` elsewhere (BOS, EOS
+    and padding are never covered).  Spans may overlap and are cut at their document's end, so the share of ids covered comes out somewhat
+    below `probability` - the more so the longer the spans.  The masks depend on the seed and on the place of an id in the batch of
+    documents alone, not on the row layout: pass a new seed per step for dynamic masking."""
+
+    def __init__(self, *, mask_id, probability=0.15, span=(1, 1), mask_share=0.8, random_share=0.1, random_ids=None, ignore=-100):
+        lo, hi = int(span[0]), int(span[1])
+        if not 1 <= lo <= hi <= 32:
+            raise ValueError("span %r: 1 <= span[0] <= span[1] <= 32" % (span,))
+        if not (0 <= probability <= 1 and 0 <= mask_share and 0 <= random_share and mask_share + random_share <= 1):
+            raise ValueError("probability, mask_share, random_share and mask_share + random_share: 0 .. 1")
+        self.mask_id, self.span, self.random_ids, self.ignore = int(mask_id), (lo, hi), random_ids, int(ignore)
+        self.start_thr = min(round((1 << 32) * probability / ((lo + hi) / 2)), 1 << 32)
+        self.mask_thr = round((1 << 32) * mask_share)
+        self.random_thr = min(round((1 << 32) * random_share), (1 << 32) - self.mask_thr)
+
+    def struct(self, vocab, seed):
+        """tm_masking under `seed`"""
+        lo, n = self.random_ids if self.random_ids is not None else (0, vocab.n_ids())
+        return N.Masking(int(seed) & 0xFFFFFFFFFFFFFFFF, self.start_thr, self.span[0], self.span[1], self.mask_thr, self.random_thr, self.mask_id, int(lo), int(n), self.ignore)
 
 
 def _torch():
@@ -149,7 +177,7 @@ def _check_dtype(torch, dtype):
 
 
 def encode_batch(vocab, docs, max_length, *, pad_id, bos_id=None, eos_id=None, pad_left=False, keep_tail=False, dtype=None, raw=True, device=None, return_offsets=False,
-                 offset_unit="bytes", regions=None, ignore_label=-100):
+                 offset_unit="bytes", regions=None, ignore_label=-100, masking=None, seed=0):
     """documents (bytes or str; raw=False: already normalized bytes) -> {"input_ids" [rows, max_length] of `dtype` (default int64),
     "attention_mask" [rows, max_length] bool, "lengths" [rows] int32}, CUDA tensors on the vocabulary's device.  Row r is
     [bos] ids [eos] pad...: the ids cut to max_length less the specials given (their head; keep_tail: their tail), the padding on the
@@ -163,8 +191,12 @@ def encode_batch(vocab, docs, max_length, *, pad_id, bos_id=None, eos_id=None, p
     label) counted in offset_unit from its document's start - in the document as passed in with raw=True, else in the normalized text -, sorted
     and without overlap inside a document, reg_offsets [rows + 1]; both host arrays or tensors of the vocabulary's device (int64 / int32
     regions, int64 offsets).  A column holds the label of the first region its id meets, ignore_label elsewhere and on BOS, EOS and padding
-    (tm_batch_collate_region_labels; the rule: include/tokenmonster_hip.h)."""
+    (tm_batch_collate_region_labels; the rule: include/tokenmonster_hip.h).
+    masking=Masking(...) (not beside regions) corrupts "input_ids" for a masked-LM step under `seed` and adds "labels" [rows, max_length] of
+    `dtype`: the original id where an id was selected, masking.ignore elsewhere (tm_batch_collate_masked)."""
     unit = span_unit(offset_unit)
+    if masking is not None and regions is not None:
+        raise ValueError("masking and regions both write \"labels\": one of them")
     if isinstance(return_offsets, str):
         if return_offsets != "raw":
             raise ValueError("return_offsets %r: False, True or \"raw\"" % (return_offsets,))
@@ -184,8 +216,13 @@ def encode_batch(vocab, docs, max_length, *, pad_id, bos_id=None, eos_id=None, p
         mask = torch.empty((nd, max_length), dtype=torch.uint8, device=dev)
         lengths = torch.empty((nd,), dtype=torch.int32, device=dev)
         how = _Collate(0, nd, max_length, id_bytes, int(pad_id), _special(bos_id), _special(eos_id), (PAD_LEFT if pad_left else 0) | (KEEP_TAIL if keep_tail else 0))
-        N.check(N.lib.tm_batch_collate(b, C.byref(how), st, ids.data_ptr(), mask.data_ptr(), lengths.data_ptr()))
         res = {"input_ids": ids, "attention_mask": mask.view(torch.bool), "lengths": lengths}
+        if masking is None:
+            N.check(N.lib.tm_batch_collate(b, C.byref(how), st, ids.data_ptr(), mask.data_ptr(), lengths.data_ptr()))
+        else:
+            res["labels"] = torch.empty((nd, max_length), dtype=dtype, device=dev)
+            N.check(N.lib.tm_batch_collate_masked(b, C.byref(how), C.byref(masking.struct(vocab, seed)), None, st, ids.data_ptr(), res["labels"].data_ptr(), mask.data_ptr(),
+                                                  lengths.data_ptr(), None))
         if return_offsets:
             spans = torch.empty((nd, max_length, 2), dtype=torch.int64, device=dev)
             text = N.TM_TEXT_RAW if return_offsets == "raw" else N.TM_TEXT_NORMALIZED
@@ -452,11 +489,13 @@ class ResidentBatch:
     def length_order(self, descending=False):
         return self._order(descending)[0]
 
-    def collate(self, indices, max_length, *, pad_id, bos_id=None, eos_id=None, pad_left=False, keep_tail=False, dtype=None):
+    def collate(self, indices, max_length, *, pad_id, bos_id=None, eos_id=None, pad_left=False, keep_tail=False, dtype=None, masking=None, seed=0):
         """row r = the row encode_batch gives document indices[r]: {"input_ids" [rows, max_length] of `dtype` (default int64), "attention_mask"
         [rows, max_length] bool, "lengths" [rows] int32, "bad_indices" int32 scalar on the device: the entries of `indices` that name no
         document - their rows are padding only}.  indices: an integer tensor (moved to the device if it is not there) or a sequence; a
-        document may stand in any number of rows."""
+        document may stand in any number of rows.  masking=Masking(...): the rows corrupted for a masked-LM step under `seed`, and "labels"
+        [rows, max_length] of `dtype` beside them, as encode_batch gives them (tm_batch_collate_masked): a document is masked the same way in
+        whatever row or batch it stands, and differently under every seed."""
         torch = _torch()
         dtype = dtype or torch.int64
         id_bytes = _check_dtype(torch, dtype)
@@ -476,11 +515,17 @@ class ResidentBatch:
             lengths = torch.empty((rows,), dtype=torch.int32, device=self.dev)
             bad = torch.empty((), dtype=torch.int32, device=self.dev)
             how = _Collate(0, rows, max_length, id_bytes, int(pad_id), _special(bos_id), _special(eos_id), (PAD_LEFT if pad_left else 0) | (KEEP_TAIL if keep_tail else 0))
-            if rows:
+            res = {"input_ids": ids, "attention_mask": mask.view(torch.bool), "lengths": lengths, "bad_indices": bad}
+            if masking is not None:
+                res["labels"] = torch.empty((rows, max_length), dtype=dtype, device=self.dev)
+            if not rows:
+                bad.zero_()
+            elif masking is None:
                 N.check(N.lib.tm_batch_collate_select(self.handle, C.byref(how), idx.data_ptr(), st, ids.data_ptr(), mask.data_ptr(), lengths.data_ptr(), bad.data_ptr()))
             else:
-                bad.zero_()
-        return {"input_ids": ids, "attention_mask": mask.view(torch.bool), "lengths": lengths, "bad_indices": bad}
+                N.check(N.lib.tm_batch_collate_masked(self.handle, C.byref(how), C.byref(masking.struct(self.vocab, seed)), idx.data_ptr(), st, ids.data_ptr(),
+                                                      res["labels"].data_ptr(), mask.data_ptr(), lengths.data_ptr(), bad.data_ptr()))
+        return res
 
     def close(self):
         if self.handle:

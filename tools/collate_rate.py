@@ -10,7 +10,8 @@ the yardstick is hipMemcpyAsync device to device of that many bytes (half read, 
 the median of 20.  --only pairs: the pair lines alone; --only fit: whole-document packing (tm_batch_fit) beside pack on the same batch, and on
 300 000 and 1 048 576 short documents; --only select: tm_batch_collate_select through the identity, the length order and a random
 permutation beside tm_batch_collate of the same documents, and tm_batch_length_order beside torch.sort(stable=True) on 300 000 and 1 048 576
-documents and on either side of a digit boundary of the largest count; --append: add to --out under a dated heading instead of replacing it.  (tm_batch_collate / tm_batch_pack wait for the batch's last run before they launch and tm_batch_pack_rows fetches two
+documents and on either side of a digit boundary of the largest count; --only masked: tm_batch_collate_masked (int64 ids and labels) beside
+tm_batch_collate_select of the same rows at L = 512; --append: add to --out under a dated heading instead of replacing it.  (tm_batch_collate / tm_batch_pack wait for the batch's last run before they launch and tm_batch_pack_rows fetches two
 offsets: host time, outside the kernels but inside the events - with 256 MiB of text it is a few percent of a call.)"""
 import argparse
 import ctypes as C
@@ -47,7 +48,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mib", type=int, default=256)
     ap.add_argument("--out", default=os.path.join("profiles", "collate.txt"))
-    ap.add_argument("--only", choices=["pairs", "fit", "select"], default=None)
+    ap.add_argument("--only", choices=["pairs", "fit", "select", "masked"], default=None)
     ap.add_argument("--append", action="store_true")
     a = ap.parse_args()
     L = 2048
@@ -65,7 +66,7 @@ def main():
     N.check(N.lib.tm_batch_totals(b, C.byref(total), None))
     n_ids, pad, eos = int(total.value), v.n_ids(), v.n_ids() + 1
     lines = ["%d MiB of englishcode-32000 text, %d documents, %d ids, L = %s; median of 20 (min .. max), GB/s = bytes read + written" % (
-        a.mib, nd, n_ids, "512" if a.only == "pairs" else "%d (the pair lines: 512)" % L)]
+        a.mib, nd, n_ids, "512" if a.only in ("pairs", "masked") else "%d (the pair lines: 512)" % L)]
 
     def copy_rate(nbytes):
         src = torch.empty(nbytes // 2, dtype=torch.uint8, device="cuda")
@@ -197,6 +198,27 @@ def main():
             report("select, %s" % name, nbytes + nd * 4, smed, lo, hi)
             lines.append("  (less collate: %+.3f ms)" % (smed - med))
 
+    def masked_lines():
+        """tm_batch_collate_masked, int64 ids + int64 labels + mask + lengths, beside tm_batch_collate_select of the SAME rows (a random permutation of
+        every document, L = 512: rows a model trains on) - token masking, SpanBERT-like spans, and start_thr 0, where no id is selected and what is
+        left of the masked call is its row walk and the second output.  The ratio is masked / select in time."""
+        LM = 512
+        ids, labels = (torch.empty((nd, LM), dtype=torch.int64, device="cuda") for _ in range(2))
+        mask = torch.empty((nd, LM), dtype=torch.uint8, device="cuda")
+        lens = torch.empty((nd,), dtype=torch.int32, device="cuda")
+        idx = torch.randperm(nd, device="cuda").to(torch.int32)
+        how = torch_api._Collate(0, nd, LM, 8, pad, N.TM_NONE, N.TM_NONE, 0)
+        smed, lo, hi = timed(lambda: N.check(N.lib.tm_batch_collate_select(b, C.byref(how), idx.data_ptr(), st, ids.data_ptr(), mask.data_ptr(), lens.data_ptr(), None)), stream)
+        nbytes = int(lens.to(torch.int64).sum().item()) * 4 + nd * LM * 9 + nd * 8
+        report("select int64 + mask + lengths, L = %d" % LM, nbytes, smed, lo, hi)
+        for name, mk in (("nothing selected", torch_api.Masking(mask_id=eos + 1, probability=0.0)), ("tokens, p = 0.15", torch_api.Masking(mask_id=eos + 1)),
+                         ("spans 1 .. 10, p = 0.15", torch_api.Masking(mask_id=eos + 1, span=(1, 10)))):
+            m = mk.struct(v, 1)
+            med, lo, hi = timed(lambda: N.check(N.lib.tm_batch_collate_masked(b, C.byref(how), C.byref(m), idx.data_ptr(), st, ids.data_ptr(), labels.data_ptr(), mask.data_ptr(),
+                                                                             lens.data_ptr(), None)), stream)
+            report("masked + labels, %s" % name, nbytes + nd * LM * 8, med, lo, hi)
+            lines.append("  (masked / select in time: %.2f; %.1f%% of the content ids selected)" % (med / smed, 100.0 * int((labels != -100).sum().item()) / max(int(lens.to(torch.int64).sum().item()), 1)))
+
     def order_lines(k, W, top):
         """tm_batch_length_order on k documents of 0 .. 255 ids each, one of them of `top` ids (tm_batch_load_ids of rows of W two-byte ids), beside
         torch.sort(stable=True) of the same counts on the same device; the order is checked against torch's"""
@@ -217,10 +239,12 @@ def main():
         print(lines[-1], flush=True)
         N.lib.tm_batch_free(bk)
 
-    if a.only in ("pairs", "fit", "select"):
+    if a.only in ("pairs", "fit", "select", "masked"):
         with torch.cuda.stream(stream):
             if a.only == "pairs":
                 pairs_lines()
+            elif a.only == "masked":
+                masked_lines()
             elif a.only == "select":
                 select_lines()
                 for k, W, top in ((300000, 256, 255), (1048576, 256, 255), (1048576, 257, 256), (4096, 65537, 65535), (4096, 65537, 65536)):
