@@ -1380,6 +1380,7 @@ static int norm_begin(tm_batch* b, hipStream_t st, const uint64_t* h_raw_off, bo
   b->d_doc_end = b->d_nend;
   b->ndocs = nd; b->nbytes = 0; b->nseg = 0; b->ngroups = 0; b->nlong = 0;
   b->text_in_slabs = false;
+  b->has_output = false;                       // (a normalize by itself, over raw text uploaded before the last run: that run's ids are not these documents')
   units_forget(b, 1u);
   b->slab_pieces = s->np;
   if (nd == 0) return TM_OK;
