@@ -385,6 +385,35 @@ func (b *HipBatch) CollateMasked(how HipCollate, m HipMasking, docIndex, stream,
 	return err
 }
 
+// HipDenoise is tm_denoise: T5 / UL2 span corruption (the rule: include/tokenmonster_hip.h).  An id opens a noise span of SpanMin .. SpanMax ids
+// with probability StartThr / 2^32; span k of a row becomes the one sentinel SentinelFirst + k * SentinelStep in the input row, at most
+// SentinelN of them a row; a target row has TargetLen columns, LabelIgnore behind its entries.
+type HipDenoise struct {
+	Seed             uint64
+	StartThr         uint64
+	SpanMin, SpanMax uint32
+	SentinelFirst    uint32
+	SentinelStep     int32
+	SentinelN        uint32
+	TargetLen        uint32
+	LabelIgnore      int32
+}
+
+// CollateDenoise is Collate (docIndex nil) or CollateSelect with span corruption: ids receives the input rows, every noise span shrunk to its
+// sentinel; targets (may be nil, how.Docs * dn.TargetLen elements of IdBytes) the spans behind their sentinels; targetLengths (may be nil) the
+// uncut entries of every target row (tm_batch_collate_denoise).
+func (b *HipBatch) CollateDenoise(how HipCollate, dn HipDenoise, docIndex, stream, ids, targets, mask, lengths, targetLengths, bad unsafe.Pointer) error {
+	h := how.c()
+	cd := C.tm_denoise{seed: C.uint64_t(dn.Seed), start_thr: C.uint64_t(dn.StartThr), span_min: C.uint32_t(dn.SpanMin), span_max: C.uint32_t(dn.SpanMax),
+		sentinel_first: C.uint32_t(dn.SentinelFirst), sentinel_step: C.int32_t(dn.SentinelStep), sentinel_n: C.uint32_t(dn.SentinelN),
+		target_len: C.uint32_t(dn.TargetLen), label_ignore: C.int32_t(dn.LabelIgnore)}
+	_, err := locked(func() C.int {
+		return C.tm_batch_collate_denoise(b.h, &h, &cd, (*C.uint32_t)(docIndex), stream, ids, targets, (*C.uint8_t)(mask), (*C.uint32_t)(lengths),
+			(*C.uint32_t)(targetLengths), (*C.uint32_t)(bad))
+	})
+	return err
+}
+
 // LengthOrder writes the documents firstDoc .. firstDoc + docs - 1 of the last run to order (docs uint32, device or page-locked memory) as absolute
 // document numbers in the order of their id counts - ascending, descending if asked - documents of equal count in ascending document number;
 // counts (may be nil) receives the count of order[i].  What CollateSelect takes as its docIndex (tm_batch_length_order).

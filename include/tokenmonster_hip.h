@@ -316,7 +316,8 @@ int tm_batch_collate_select(tm_batch* b, const tm_collate* how, const uint32_t* 
  * with random_thr > 0; mask_id or random_lo + random_n - 1 beyond id_bytes or 32 bits; with id_bytes == 2 a label_ignore outside
  * 0 .. 65535.  Everything else - argument errors, the limit of 2^36 elements, the wait for the batch's last run, nothing kept in the batch,
  * every element of every given output written, any base that is a multiple of the element size - is tm_batch_collate_select's.  Ids from
- * tm_batch_load_ids are accepted.  Not covered: the window, pair, pack and fit layouts; whole-word masking; T5 sentinel compaction. */
+ * tm_batch_load_ids are accepted.  Not covered: the window, pair, pack and fit layouts; whole-word masking.  T5 sentinel compaction:
+ * tm_batch_collate_denoise below. */
 typedef struct tm_masking {
   uint64_t seed;
   uint64_t start_thr;            /* 0 .. 2^32: an id opens a span iff w0 < start_thr                      */
@@ -328,6 +329,45 @@ typedef struct tm_masking {
 } tm_masking;
 int tm_batch_collate_masked(tm_batch* b, const tm_collate* how, const tm_masking* m, const uint32_t* doc_index, void* stream,
                             void* ids_out, void* labels_out, uint8_t* mask_out, uint32_t* lengths_out, uint32_t* bad_out);
+/* Span corruption, the denoising objective of T5 and UL2: the rows of tm_batch_collate (doc_index == NULL; bad_out is then written as 0) or
+ * of tm_batch_collate_select (doc_index given; first_doc must be 0) as the INPUT of an encoder-decoder, every noise span shrunk to one
+ * sentinel id, and beside them a TARGET row per document with the spans behind their sentinels.  Unlike the masked rows these compact: an
+ * id's column depends on what was selected in front of it.  Let W = [src, src + m) be the content ids tm_batch_collate keeps for the row -
+ * the document cut to row_len less the specials given, its tail under TM_COLLATE_KEEP_TAIL:
+ *  1. sel(g), g in W, is rules 1 - 3 of tm_batch_collate_masked with seed, start_thr, span_min and span_max from tm_denoise.  It is computed
+ *     over the DOCUMENT, so spans reach into W from ids the row cut off, and it is keyed by g, so a document is corrupted the same way in
+ *     any row or batch;
+ *  2. a noise span is a maximal run of consecutive g in W with sel(g); the spans of a row are numbered k = 0, 1, ... in ascending order.
+ *     Spans with k >= sentinel_n are no noise: their ids count as unselected.  s(k) = sentinel_first + k * sentinel_step;
+ *  3. the input row, ids_out[rows * row_len]: [bos], then for the ids of W in order - an unselected id: itself; the first id of span k:
+ *     s(k); every other id of a span: nothing -, then [eos], then pad_id up to row_len.  mask_out (may be NULL) is 1 on an entry and 0 on
+ *     padding, lengths_out (may be NULL) the entries of the input row.  It never has more entries than the plain row: it always fits;
+ *  4. the target row, targets_out[rows * target_len] elements of id_bytes (may be NULL): for k = 0, 1, ...: s(k), then the ids of span k;
+ *     then eos_id if given; then label_ignore, sign-extended, up to target_len.  No BOS and no closing sentinel: what T5's own preprocessor
+ *     emits.  target_lengths_out[r] (may be NULL) is the UNCUT number of entries, EOS included (one of 2^32 or more counts as 2^32 - 1);
+ *     where it exceeds target_len the row holds the first target_len - he content entries and then the EOS, he = 1 if eos_id is given,
+ *     else 0 - the caller sees every cut row there.  Nothing selected: the target is [eos] alone.
+ * A row of a bad index: the input row pad_id only, mask 0, length 0; the target row label_ignore only, target length 0.
+ * TM_E_INVALID: a NULL dn; spans outside 1 <= span_min <= span_max <= 32; start_thr above 2^32; sentinel_step == 0; sentinel_n == 0;
+ * target_len == 0; any s(k), k < sentinel_n, outside 0 .. 2^(8 * min(id_bytes, 4)) - 1; with id_bytes == 2 a label_ignore outside
+ * 0 .. 65535; TM_COLLATE_PAD_LEFT - left padding needs the compacted length before the first store, and encoder-decoder models pad
+ * right; rows * target_len beyond 2^36 elements.  Everything else - argument errors, the limit of 2^36 elements of ids_out, the wait for
+ * the batch's last run, nothing kept in the batch, every element of every given output written, any base that is a multiple of the
+ * element size, bad indices and bad_out - is tm_batch_collate_masked's.  Ids from tm_batch_load_ids are accepted.  One workgroup walks one
+ * row (tm_denoise.hip): rows of a few thousand ids are what it is for. */
+typedef struct tm_denoise {
+  uint64_t seed;
+  uint64_t start_thr;              /* 0 .. 2^32, as in tm_masking                                           */
+  uint32_t span_min, span_max;     /* 1 <= span_min <= span_max <= 32                                       */
+  uint32_t sentinel_first;         /* id of noise span 0 of a row                                           */
+  int32_t  sentinel_step;          /* span k gets sentinel_first + k * sentinel_step (T5: -1); not 0        */
+  uint32_t sentinel_n;             /* >= 1: a row uses at most this many sentinels                          */
+  uint32_t target_len;             /* T >= 1: columns of a target row                                       */
+  int32_t  label_ignore;           /* target padding, sign-extended to id_bytes                             */
+} tm_denoise;
+int tm_batch_collate_denoise(tm_batch* b, const tm_collate* how, const tm_denoise* dn, const uint32_t* doc_index, void* stream,
+                             void* ids_out, void* targets_out, uint8_t* mask_out, uint32_t* lengths_out,
+                             uint32_t* target_lengths_out, uint32_t* bad_out);
 /* tm_batch_length_order: the documents first_doc .. first_doc + ndocs - 1 of the last run in the order of their id counts
  * n_d = tok_offsets[d + 1] - tok_offsets[d] (one of 2^32 ids or more counts as 2^32 - 1), ascending, under TM_ORDER_DESCENDING descending.
  * STABLE in both directions: documents of equal count stand in ascending document number.  order_out[ndocs] (device or page-locked memory)

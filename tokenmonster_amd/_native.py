@@ -30,6 +30,12 @@ class Masking(C.Structure):
                 ("mask_id", C.c_uint32), ("random_lo", C.c_uint32), ("random_n", C.c_uint32), ("label_ignore", C.c_int32)]
 
 
+class Denoise(C.Structure):
+    """tm_denoise"""
+    _fields_ = [("seed", C.c_uint64), ("start_thr", C.c_uint64), ("span_min", C.c_uint32), ("span_max", C.c_uint32), ("sentinel_first", C.c_uint32),
+                ("sentinel_step", C.c_int32), ("sentinel_n", C.c_uint32), ("target_len", C.c_uint32), ("label_ignore", C.c_int32)]
+
+
 class Pair(C.Structure):
     """tm_pair"""
     _fields_ = [(n, C.c_uint32) for n in ("first_a", "first_b", "npairs", "row_len", "id_bytes", "pad_id", "bos_id", "sep_id", "eos_id", "sep_count",
@@ -112,6 +118,7 @@ SIGNATURES = {
     "tm_tokenize_batch_raw_spans": (C.c_int, [vp, vp, vp, C.c_uint32, vp, C.c_uint64, vp, vp, vp]),
     "tm_batch_collate_select": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp]),
     "tm_batch_collate_masked": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "tm_batch_collate_denoise": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "tm_batch_length_order": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp]),
     "tm_batch_fit_rows": (C.c_int, [vp, vp, u64p]),
     "tm_batch_fit": (C.c_int, [vp, vp, vp, C.c_uint64, vp, vp, vp, vp, vp, vp]),

@@ -9,6 +9,7 @@ without an id crossing the host link (tm_batch_collate / tm_batch_windows / tm_b
     decode_batch   a [rows, L] tensor of ids -> list of bytes
     tokenize_resident   tokenize once, draw batches many times: the documents' length order and encode_batch's rows by document number
     Masking        masked-LM corruption of encode_batch's and ResidentBatch.collate's rows on the device, with "labels" (masking=..., seed=...)
+    SpanCorruption T5 / UL2 span corruption of the same rows: sentinel inputs, and the spans as "labels" (denoise=..., target_length=..., seed=...)
 
 torch is imported on first use; nothing else in the package imports this module.  A program that uses it imports torch BEFORE
 tokenmonster_amd: torch ships a HIP runtime of its own, the one loaded first serves the whole process, and only torch's serves both.  The kernels run on torch's CURRENT stream of the
@@ -56,6 +57,40 @@ class Masking:
         """tm_masking under `seed`"""
         lo, n = self.random_ids if self.random_ids is not None else (0, vocab.n_ids())
         return N.Masking(int(seed) & 0xFFFFFFFFFFFFFFFF, self.start_thr, self.span[0], self.span[1], self.mask_thr, self.random_thr, self.mask_id, int(lo), int(n), self.ignore)
+
+
+class SpanCorruption:
+    """T5 / UL2 span corruption for encode_batch(denoise=...) and ResidentBatch.collate(denoise=...) (tm_batch_collate_denoise; the rule:
+    include/tokenmonster_hip.h).  An id of a document opens a noise span with probability noise_density / mean span length, a span covers
+    span[0] .. span[1] ids (uniform), exactly as Masking selects.  Noise span k of a row becomes the ONE id sentinel_first + k * sentinel_step
+    in "input_ids" (T5's <extra_id_k> count down from the vocabulary's end: sentinel_step -1), and "labels" [rows, target_length] holds every
+    span behind its sentinel, then the EOS, then `ignore`.  A row uses at most sentinel_n sentinels: later spans stay as they are.
+    "target_lengths" holds the uncut length of every target row, so a row cut at target_length shows.  The spans depend on the seed and on
+    the place of an id in the batch of documents alone: pass a new seed per step."""
+
+    def __init__(self, sentinel_first, sentinel_step=-1, sentinel_n=100, noise_density=0.15, span=(1, 5), ignore=-100):
+        lo, hi = int(span[0]), int(span[1])
+        if not 1 <= lo <= hi <= 32:
+            raise ValueError("span %r: 1 <= span[0] <= span[1] <= 32" % (span,))
+        if not 0 <= noise_density <= 1:
+            raise ValueError("noise_density: 0 .. 1")
+        if int(sentinel_step) == 0 or int(sentinel_n) < 1:
+            raise ValueError("sentinel_step 0 or sentinel_n < 1")
+        self.sentinel_first, self.sentinel_step, self.sentinel_n, self.span, self.ignore = int(sentinel_first), int(sentinel_step), int(sentinel_n), (lo, hi), int(ignore)
+        self.start_thr = min(round((1 << 32) * noise_density / ((lo + hi) / 2)), 1 << 32)
+
+    def struct(self, target_length, seed):
+        """tm_denoise under `seed`"""
+        return N.Denoise(int(seed) & 0xFFFFFFFFFFFFFFFF, self.start_thr, self.span[0], self.span[1], self.sentinel_first, self.sentinel_step, self.sentinel_n,
+                         int(target_length), self.ignore)
+
+
+def _check_denoise(denoise, target_length, masking, regions, pad_left):
+    if denoise is not None:
+        if masking is not None or regions is not None or pad_left:
+            raise ValueError("denoise beside masking, regions or pad_left: span corruption writes \"labels\" of its own and pads on the right")
+        if target_length is None or int(target_length) < 1:
+            raise ValueError("denoise needs target_length >= 1: the columns of \"labels\"")
 
 
 def _torch():
@@ -177,7 +212,7 @@ def _check_dtype(torch, dtype):
 
 
 def encode_batch(vocab, docs, max_length, *, pad_id, bos_id=None, eos_id=None, pad_left=False, keep_tail=False, dtype=None, raw=True, device=None, return_offsets=False,
-                 offset_unit="bytes", regions=None, ignore_label=-100, masking=None, seed=0):
+                 offset_unit="bytes", regions=None, ignore_label=-100, masking=None, seed=0, denoise=None, target_length=None):
     """documents (bytes or str; raw=False: already normalized bytes) -> {"input_ids" [rows, max_length] of `dtype` (default int64),
     "attention_mask" [rows, max_length] bool, "lengths" [rows] int32}, CUDA tensors on the vocabulary's device.  Row r is
     [bos] ids [eos] pad...: the ids cut to max_length less the specials given (their head; keep_tail: their tail), the padding on the
@@ -193,8 +228,12 @@ def encode_batch(vocab, docs, max_length, *, pad_id, bos_id=None, eos_id=None, p
     regions, int64 offsets).  A column holds the label of the first region its id meets, ignore_label elsewhere and on BOS, EOS and padding
     (tm_batch_collate_region_labels; the rule: include/tokenmonster_hip.h).
     masking=Masking(...) (not beside regions) corrupts "input_ids" for a masked-LM step under `seed` and adds "labels" [rows, max_length] of
-    `dtype`: the original id where an id was selected, masking.ignore elsewhere (tm_batch_collate_masked)."""
+    `dtype`: the original id where an id was selected, masking.ignore elsewhere (tm_batch_collate_masked).
+    denoise=SpanCorruption(...) (not beside masking, regions or pad_left) makes the rows the input of a T5-style denoising step under `seed`:
+    every noise span of "input_ids" one sentinel, "labels" [rows, target_length] of `dtype` the spans behind their sentinels, and
+    "target_lengths" [rows] int32 their uncut lengths (tm_batch_collate_denoise).  "lengths" counts the compacted rows."""
     unit = span_unit(offset_unit)
+    _check_denoise(denoise, target_length, masking, regions, pad_left)
     if masking is not None and regions is not None:
         raise ValueError("masking and regions both write \"labels\": one of them")
     if isinstance(return_offsets, str):
@@ -217,7 +256,12 @@ def encode_batch(vocab, docs, max_length, *, pad_id, bos_id=None, eos_id=None, p
         lengths = torch.empty((nd,), dtype=torch.int32, device=dev)
         how = _Collate(0, nd, max_length, id_bytes, int(pad_id), _special(bos_id), _special(eos_id), (PAD_LEFT if pad_left else 0) | (KEEP_TAIL if keep_tail else 0))
         res = {"input_ids": ids, "attention_mask": mask.view(torch.bool), "lengths": lengths}
-        if masking is None:
+        if denoise is not None:
+            res["labels"] = torch.empty((nd, int(target_length)), dtype=dtype, device=dev)
+            res["target_lengths"] = torch.empty((nd,), dtype=torch.int32, device=dev)
+            N.check(N.lib.tm_batch_collate_denoise(b, C.byref(how), C.byref(denoise.struct(target_length, seed)), None, st, ids.data_ptr(), res["labels"].data_ptr(),
+                                                   mask.data_ptr(), lengths.data_ptr(), res["target_lengths"].data_ptr(), None))
+        elif masking is None:
             N.check(N.lib.tm_batch_collate(b, C.byref(how), st, ids.data_ptr(), mask.data_ptr(), lengths.data_ptr()))
         else:
             res["labels"] = torch.empty((nd, max_length), dtype=dtype, device=dev)
@@ -489,13 +533,17 @@ class ResidentBatch:
     def length_order(self, descending=False):
         return self._order(descending)[0]
 
-    def collate(self, indices, max_length, *, pad_id, bos_id=None, eos_id=None, pad_left=False, keep_tail=False, dtype=None, masking=None, seed=0):
+    def collate(self, indices, max_length, *, pad_id, bos_id=None, eos_id=None, pad_left=False, keep_tail=False, dtype=None, masking=None, seed=0, denoise=None,
+                target_length=None):
         """row r = the row encode_batch gives document indices[r]: {"input_ids" [rows, max_length] of `dtype` (default int64), "attention_mask"
         [rows, max_length] bool, "lengths" [rows] int32, "bad_indices" int32 scalar on the device: the entries of `indices` that name no
         document - their rows are padding only}.  indices: an integer tensor (moved to the device if it is not there) or a sequence; a
         document may stand in any number of rows.  masking=Masking(...): the rows corrupted for a masked-LM step under `seed`, and "labels"
         [rows, max_length] of `dtype` beside them, as encode_batch gives them (tm_batch_collate_masked): a document is masked the same way in
-        whatever row or batch it stands, and differently under every seed."""
+        whatever row or batch it stands, and differently under every seed.  denoise=SpanCorruption(...) (not beside masking or pad_left): the
+        rows as the input of a T5-style denoising step, "labels" [rows, target_length] and "target_lengths" [rows] beside them, as encode_batch
+        gives them (tm_batch_collate_denoise)."""
+        _check_denoise(denoise, target_length, masking, None, pad_left)
         torch = _torch()
         dtype = dtype or torch.int64
         id_bytes = _check_dtype(torch, dtype)
@@ -518,8 +566,14 @@ class ResidentBatch:
             res = {"input_ids": ids, "attention_mask": mask.view(torch.bool), "lengths": lengths, "bad_indices": bad}
             if masking is not None:
                 res["labels"] = torch.empty((rows, max_length), dtype=dtype, device=self.dev)
+            if denoise is not None:
+                res["labels"] = torch.empty((rows, int(target_length)), dtype=dtype, device=self.dev)
+                res["target_lengths"] = torch.empty((rows,), dtype=torch.int32, device=self.dev)
             if not rows:
                 bad.zero_()
+            elif denoise is not None:
+                N.check(N.lib.tm_batch_collate_denoise(self.handle, C.byref(how), C.byref(denoise.struct(target_length, seed)), idx.data_ptr(), st, ids.data_ptr(),
+                                                       res["labels"].data_ptr(), mask.data_ptr(), lengths.data_ptr(), res["target_lengths"].data_ptr(), bad.data_ptr()))
             elif masking is None:
                 N.check(N.lib.tm_batch_collate_select(self.handle, C.byref(how), idx.data_ptr(), st, ids.data_ptr(), mask.data_ptr(), lengths.data_ptr(), bad.data_ptr()))
             else:

@@ -11,7 +11,8 @@ the median of 20.  --only pairs: the pair lines alone; --only fit: whole-documen
 300 000 and 1 048 576 short documents; --only select: tm_batch_collate_select through the identity, the length order and a random
 permutation beside tm_batch_collate of the same documents, and tm_batch_length_order beside torch.sort(stable=True) on 300 000 and 1 048 576
 documents and on either side of a digit boundary of the largest count; --only masked: tm_batch_collate_masked (int64 ids and labels) beside
-tm_batch_collate_select of the same rows at L = 512; --append: add to --out under a dated heading instead of replacing it.  (tm_batch_collate / tm_batch_pack wait for the batch's last run before they launch and tm_batch_pack_rows fetches two
+tm_batch_collate_select of the same rows at L = 512; --only denoise: tm_batch_collate_denoise (int64 inputs and targets of 128, spans of 1 .. 5 at
+density 0.15) beside tm_batch_collate_masked and tm_batch_collate_select of the same rows at L = 512, and a copy that writes the bytes it writes; --append: add to --out under a dated heading instead of replacing it.  (tm_batch_collate / tm_batch_pack wait for the batch's last run before they launch and tm_batch_pack_rows fetches two
 offsets: host time, outside the kernels but inside the events - with 256 MiB of text it is a few percent of a call.)"""
 import argparse
 import ctypes as C
@@ -48,7 +49,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mib", type=int, default=256)
     ap.add_argument("--out", default=os.path.join("profiles", "collate.txt"))
-    ap.add_argument("--only", choices=["pairs", "fit", "select", "masked"], default=None)
+    ap.add_argument("--only", choices=["pairs", "fit", "select", "masked", "denoise"], default=None)
     ap.add_argument("--append", action="store_true")
     a = ap.parse_args()
     L = 2048
@@ -66,7 +67,7 @@ def main():
     N.check(N.lib.tm_batch_totals(b, C.byref(total), None))
     n_ids, pad, eos = int(total.value), v.n_ids(), v.n_ids() + 1
     lines = ["%d MiB of englishcode-32000 text, %d documents, %d ids, L = %s; median of 20 (min .. max), GB/s = bytes read + written" % (
-        a.mib, nd, n_ids, "512" if a.only in ("pairs", "masked") else "%d (the pair lines: 512)" % L)]
+        a.mib, nd, n_ids, "512" if a.only in ("pairs", "masked", "denoise") else "%d (the pair lines: 512)" % L)]
 
     def copy_rate(nbytes):
         src = torch.empty(nbytes // 2, dtype=torch.uint8, device="cuda")
@@ -219,6 +220,34 @@ def main():
             report("masked + labels, %s" % name, nbytes + nd * LM * 8, med, lo, hi)
             lines.append("  (masked / select in time: %.2f; %.1f%% of the content ids selected)" % (med / smed, 100.0 * int((labels != -100).sum().item()) / max(int(lens.to(torch.int64).sum().item()), 1)))
 
+    def denoise_lines():
+        """tm_batch_collate_denoise, int64 inputs + int64 targets of 128 + mask + both lengths, beside tm_batch_collate_masked (the yardstick: the same
+        Philox over the same ids) and tm_batch_collate_select of the SAME rows (a random permutation of every document, L = 512), spans of 1 .. 5 at
+        density 0.15, and a device-to-device copy that writes as many bytes as the denoise call writes."""
+        LM, TL = 512, 128
+        ids, labels = (torch.empty((nd, LM), dtype=torch.int64, device="cuda") for _ in range(2))
+        targets = torch.empty((nd, TL), dtype=torch.int64, device="cuda")
+        mask = torch.empty((nd, LM), dtype=torch.uint8, device="cuda")
+        lens, tlens = (torch.empty((nd,), dtype=torch.int32, device="cuda") for _ in range(2))
+        idx = torch.randperm(nd, device="cuda").to(torch.int32)
+        how = torch_api._Collate(0, nd, LM, 8, pad, N.TM_NONE, eos, 0)
+        smed, lo, hi = timed(lambda: N.check(N.lib.tm_batch_collate_select(b, C.byref(how), idx.data_ptr(), st, ids.data_ptr(), mask.data_ptr(), lens.data_ptr(), None)), stream)
+        read = (int(lens.to(torch.int64).sum().item()) - nd) * 4 + nd * 4
+        report("select int64 + mask + lengths, L = %d" % LM, read + nd * LM * 9 + nd * 4, smed, lo, hi)
+        m = torch_api.Masking(mask_id=eos + 1, span=(1, 5)).struct(v, 1)
+        mmed, lo, hi = timed(lambda: N.check(N.lib.tm_batch_collate_masked(b, C.byref(how), C.byref(m), idx.data_ptr(), st, ids.data_ptr(), labels.data_ptr(), mask.data_ptr(),
+                                                                          lens.data_ptr(), None)), stream)
+        report("masked + labels, spans 1 .. 5", read + nd * LM * 17 + nd * 4, mmed, lo, hi)
+        dn = torch_api.SpanCorruption(eos + 100, noise_density=0.15, span=(1, 5)).struct(TL, 1)
+        dmed, lo, hi = timed(lambda: N.check(N.lib.tm_batch_collate_denoise(b, C.byref(how), C.byref(dn), idx.data_ptr(), st, ids.data_ptr(), targets.data_ptr(), mask.data_ptr(),
+                                                                           lens.data_ptr(), tlens.data_ptr(), None)), stream)
+        written = nd * LM * 9 + nd * TL * 8 + nd * 8
+        report("denoise + targets of %d, spans 1 .. 5" % TL, read + written, dmed, lo, hi)
+        cgbs, cmed = copy_rate(2 * written)
+        lines.append("  (denoise / masked in time: %.2f; denoise / select: %.2f; a copy that writes its %d MB: %.3f ms; %d of %d targets cut at %d, %.1f%% of the input entries kept)" % (
+            dmed / mmed, dmed / smed, written >> 20, cmed, int((tlens > TL).sum().item()), nd, TL, 100.0 * int(lens.to(torch.int64).sum().item()) / max(read // 4, 1)))
+        print(lines[-1], flush=True)
+
     def order_lines(k, W, top):
         """tm_batch_length_order on k documents of 0 .. 255 ids each, one of them of `top` ids (tm_batch_load_ids of rows of W two-byte ids), beside
         torch.sort(stable=True) of the same counts on the same device; the order is checked against torch's"""
@@ -239,12 +268,14 @@ def main():
         print(lines[-1], flush=True)
         N.lib.tm_batch_free(bk)
 
-    if a.only in ("pairs", "fit", "select", "masked"):
+    if a.only in ("pairs", "fit", "select", "masked", "denoise"):
         with torch.cuda.stream(stream):
             if a.only == "pairs":
                 pairs_lines()
             elif a.only == "masked":
                 masked_lines()
+            elif a.only == "denoise":
+                denoise_lines()
             elif a.only == "select":
                 select_lines()
                 for k, W, top in ((300000, 256, 255), (1048576, 256, 255), (1048576, 257, 256), (4096, 65537, 65535), (4096, 65537, 65536)):
